@@ -14,17 +14,26 @@ Workloads (--workload, default "auto" = C2 on one GPU, C5 on sever
       (sharding.shard_hops), every rank runs ONE launch of the fused kernel over its hops' frame
       ranges (rpf_accumulate_device_hops: accumulators handed over and zeroed at hop boundaries) and the
       per-bin accumulators meet in ONE asynchronous RCCL reduce of 8 x 4096 doubles per
-      scan, overlapped with the next scan's kernels.  Rank 0 checks the reduced spectra
-      against the committed float64 fixtures (tests/golden/c5_hop*.npz) before printing.
+      scan, overlapped with the next scan's kernels.  With --full, rank 0 checks the reduced
+      spectra against the committed float64 fixtures (tests/golden/c5_hop*.npz) before printing.
 With C2/C3/C4 on several GPUs every rank runs its own acquisitions (weak scaling).
 
 Successive steps walk a ring of distinct replay buffers whose total size exceeds the
 256 MiB Infinity Cache, so every step reads its bytes from HBM.
 
 Timing: an untimed pre-warm of >= 0.2 s (clocks, caches, lazy HIP state), then W warm-up
-steps, then EXACTLY K steps between barrier + synchronize; when one such region is shorter
-than 0.5 s it is repeated and the MEDIAN region is reported (regions listed in
-"timing"), so a 20-step run reports what a 2000-step run reports.
+steps, then ONE region of exactly K steps between barrier + synchronize; `ms_per_step` is that
+region's time over K.
+
+A plain run does only that.  `--full` adds what the headline does not need: HIP-event brackets of
+the fused kernel inside the timed region and the roofline built on them, the CPU baseline, the
+end-to-end (pinned host buffer) legs, C5's one-GPU comparator and the check of the reduced C5
+spectra against the committed fixtures.
+
+`--dump-outputs DIR` writes, after the timed region, what its last step computed on rank 0 as
+DIR/power.npy (float64): the spectrum of the last acquisition (C2-C4, shape [N]) or the spectra
+of the last scan's hops (C5, shape [hops, N]).  The inputs are seeded, so runs with the same
+arguments see the same bytes.
 
 Ranks: `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N
 ranks itself (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same
@@ -57,8 +66,6 @@ CLOCK_GHZ = 2.4                # peak shader clock used for the issue-slot fract
 N_CUS = 256
 CPU_BASELINE_SECONDS = 10.0
 PREWARM_SECONDS = 0.2
-MIN_REGION_SECONDS = 0.5
-MAX_REGIONS = 25
 
 WORKLOADS = {
     "C2": dict(N=4096, R=10000, window=False, seed=2),
@@ -299,11 +306,17 @@ def build_parser():
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks of the job, one per device; > 1 without WORLD_SIZE in the environment: bench.py "
                          "starts them itself under torch.distributed.run")
-    ap.add_argument("--steps", type=int, default=None, help="default: 2000 (C2/C3), 200 (C5), 100 (C4)")
+    ap.add_argument("--steps", type=positive_int, default=None,
+                    help="timed steps, all in one region; default: 2000 (C2/C3), 200 (C5), 100 (C4)")
     ap.add_argument("--warmup", type=int, default=None, help="default: steps / 20")
     ap.add_argument("--replay-buffers", type=int, default=0, help="0 = enough to exceed the Infinity Cache")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel brackets and roofline, CPU baseline, end-to-end legs, C5's one-GPU comparator "
+                         "and fixture check (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/power.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="(--full) skip the end-to-end legs")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed and run the reduce even with one rank")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
@@ -326,8 +339,15 @@ def build_parser():
                     help="C5: consecutive scans whose hops share ONE persistent kernel launch (a scan's hops already do); "
                          "0 = as many as divide --scans-per-reduce and fit rpf_max_hops_per_launch(); 1 = a launch per scan")
     ap.add_argument("--event-every", type=int, default=8,
-                    help="bracket the fused kernel with HIP events on every k-th timed step")
+                    help="(--full) bracket the fused kernel with HIP events on every k-th timed step")
     return ap
+
+
+def positive_int(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError("must be at least 1, got %d" % value)
+    return value
 
 
 def scans_per_launch(per_block, shards_max, max_hops, asked=0):
@@ -580,12 +600,14 @@ def main():
         torch.cuda.synchronize()
 
     # this rank's own spectrum of its first shard in replay buffer 0 (checked against the CPU oracle below)
-    d_chk = torch.zeros(N, dtype=torch.float64, device=dev)
-    ds.accumulate_device(base[0].data_ptr(), 2 * N * mine[0][2], mine[0][2], d_chk.data_ptr(), s)
-    torch.cuda.synchronize()
-    pwr_first = d_chk.cpu().numpy().copy()
+    pwr_first = None
+    if args.full:
+        d_chk = torch.zeros(N, dtype=torch.float64, device=dev)
+        ds.accumulate_device(base[0].data_ptr(), 2 * N * mine[0][2], mine[0][2], d_chk.data_ptr(), s)
+        torch.cuda.synchronize()
+        pwr_first = d_chk.cpu().numpy().copy()
 
-    # ---- untimed pre-warm, warm-up, timed regions ----------------------------------------------
+    # ---- untimed pre-warm, warm-up, timed region -----------------------------------------------
     t0 = time.perf_counter()
     i = 0
     while True:
@@ -605,47 +627,48 @@ def main():
     fence(args.warmup - 1 if args.warmup else None)
 
     events = []
-    regions = []
-    my_regions = []
     last_blk = 0
     fused_before = ds.fused_status()
-    while True:
-        t0 = time.perf_counter()
-        for i in range(args.steps):
-            ev = None
-            # (C5: only the steps that launch -- every k_scan-th -- and only whole batches, so that the brackets are
-            #  all launches of the same size)
-            if args.event_every > 0 and i % args.event_every == 0 and len(events) < 4096 and (
-                    not strong or (i % k_scan == 0 and i + k_scan <= args.steps)):
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                events.append(ev)
-            last_blk = step(i, ev, limit=args.steps)
-        fence(args.steps - 1)
-        elapsed = time.perf_counter() - t0
-        my_regions.append(elapsed)
-        if use_dist:
-            t = torch.tensor([elapsed], dtype=torch.float64, device=ctrl_dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            elapsed = float(t.item())
-        regions.append(elapsed)
-        # repeat short regions (decided on the max-over-ranks time, so every rank agrees)
-        target = min(MAX_REGIONS, max(1, int(math.ceil(MIN_REGION_SECONDS / max(regions[0], 1e-9)))))
-        if len(regions) >= target:
-            break
-    elapsed = float(np.median(regions))
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        ev = None
+        # (C5: only the steps that launch -- every k_scan-th -- and only whole batches, so that the brackets are
+        #  all launches of the same size)
+        if args.full and args.event_every > 0 and i % args.event_every == 0 and len(events) < 4096 and (
+                not strong or (i % k_scan == 0 and i + k_scan <= args.steps)):
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            events.append(ev)
+        last_blk = step(i, ev, limit=args.steps)
+    fence(args.steps - 1)
+    my_elapsed = elapsed = time.perf_counter() - t0
+    if use_dist:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=ctrl_dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
     # A fused four-step launch that gives up returns RPF_OK and a NaN spectrum (include/rpf_engine.h): a timed region that
     # contains one has timed work that produced nothing, and its line would be invalid.
     fused_after = ds.fused_status()
     if fused_after["gave_up"] > fused_before["gave_up"]:
-        print("bench.py: rank %d: %d fused four-step launch(es) gave up inside the timed regions (NaN spectra): no line"
+        print("bench.py: rank %d: %d fused four-step launch(es) gave up inside the timed region (NaN spectra): no line"
               % (rank, fused_after["gave_up"] - fused_before["gave_up"]), file=sys.stderr)
         sys.exit(3)
 
+    # ---- what the last timed step computed: one spectrum (C2-C4) or the last scan's hops (C5) -------
+    last_sub = (args.steps - 1) % per_block
+    if strong:
+        # after the reduce rank 0 holds every hop; a rank of its own (one process, or --shard-as) only its shards
+        out_hops = list(range(hops)) if world > 1 and not args.shard_as else [m[0] for m in mine]
+        last_rows = [row_of(hop, last_sub) for hop in out_hops]
+    else:
+        last_rows = last_sub
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "power.npy"), d_pwr[last_blk][last_rows].cpu().numpy())
+
     # ---- C5: the reduced spectra of the last scan against the committed fixtures -----------------
     check = None
-    if strong and rank == 0 and not args.shard_as:
-        last_sub = (args.steps - 1) % per_block
-        got = d_pwr[last_blk][[row_of(hop, last_sub) for hop in range(hops)]].cpu().numpy()
+    if args.full and strong and rank == 0 and not args.shard_as:
+        got = d_pwr[last_blk][last_rows].cpu().numpy()
         worst = 0.0
         for hop in range(hops):
             g = np.load(os.path.join(ROOT, "tests", "golden", "c5_hop%d_n4096_r5000.npz" % hop))
@@ -680,7 +703,7 @@ def main():
         return h5 * r5 * n5 * per * nlaunch / (time.perf_counter() - t0), per
 
     one_gpu = None
-    if (strong and not args.shard_as) or (name == "C2" and world == 1 and selected.startswith("auto")):
+    if args.full and ((strong and not args.shard_as) or (name == "C2" and world == 1 and selected.startswith("auto"))):
         if rank == 0:
             one_gpu = one_gpu_scan_rate()
         if use_dist:
@@ -689,7 +712,7 @@ def main():
     # every rank's own view of the timed region (so that a multi-GPU run explains itself): its wall time
     # for the K steps, its fused-kernel bracket, what it processed
     k1_all = [a.elapsed_time(b) for a, b in events]
-    mine_report = {"rank": rank, "device": torch.cuda.get_device_name(dev), "device_index": dev.index or 0, "region_s_median": float(np.median(my_regions)),
+    mine_report = {"rank": rank, "device": torch.cuda.get_device_name(dev), "device_index": dev.index or 0, "region_s": my_elapsed,
                    "kernel_ms_median": float(np.median(k1_all)) if k1_all else None,
                    "frames_per_step": sum(m[2] for m in mine) if strong else mine[0][2],
                    "hops_per_step": len(mine) if strong else 1,
@@ -773,8 +796,7 @@ def main():
                            "gloo (staged through pinned host memory)" if gloo else "RCCL",
                            rows, N, ("%d scans" % per_block if per_block > 1 else "scan") if strong else "8 steps"))
                        if use_dist else "none"},
-            "timing": {"prewarm_steps": prewarm_steps, "regions_s": regions, "reported": "median region",
-                       "min_region_s": min(regions), "max_region_s": max(regions)},
+            "timing": {"prewarm_steps": prewarm_steps, "region_s": elapsed},
             "roofline": roof,
         }
         if use_dist:
@@ -805,7 +827,7 @@ def main():
                 out["one_gpu_same_workload"] = ref
             else:       # the C2 line of a one-rank run: what a --gpus N > 1 run of this script (C5) is to be divided by
                 out["multi_gpu_reference"] = dict(ref, workload_name="C5")
-        if world == 1 and not args.force_dist:
+        if args.full and world == 1 and not args.force_dist:
             # rank 0's first shard on the host for the CPU legs
             host = base[0].cpu().numpy()
             fr = mine[0][2]

@@ -19,6 +19,15 @@ def parse(*argv):
     return bench.build_parser().parse_args(list(argv))
 
 
+def test_plain_run_is_the_default_and_steps_are_counted():
+    args = parse("--gpus", "1", "--steps", "20", "--warmup", "5")
+    assert args.full is False and args.dump_outputs is None and args.steps == 20
+    args = parse("--full", "--dump-outputs", "out")
+    assert args.full is True and args.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        parse("--steps", "0")
+
+
 def test_one_rank_or_existing_ranks_run_in_process():
     assert bench.plan_launch(parse(), [], {}, 1) is None
     assert bench.plan_launch(parse("--gpus", "1"), ["--gpus", "1"], {}, 8) is None

@@ -224,12 +224,12 @@ def _bench_line(args, env_extra=None, nproc=0):
 
 
 def test_bench_c5_line_through_rccl_is_checked_against_the_fixtures():
-    """bench.py --workload C5 with torch.distributed initialised (RCCL, world size 1 on this box):
+    """bench.py --workload C5 --full with torch.distributed initialised (RCCL, world size 1 on this box):
     the strong-scaling line carries the check of the REDUCED spectra against the committed C5
     fixtures, the same-workload one-GPU figure and what RCCL saw, and stdout is the one JSON line (RCCL's banner goes
     to stderr).  Two consecutive scans share a launch at one rank (8 hops x 2 = the kernel's 16-entry hop table); an odd
     step count leaves a ragged tail that goes hop by hop."""
-    d = _bench_line(["--workload", "C5", "--force-dist", "--steps", "9", "--warmup", "2", "--no-cpu-baseline"])
+    d = _bench_line(["--workload", "C5", "--force-dist", "--steps", "9", "--warmup", "2", "--full", "--no-cpu-baseline"])
     assert d["scaling"] == "strong" and d["n_gpus"] == 1 and d["config"]["reduce"].startswith("one async RCCL reduce")
     assert d["check"]["hops"] == 8 and d["check"]["reduced_spectra_vs_float64_fixtures_max_rel"] < PARITY
     assert d["value"] > 5e10 and d["roofline"]["frac"] > 0.05
@@ -237,16 +237,46 @@ def test_bench_c5_line_through_rccl_is_checked_against_the_fixtures():
     assert d["rccl"]["world_size"] == 1 and d["rccl"]["version"] and d["rccl"]["backend"] == "nccl"
     assert d["one_gpu_same_workload"]["value"] > 5e10
     # a launch per scan (round 5's form) gives the same spectra
-    d1 = _bench_line(["--workload", "C5", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--scans-per-launch", "1"])
+    d1 = _bench_line(["--workload", "C5", "--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline",
+                      "--scans-per-launch", "1"])
     assert d1["config"]["scans_per_launch"] == 1 and d1["check"]["reduced_spectra_vs_float64_fixtures_max_rel"] < PARITY
 
 
 def test_bench_default_line_carries_the_multi_gpu_reference():
-    """`python bench.py` (one rank: config C2, the metric): the line also carries config C5's one-GPU rate, the
+    """`python bench.py --full` (one rank: config C2, the metric): the line also carries config C5's one-GPU rate, the
     denominator of the C5 lines a `--gpus N > 1` run of the same script prints."""
-    d = _bench_line(["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-end-to-end"])
+    d = _bench_line(["--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-end-to-end"])
     assert d["config"]["workload_name"] == "C2" and d["scaling"] == "weak" and d["n_gpus"] == 1
     assert d["multi_gpu_reference"]["workload_name"] == "C5" and d["multi_gpu_reference"]["value"] > 5e10
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_last_step(c2, tmp_path):
+    """A plain run (no --full) times exactly --steps steps in one region and carries nothing --full owns;
+    --dump-outputs writes the last timed step's spectrum.  With 3 replay buffers, step 7 reads buffer 0: the
+    unrotated C2 stream, whose spectrum the C-ABI gives directly."""
+    stream, d_in, dev = c2
+    d = _bench_line(["--steps", "7", "--warmup", "2", "--replay-buffers", "3", "--dump-outputs", str(tmp_path)])
+    assert d["config"]["workload_name"] == "C2" and d["steps"] == 7 and d["warmup"] == 2
+    assert d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] == pytest.approx(d["timing"]["region_s"] * 1e3 / 7)
+    assert d["value"] == pytest.approx(N * R * 7 / d["timing"]["region_s"])
+    assert d["roofline"] is None and not {"cpu_baseline", "end_to_end", "multi_gpu_reference"} & set(d)
+    got = np.load(tmp_path / "power.npy")
+    assert got.dtype == np.float64 and got.shape == (N,)
+    with rpf.Datastore(rpf.Params(N=N, repeats=R)) as ds:
+        want = device_run(ds, d_in, 0, R, dev)
+    assert max_rel(got, want) < ADDITIVITY
+
+
+def test_bench_c5_dump_is_the_last_scan(tmp_path):
+    """--workload C5 --dump-outputs: the last timed scan's 8 spectra (3 steps: one launch of two scans, then a ragged
+    tail hop by hop), each against its float64 fixture; without --full the line carries no check of its own."""
+    d = _bench_line(["--workload", "C5", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 3 and "check" not in d and "one_gpu_same_workload" not in d
+    got = np.load(tmp_path / "power.npy")
+    assert got.dtype == np.float64 and got.shape == (8, N)
+    for hop in range(8):
+        assert max_rel(got[hop], load_golden(C5_CASES[hop])["pwr"]) < PARITY
 
 
 def test_bench_c5_two_ranks():
@@ -255,7 +285,7 @@ def test_bench_c5_two_ranks():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU on this box: the 2-rank RCCL run needs two")
-    d = _bench_line(["--gpus", "2", "--steps", "8", "--warmup", "2"])
+    d = _bench_line(["--gpus", "2", "--steps", "8", "--warmup", "2", "--full"])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["workload_name"] == "C5"
     assert len(d["per_rank"]) == 2 and {p["rank"] for p in d["per_rank"]} == {0, 1}
     assert d["check"]["reduced_spectra_vs_float64_fixtures_max_rel"] < PARITY
@@ -285,7 +315,7 @@ def test_bench_c5_rehearsal_ranks_share_one_gpu(ranks, form):
     exact command -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N ...`, ranks from the environment.  10 steps: two whole
     blocks of four scans and a ragged one."""
-    args = ["--gpus", str(ranks), "--dist-backend", "gloo", "--share-device", "--steps", "10", "--warmup", "2"]
+    args = ["--gpus", str(ranks), "--dist-backend", "gloo", "--share-device", "--steps", "10", "--warmup", "2", "--full"]
     d = _bench_line(args, nproc=ranks if form == "driver" else 0)
     assert d["n_gpus"] == ranks and d["scaling"] == "strong" and d["config"]["workload_name"] == "C5"
     assert "rehearsal" in d and "gloo" in d["config"]["reduce"]

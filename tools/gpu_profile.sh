@@ -10,16 +10,16 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
 date -u +%Y-%m-%dT%H:%M:%SZ > $OUT/captured.txt
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end > $OUT/bench_20steps.json 2>> $OUT/bench.err
-python bench.py --workload C3 --no-cpu-baseline --no-end-to-end > $OUT/c3_bench.json 2> $OUT/c3_bench.err
-python bench.py --workload C4 --no-end-to-end > $OUT/c4_bench.json 2> $OUT/c4_bench.err
-python bench.py --workload C5 --no-cpu-baseline --no-end-to-end > $OUT/c5_bench.json 2> $OUT/c5_bench.err
-python bench.py --workload C5 --force-dist --no-cpu-baseline > $OUT/c5_rccl_bench.json 2>> $OUT/c5_bench.err
-python bench.py --workload C5 --shard-as 8 --no-cpu-baseline --no-end-to-end > $OUT/c5_shard8_bench.json 2>> $OUT/c5_bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end > $OUT/bench_20steps.json 2>> $OUT/bench.err
+python bench.py --full --workload C3 --no-cpu-baseline --no-end-to-end > $OUT/c3_bench.json 2> $OUT/c3_bench.err
+python bench.py --full --workload C4 --no-end-to-end > $OUT/c4_bench.json 2> $OUT/c4_bench.err
+python bench.py --full --workload C5 --no-cpu-baseline --no-end-to-end > $OUT/c5_bench.json 2> $OUT/c5_bench.err
+python bench.py --full --workload C5 --force-dist --no-cpu-baseline > $OUT/c5_rccl_bench.json 2>> $OUT/c5_bench.err
+python bench.py --full --workload C5 --shard-as 8 --no-cpu-baseline --no-end-to-end > $OUT/c5_shard8_bench.json 2>> $OUT/c5_bench.err
 cut -c1-200 $OUT/bench.json $OUT/c4_bench.json $OUT/c5_bench.json
 cd /tmp && export TMPDIR=/tmp
-B="--steps 400 --warmup 40 --no-cpu-baseline --no-end-to-end"
+B="--steps 400 --warmup 40 --full --no-cpu-baseline --no-end-to-end"
 prof() {   # name, bench args...
   local name=$1; shift
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${name}_trace -o $name -- python $ROOT/bench.py "$@" > $OUT/${name}_trace.log 2>&1
@@ -29,8 +29,8 @@ prof() {   # name, bench args...
 }
 prof c2 $B
 prof c3 $B --workload C3
-prof c4 --workload C4 --steps 20 --warmup 3 --no-cpu-baseline --no-end-to-end
-prof c5 --workload C5 --steps 100 --warmup 10 --no-cpu-baseline --no-end-to-end
+prof c4 --workload C4 --full --steps 20 --warmup 3 --no-cpu-baseline --no-end-to-end
+prof c5 --workload C5 --full --steps 100 --warmup 10 --no-cpu-baseline --no-end-to-end
 timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d $OUT/c2_pmc_sq -o c2 -- python $ROOT/bench.py $B > $OUT/c2_pmc_sq.log 2>&1
 timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/c2_pmc_lds -o c2 -- python $ROOT/bench.py $B > $OUT/c2_pmc_lds.log 2>&1
 cd $ROOT

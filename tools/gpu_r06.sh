@@ -34,7 +34,7 @@ fourstep)
   for rep in 1 2 3; do
     for v in ${FS_VARIANTS:-shipped fswlast fswdbl f32pass}; do
       lib=; [ $v != shipped ] && lib=$ROOT/rtl-power-fftw_amd/librpf_engine_$v.so
-      RPF_ENGINE_LIB=$lib timeout 300 python bench.py --workload C4 --no-cpu-baseline --no-end-to-end > $OUT/c4_${v}_$rep.json 2> $OUT/c4_${v}_$rep.err
+      RPF_ENGINE_LIB=$lib timeout 300 python bench.py --full --workload C4 --no-cpu-baseline --no-end-to-end > $OUT/c4_${v}_$rep.json 2> $OUT/c4_${v}_$rep.err
       bench_val $OUT/c4_${v}_$rep.json "C4 $v run $rep:"
     done
   done
@@ -52,14 +52,14 @@ k1)
 c5)
   timeout 900 python -m pytest tests/test_gpu_fullsize.py -m gpu -x -q -k "bench" > $OUT/c5_pytest.log 2>&1; echo "pytest rc=$?"; tail -5 $OUT/c5_pytest.log
   for k in 0 1; do
-    timeout 300 python bench.py --workload C5 --scans-per-launch $k --no-cpu-baseline --no-end-to-end > $OUT/c5_one_gpu_k$k.json 2> $OUT/c5_one_gpu_k$k.err; bench_val $OUT/c5_one_gpu_k$k.json "C5 one GPU, --scans-per-launch $k:"
+    timeout 300 python bench.py --full --workload C5 --scans-per-launch $k --no-cpu-baseline --no-end-to-end > $OUT/c5_one_gpu_k$k.json 2> $OUT/c5_one_gpu_k$k.err; bench_val $OUT/c5_one_gpu_k$k.json "C5 one GPU, --scans-per-launch $k:"
     for n in 2 4 8; do
-      timeout 300 python bench.py --workload C5 --shard-as $n --scans-per-launch $k --no-cpu-baseline --no-end-to-end > $OUT/c5_shard_as${n}_k$k.json 2> $OUT/c5_shard_as${n}_k$k.err; bench_val $OUT/c5_shard_as${n}_k$k.json "C5 --shard-as $n, --scans-per-launch $k:"
-      timeout 300 python bench.py --workload C5 --shard-as $n --scans-per-launch $k --force-dist --no-cpu-baseline --no-end-to-end > $OUT/c5_shard_as${n}_k${k}_rccl.json 2> $OUT/c5_shard_as${n}_k${k}_rccl.err; bench_val $OUT/c5_shard_as${n}_k${k}_rccl.json "   ... + a one-rank RCCL reduce per 4 scans:"
+      timeout 300 python bench.py --full --workload C5 --shard-as $n --scans-per-launch $k --no-cpu-baseline --no-end-to-end > $OUT/c5_shard_as${n}_k$k.json 2> $OUT/c5_shard_as${n}_k$k.err; bench_val $OUT/c5_shard_as${n}_k$k.json "C5 --shard-as $n, --scans-per-launch $k:"
+      timeout 300 python bench.py --full --workload C5 --shard-as $n --scans-per-launch $k --force-dist --no-cpu-baseline --no-end-to-end > $OUT/c5_shard_as${n}_k${k}_rccl.json 2> $OUT/c5_shard_as${n}_k${k}_rccl.err; bench_val $OUT/c5_shard_as${n}_k${k}_rccl.json "   ... + a one-rank RCCL reduce per 4 scans:"
     done
   done
   for n in 2 8; do
-    timeout 600 python bench.py --gpus $n --dist-backend gloo --share-device --steps 50 --warmup 5 > $OUT/c5_${n}rank_gloo.json 2> $OUT/c5_${n}rank_gloo.err; echo "rehearsal $n ranks rc=$?"
+    timeout 600 python bench.py --full --gpus $n --dist-backend gloo --share-device --steps 50 --warmup 5 > $OUT/c5_${n}rank_gloo.json 2> $OUT/c5_${n}rank_gloo.err; echo "rehearsal $n ranks rc=$?"
     python3 -c "import json;d=json.load(open('$OUT/c5_${n}rank_gloo.json'));print(d['n_gpus'], d['value']/1e9, d['check'], d['rccl'], d['config']['scans_per_launch'])"
   done
   ;;
