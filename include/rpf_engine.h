@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define RPF_ABI_VERSION 2   /* 2: rpf_accumulate_device_hops, rpf_device_fused_hops, rpf_scan_reducer_* */
+#define RPF_ABI_VERSION 2   /* 2: rpf_accumulate_device_hops, rpf_device_fused_hops, rpf_scan_reducer_*;
+                               additive within 2: rpf_config::frame_step, rpf_frames_in, rpf_frame_span */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -51,6 +52,16 @@ typedef struct rpf_config {
     int64_t buffer_capacity;  /* params.buf_length in bytes (params.h:43)         */
     int32_t device;           /* HIP device ordinal                               */
     uint32_t flags;           /* RPF_FLAG_*                                       */
+    /* Appended within ABI 2 (struct_size tells the two forms apart: a config of
+     * offsetof(rpf_config, frame_step) = 40 bytes, which ends at `flags`, means
+     * frame_step = N).  Frame step S in complex samples, 1 <= S <= N; 0 = N.
+     * Frame f is samples [f S, f S + N) = bytes [2 f S, 2 f S + 2N) of the stream:
+     * S < N overlaps consecutive frames (Welch averaging).  Each frame is unpacked
+     * as always -- -127, (-1)^n, window -- with n the index INSIDE the frame.  A
+     * stream of B bytes holds frames(B) = B < 2N ? 0 : (B - 2N) / (2S) + 1 frames
+     * (rpf_frames_in); every entry point counts frames that way.  S < 0 or S > N:
+     * RPF_ERR_INVALID_ARGUMENT from rpf_engine_create, before any device is touched. */
+    int32_t frame_step;
 } rpf_config;
 
 #define RPF_FLAG_NONE 0u
@@ -159,7 +170,7 @@ int rpf_stream_unregister(rpf_engine* e, const void* stream);
  * what a launch needs -- a call that needs more than any before it synchronises `hip_stream` once, frees and
  * allocates); d_pwr_out[N] (device doubles, 16-byte aligned -- the reduce stores
  * bin pairs -- else RPF_ERR_INVALID_ARGUMENT; the same holds for every d_pwr_out below) is
- * overwritten with the sum over frames [0, min(repeats, nbytes/(2N))).  Used by bench.py and the
+ * overwritten with the sum over frames [0, min(repeats, rpf_frames_in(e, nbytes))).  Used by bench.py and the
  * full-size parity tests; does not touch the buffer queues. */
 int rpf_accumulate_device(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
                           double* d_pwr_out, void* hip_stream, int64_t* repeats_done);
@@ -175,7 +186,7 @@ int rpf_device_reduce(rpf_engine* e, double* d_pwr_out, void* hip_stream);
 
 /* A whole scan in one call: n_hops device-resident acquisitions (the reference's scan is a loop of
  * hops, /root/reference/src/rtl_power_fftw.cxx:133-174, each starting from a zeroed accumulator,
- * acquisition.cxx:252-254).  Hop h = the first min(repeats[h], nbytes[h]/(2N)) frames of
+ * acquisition.cxx:252-254).  Hop h = the first min(repeats[h], rpf_frames_in(e, nbytes[h])) frames of
  * d_streams[h]; its spectrum goes to d_pwr_out[h*N .. h*N+N) (device doubles, overwritten; zeros
  * for a hop without a whole frame).  For the sizes the LDS-resident kernel serves (powers of two
  * 64 .. 8192) up to rpf_max_hops_per_launch() hops share ONE persistent kernel launch -- the
@@ -191,6 +202,15 @@ int rpf_accumulate_device_hops(rpf_engine* e, const void* const* d_streams, cons
 int rpf_device_fused_hops(rpf_engine* e, const void* const* d_streams, const size_t* nbytes,
                           const int64_t* repeats, int n_hops, void* hip_stream, int64_t* repeats_done);
 int rpf_max_hops_per_launch(void);
+
+/* Pure helpers on the engine's N and frame step S, so that callers never re-derive the formula:
+ * frames(nbytes) = nbytes < 2N ? 0 : (nbytes - 2N) / (2S) + 1, and the bytes `frames` frames span,
+ * 2N + 2S (frames - 1) (0 for no frame).  With S != N: rpf_accumulate_device_hops runs hop by hop
+ * (the scan kernel reads frames side by side), rpf_device_fused_hops returns RPF_ERR_INVALID_ARGUMENT,
+ * and so does rpf_device_fused on a size the LDS-resident K1 does not serve (rpf_accumulate_device is
+ * the general entry point). */
+int64_t rpf_frames_in(const rpf_engine* e, size_t nbytes);
+size_t rpf_frame_span(const rpf_engine* e, int64_t frames);
 
 /* Datastore::pwr as it sits in HBM after rpf_finish: copied (device to device, or peer to peer when
  * dst_device is another device) into d_dst[N]; synchronises hip_stream before returning. */

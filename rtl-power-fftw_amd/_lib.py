@@ -40,7 +40,12 @@ class rpf_config(ctypes.Structure):
         ("buffer_capacity", ctypes.c_int64),
         ("device", ctypes.c_int32),
         ("flags", ctypes.c_uint32),
+        ("frame_step", ctypes.c_int32),      # appended within ABI 2: 0 = N
     ]
+
+
+# rpf_config of ABI 2's first form (up to `flags`): frame step N
+CONFIG_SIZE_V2_0 = rpf_config.frame_step.offset
 
 
 FLAG_NO_LDS_DMA = 1
@@ -79,6 +84,8 @@ _SYMBOLS = [
                                              ctypes.POINTER(ctypes.c_int64), ctypes.c_int, _P,
                                              ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_max_hops_per_launch", ctypes.c_int, []),
+    ("rpf_frames_in", ctypes.c_int64, [_P, ctypes.c_size_t]),
+    ("rpf_frame_span", ctypes.c_size_t, [_P, ctypes.c_int64]),
     ("rpf_copy_power_device", ctypes.c_int, [_P, _P, _P, ctypes.c_int]),
     ("rpf_scan_reducer_create", ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.POINTER(_P)]),

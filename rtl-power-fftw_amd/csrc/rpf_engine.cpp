@@ -70,6 +70,7 @@ struct StagingSlot {
 struct rpf_engine {
     // configuration (Params fields Datastore reads)
     int N = 0;
+    int step = 0;                 // frame step S in complex samples (rpf_config::frame_step; N = frames side by side)
     bool has_window = false;
     int n_buffers = 0;
     size_t buffer_capacity = 0;
@@ -134,6 +135,8 @@ struct rpf_engine {
     size_t scratch_bytes = 0;             // its size now; grown on demand (two-kernel four-step and large Bluestein paths)
     size_t scratch_per_frame = 0, scratch_max = 0;
     rpf::cf* d_step2 = nullptr;           // large Bluestein: second transform's inter-step twiddles
+    uint8_t* d_gather = nullptr;          // overlapped frames on the non-K1 families: one chunk, side by side
+    int64_t gather_frames = 0;            // ... frames it holds (kGatherBytes / 2N, at least one)
     float* d_window = nullptr;
     double* d_partial = nullptr;
     double* d_pwr = nullptr;
@@ -175,6 +178,26 @@ int fail(rpf_engine* e, int rc, const std::string& msg)
     if (e) e->last_error = msg;
     g_last_error = msg;
     return rc;
+}
+
+// frames(B) of a stream of B bytes at frame step S: frame f is bytes [2fS, 2fS + 2N).
+int64_t frames_in(const rpf_engine* e, size_t nbytes)
+{
+    const size_t frame = 2 * static_cast<size_t>(e->N), step = 2 * static_cast<size_t>(e->step);
+    return nbytes < frame ? 0 : static_cast<int64_t>((nbytes - frame) / step + 1);
+}
+
+// Bytes `frames` frames span: 2N + 2S (frames - 1).
+size_t frame_span(const rpf_engine* e, int64_t frames)
+{
+    return frames < 1 ? 0 : 2 * static_cast<size_t>(e->N) + 2 * static_cast<size_t>(e->step) * static_cast<size_t>(frames - 1);
+}
+
+bool overlapped(const rpf_engine* e) { return e->step != e->N; }
+
+bool is_k1(const rpf_engine* e)
+{
+    return !(e->fourstep || e->mixed || e->bluestein || e->bigblu || e->generic);
 }
 
 // Makes the engine's device current for the scope of an entry point and puts the
@@ -224,9 +247,11 @@ int launch_fused_hops(rpf_engine* e, const uint8_t* const* d_frames, const int64
         if (nframes[0] < 1) return RPF_OK;
         const int64_t wanted = (nframes[0] + e->plan.fpw - 1) / e->plan.fpw;
         const int grid = static_cast<int>(std::min<int64_t>(e->plan.grid, wanted));
-        const bool dma1 = e->use_dma && (reinterpret_cast<uintptr_t>(d_frames[0]) % 16) == 0;
+        // overlapped frames: the strided instantiation, LDS-DMA where every frame start is 16-byte aligned
+        const long pitch = 2L * e->step;
+        const bool dma1 = e->use_dma && (reinterpret_cast<uintptr_t>(d_frames[0]) % 16) == 0 && pitch % 16 == 0;
         HIP_TRY(e, rpf::launch_fft_accum(e->N, e->variant, e->has_window, dma1, d_frames[0], nframes[0], e->d_twiddles,
-                                         e->d_window, e->d_partial, grid, stream, &e->last));
+                                         e->d_window, e->d_partial, grid, stream, &e->last, pitch));
         for (int h = 1; h <= rpf::kMaxHops; ++h) slots->begin[h] = grid;
         *nslots = grid;
         return RPF_OK;
@@ -304,7 +329,8 @@ void note_device_path_aborts(rpf_engine* e)
 }
 
 // Enqueue K1 (or the four-step pair K2a/K2b) for `nframes` frames starting at
-// d_frames; leaves *nslots partial spectra in e->d_partial.
+// d_frames; leaves *nslots partial spectra in e->d_partial.  K1 reads the frames at the engine's frame step; every
+// other family reads them side by side (launch_frames gathers overlapped frames for them first).
 int launch_transform(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hipStream_t stream,
                      int* nslots)
 {
@@ -377,6 +403,32 @@ int launch_transform(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hi
     return launch_fused_hops(e, &d_frames, &nframes, 1, stream, &slots, nslots);
 }
 
+int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out, bool accumulate,
+                        hipStream_t stream, unsigned* slot_verdict);
+
+// Overlapped frames on a family that reads frames side by side: chunks of at most kGatherBytes of frames are gathered
+// into e->d_gather (rpf_frames.hip) and the size's unchanged transform + reduce runs over each, the chunks after the
+// first adding into d_out.  (Four-step sizes are on the two-kernel path here: rpf_engine_create.)
+int launch_gathered(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out, bool accumulate,
+                    hipStream_t stream)
+{
+    const size_t frame = 2 * static_cast<size_t>(e->N);
+    if (!e->d_gather) {
+        e->gather_frames = std::max<int64_t>(1, static_cast<int64_t>(rpf::kGatherBytes / frame));
+        void* p = nullptr;
+        HIP_TRY(e, hipMalloc(&p, static_cast<size_t>(e->gather_frames) * frame));
+        e->d_gather = static_cast<uint8_t*>(p);
+    }
+    const long pitch = 2L * e->step;
+    for (int64_t f0 = 0; f0 < nframes; f0 += e->gather_frames) {
+        const int64_t n = std::min(e->gather_frames, nframes - f0);
+        HIP_TRY(e, rpf::launch_gather_frames(d_frames + f0 * pitch, n, pitch, static_cast<long>(frame), e->d_gather, stream));
+        const int rc = launch_side_by_side(e, e->d_gather, n, d_out, accumulate || f0 > 0, stream, nullptr);
+        if (rc != RPF_OK) return rc;
+    }
+    return RPF_OK;
+}
+
 // Transform + reduce for `nframes` frames starting at d_frames.
 // slot_verdict: the queue path's pinned word for this launch -- if a fused launch gives up, K3 leaves d_out as it
 // is, the word becomes 1 and the worker re-runs the bytes on K2a/K2b (recover_fused); null (the device-resident
@@ -385,6 +437,14 @@ int launch_frames(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, doubl
                   bool accumulate, hipStream_t stream, unsigned* slot_verdict = nullptr)
 {
     if (nframes <= 0) return RPF_OK;
+    if (overlapped(e) && !is_k1(e)) return launch_gathered(e, d_frames, nframes, d_out, accumulate, stream);
+    return launch_side_by_side(e, d_frames, nframes, d_out, accumulate, stream, slot_verdict);
+}
+
+// launch_frames for frames the transform reads where they lie (K1 at any frame step; the other families at step N)
+int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out, bool accumulate,
+                        hipStream_t stream, unsigned* slot_verdict)
+{
     if (e->fused && !slot_verdict) note_device_path_aborts(e);
     int nslots = 0;
     int rc = launch_transform(e, d_frames, nframes, stream, &nslots);
@@ -483,7 +543,7 @@ void worker_main(rpf_engine* e)
         e->recycle_cv.notify_one();
     };
 
-    const size_t frame_bytes = 2 * static_cast<size_t>(e->N);
+    const size_t step_bytes = 2 * static_cast<size_t>(e->step);    // frame f starts at byte f * step_bytes
     const size_t slot_bytes = e->coalesce * e->buffer_capacity;
     size_t carry = 0;             // bytes of an unfinished frame at the end of the previous slot
     const uint8_t* carry_src = nullptr;
@@ -557,7 +617,7 @@ void worker_main(rpf_engine* e)
             WORKER_TRY(hipMemcpyAsync(dst - carry, carry_src, carry, hipMemcpyDeviceToDevice, e->compute_stream),
                        "hipMemcpyAsync(carry)");
         const size_t avail = carry + off;
-        int64_t nframes = static_cast<int64_t>(avail / frame_bytes);
+        int64_t nframes = frames_in(e, avail);
         nframes = std::min<int64_t>(nframes, e->repeats - frames_issued);    // datastore.cxx:67
         if (ok() && nframes > 0) {
             if (cur->verdict) *cur->verdict = 0;
@@ -573,9 +633,10 @@ void worker_main(rpf_engine* e)
         }
         WORKER_TRY(hipEventRecord(cur->kernel_done, e->compute_stream), "hipEventRecord(kernel_done)");
         cur->in_flight = ok();
-        // the unfinished frame (if any) stays in this slot until the next one is launched
-        const size_t consumed = static_cast<size_t>(std::max<int64_t>(nframes, 0)) * frame_bytes;
-        carry = (frames_issued < e->repeats) ? (avail - consumed) % frame_bytes : 0;
+        // the unfinished frame (if any) stays in this slot until the next one is launched: what follows the last
+        // frame's start + 2S, < 2N bytes (everything, before the first frame is complete)
+        const size_t consumed = static_cast<size_t>(std::max<int64_t>(nframes, 0)) * step_bytes;
+        carry = (frames_issued < e->repeats) ? avail - consumed : 0;
         carry_src = dst + off - carry;
         cur = nullptr;
         off = 0;
@@ -626,7 +687,7 @@ void worker_main(rpf_engine* e)
         for (size_t i = 0; i < batch.size();) {
             HostBuffer* const b = batch[i];
             // datastore.cxx:67: once the quota is met (by what is staged already) the rest of the stream is ignored
-            const int64_t staged = frames_issued + static_cast<int64_t>((carry + off) / frame_bytes);
+            const int64_t staged = frames_issued + frames_in(e, carry + off);
             if (!ok() || b->size == 0 || staged >= e->repeats) {
                 if (!b->external) hand_back(b, nullptr);
                 ++i;
@@ -640,7 +701,7 @@ void worker_main(rpf_engine* e)
             while (i + run < batch.size()) {
                 const HostBuffer* const nb = batch[i + run];
                 if (nb->data != b->data + bytes || nb->size == 0 || nb->external != b->external || off + bytes + nb->size > slot_bytes) break;
-                if (frames_issued + static_cast<int64_t>((carry + off + bytes) / frame_bytes) >= e->repeats) break;
+                if (frames_issued + frames_in(e, carry + off + bytes) >= e->repeats) break;
                 bytes += nb->size;
                 ++run;
             }
@@ -697,6 +758,7 @@ void release_device(rpf_engine* e)
     if (e->d_fused_scratch) (void)hipFree(e->d_fused_scratch);
     if (e->h_fused_words) (void)hipHostFree(e->h_fused_words);
     if (e->d_step2) (void)hipFree(e->d_step2);
+    if (e->d_gather) (void)hipFree(e->d_gather);
     if (e->d_chirp) (void)hipFree(e->d_chirp);
     if (e->d_bhat) (void)hipFree(e->d_bhat);
     if (e->d_window) (void)hipFree(e->d_window);
@@ -737,11 +799,18 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
 {
     if (!out) return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "rpf_engine_create: out is NULL");
     *out = nullptr;
-    if (!cfg || cfg->struct_size != sizeof(rpf_config))
+    // (the config of ABI 2's first form ends at `flags`: frame step N)
+    if (!cfg || (cfg->struct_size != sizeof(rpf_config) && cfg->struct_size != offsetof(rpf_config, frame_step)))
         return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "rpf_engine_create: bad rpf_config size");
     if (cfg->N < 2 || (cfg->N % 2) != 0)
         return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
                     "Number of bins must be a positive even number.");
+    const int32_t frame_step = cfg->struct_size == sizeof(rpf_config) ? cfg->frame_step : 0;
+    if (frame_step < 0 || frame_step > cfg->N)
+        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
+                    "Frame step must be between 1 and the number of bins (" + std::to_string(cfg->N) + "), or 0 for " +
+                        std::to_string(cfg->N) + "; got " + std::to_string(frame_step) + ".");
+    const int step = frame_step == 0 ? cfg->N : frame_step;
     const int variant = static_cast<int>((cfg->flags >> 8) & 0xffu);
     // (asking for the fused four-step kernel is asking for the four-step path)
     // 32768 is served twice, by the split form 2 x 16384 and by the four-step kernels.  Plain runs are faster on the
@@ -777,6 +846,7 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
 
     rpf_engine* e = new rpf_engine();
     e->N = cfg->N;
+    e->step = step;
     e->has_window = cfg->window != nullptr;
     e->n_buffers = cfg->n_buffers;
     e->buffer_capacity = static_cast<size_t>(cfg->buffer_capacity);
@@ -899,7 +969,9 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
         // The fused kernel (one persistent launch, the intermediate stays in each XCD's L2) where
         // the device is the 8 x 32-CU part it is written for and its teams assemble; else K2a/K2b.
         int fused_grid = 0;
-        if (!(cfg->flags & RPF_FLAG_NO_FOURSTEP_FUSED) &&
+        // (overlapped frames: the two-kernel path -- the fused kernel's give-up verdict is one word per staging slot,
+        // which the gather path's several launches per slot would share)
+        if (!(cfg->flags & RPF_FLAG_NO_FOURSTEP_FUSED) && step == e->N &&
             rpf::fourstep_fused_prepare(e->N, e->device, &fused_grid) == hipSuccess) {
             CREATE_TRY(hipMalloc(&e->d_fused_scratch, rpf::fourstep_fused_scratch_bytes(e->N)));
             CREATE_TRY(hipMalloc(&e->d_fused_ctl, rpf::fourstep_fused_ctl_bytes()));
@@ -1255,7 +1327,7 @@ int rpf_accumulate_device(rpf_engine* e, const void* d_stream, size_t nbytes, in
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the HIP null stream
-    int64_t nframes = static_cast<int64_t>(nbytes / (2 * static_cast<size_t>(e->N)));
+    int64_t nframes = frames_in(e, nbytes);
     nframes = std::min(nframes, repeats);
     if (repeats_done) *repeats_done = nframes;
     if (nframes == 0) {
@@ -1273,9 +1345,12 @@ int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t
     if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: acquisition running");
     if (reinterpret_cast<uintptr_t>(d_stream) & 1)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: d_stream must be at least 2-byte aligned");
+    if (overlapped(e) && !is_k1(e))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    "rpf_device_fused: overlapped frames (frame step < N) on this size need rpf_accumulate_device");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
-    int64_t nframes = static_cast<int64_t>(nbytes / (2 * static_cast<size_t>(e->N)));
+    int64_t nframes = frames_in(e, nbytes);
     nframes = std::min(nframes, repeats);
     if (nframes < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: no whole frame");
     if (repeats_done) *repeats_done = nframes;
@@ -1312,7 +1387,7 @@ int rpf_device_reduce(rpf_engine* e, double* d_pwr_out, void* hip_stream)
     return RPF_OK;
 }
 
-// Shared argument checks of the hop entries; fills frames[h] = min(repeats[h], nbytes[h] / 2N).
+// Shared argument checks of the hop entries; fills frames[h] = min(repeats[h], frames(nbytes[h])).
 static int check_hops(rpf_engine* e, const char* who, const void* const* d_streams, const size_t* nbytes,
                       const int64_t* repeats, int H, std::vector<int64_t>* frames)
 {
@@ -1325,17 +1400,16 @@ static int check_hops(rpf_engine* e, const char* who, const void* const* d_strea
         if (!d_streams[h] && nbytes[h]) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL stream");
         if (reinterpret_cast<uintptr_t>(d_streams[h]) & 1)
             return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": streams must be at least 2-byte aligned");
-        (*frames)[h] = std::min<int64_t>(static_cast<int64_t>(nbytes[h] / (2 * static_cast<size_t>(e->N))), repeats[h]);
+        (*frames)[h] = std::min<int64_t>(frames_in(e, nbytes[h]), repeats[h]);
     }
     return RPF_OK;
 }
 
-static bool is_k1(const rpf_engine* e)
-{
-    return !(e->fourstep || e->mixed || e->bluestein || e->bigblu || e->generic);
-}
-
 int rpf_max_hops_per_launch(void) { return rpf::kMaxHops; }
+
+int64_t rpf_frames_in(const rpf_engine* e, size_t nbytes) { return e ? frames_in(e, nbytes) : 0; }
+
+size_t rpf_frame_span(const rpf_engine* e, int64_t frames) { return e ? frame_span(e, frames) : 0; }
 
 int rpf_accumulate_device_hops(rpf_engine* e, const void* const* d_streams, const size_t* nbytes,
                                const int64_t* repeats, int n_hops, double* d_pwr_out, void* hip_stream,
@@ -1353,8 +1427,9 @@ int rpf_accumulate_device_hops(rpf_engine* e, const void* const* d_streams, cons
     if (repeats_done)
         for (int h = 0; h < n_hops; ++h) repeats_done[h] = frames[h];
     const size_t N = static_cast<size_t>(e->N);
-    if (!is_k1(e)) {
-        // the other kernel families run one acquisition per launch set
+    if (!is_k1(e) || overlapped(e)) {
+        // the other kernel families -- and overlapped frames (the scan kernel reads frames side by side) -- run one
+        // acquisition per launch set
         for (int h = 0; h < n_hops; ++h) {
             if (frames[h] == 0) {
                 HIP_TRY(e, hipMemsetAsync(d_pwr_out + h * N, 0, sizeof(double) * N, s));
@@ -1391,9 +1466,10 @@ int rpf_device_fused_hops(rpf_engine* e, const void* const* d_streams, const siz
     std::vector<int64_t> frames;
     int rc = check_hops(e, "rpf_device_fused_hops", d_streams, nbytes, repeats, n_hops, &frames);
     if (rc != RPF_OK) return rc;
-    if (!is_k1(e) || n_hops > rpf::kMaxHops)
+    if (!is_k1(e) || n_hops > rpf::kMaxHops || overlapped(e))
         return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    "rpf_device_fused_hops: needs a size the LDS-resident kernel serves and at most rpf_max_hops_per_launch() hops");
+                    "rpf_device_fused_hops: needs a size the LDS-resident kernel serves, frames side by side (frame step N) "
+                    "and at most rpf_max_hops_per_launch() hops");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     if (repeats_done)

@@ -29,12 +29,13 @@ bool kernel_supported(int N, int vid = 0);
 hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, LaunchInfo* li);
 
 // Fused unpack + FFT + |X|^2 accumulate over frames [0, nframes) of d_stream
-// (frame f = bytes [2N f, 2N (f+1))).  Writes one partial spectrum of N doubles
+// (frame f = bytes [pitch f, pitch f + 2N); pitch 0 = 2N).  Writes one partial spectrum of N doubles
 // per workgroup to d_partial (every workgroup writes, zeros included).
-// `grid` is the number of workgroups to launch (<= the planned grid).
+// `grid` is the number of workgroups to launch (<= the planned grid).  pitch: even, <= 2N; any pitch
+// but 2N runs the strided instantiation (use_dma then also needs pitch % 16 == 0).
 hipError_t launch_fft_accum(int N, int vid, bool window, bool use_dma, const uint8_t* d_stream,
                             long nframes, const cf* d_twiddles, const float* d_window,
-                            double* d_partial, int grid, hipStream_t stream, LaunchInfo* li);
+                            double* d_partial, int grid, hipStream_t stream, LaunchInfo* li, long pitch = 0);
 // The same over the hops of `hops` (hop_partition.h: frame f of hop h = bytes [2N f, 2N (f+1)) of
 // hops.stream[h]) in ONE launch.  Workgroup w writes one partial spectrum of N doubles per hop it
 // touches, at slot hops.slot_bias[h] + w of d_partial.  `grid` is what partition_hops returned
@@ -138,6 +139,14 @@ void generic_twiddle_tables(int N, std::vector<cf>& t0, std::vector<cf>& t1, int
 hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const float* d_window, const cf* d_g,
                           const cf* d_bhat, const cf* d_t0, const cf* d_t1, int h, cf* d_scratch, double* d_pwr,
                           bool accumulate, hipStream_t stream);
+
+// ---- overlapped frames on the other kernel families (rpf_frames.hip) --------------------------------
+// d_dst[f * frame_bytes .. (f+1) * frame_bytes) = d_src[f * pitch .. f * pitch + frame_bytes) for f < nframes:
+// the frames of a stream with frame step S < N, laid side by side so that a kernel that addresses frames at 2N
+// can run over them.  frame_bytes and pitch even; d_src, d_dst 2-byte aligned.
+constexpr size_t kGatherBytes = static_cast<size_t>(64) << 20;   // gathered frames per chunk (the engine's scratch)
+hipError_t launch_gather_frames(const uint8_t* d_src, long nframes, long pitch, long frame_bytes, uint8_t* d_dst,
+                                hipStream_t stream);
 
 // Master twiddle table W_N^k = exp(-2 pi i k / N), k in [0,N), evaluated in
 // long double and rounded once to float.

@@ -72,6 +72,29 @@ __device__ __forceinline__ void stage_raw(const uint8_t* __restrict__ stream, ID
     }
 }
 
+// The same at a run-time frame pitch (bytes from one frame's start to the next): the frames of a stream with frame
+// step S < N (rpf_config::frame_step) lie 2S apart.  Only the strided K1 uses it.
+template <class G, bool DMA>
+__device__ __forceinline__ void stage_raw_pitched(const uint8_t* __restrict__ stream, long fb, long nframes, long pitch,
+                                                  uint8_t* wave_raw, int wave, int lane)
+{
+    constexpr int PIECES = G::P / 8;
+#pragma unroll
+    for (int i = 0; i < PIECES; ++i) {
+        const int j = i * 1024 + lane * 16;
+        int slot, off;
+        raw_source<G>(wave, j, &slot, &off);
+        long f = fb + slot;
+        f = f < nframes ? f : nframes - 1;
+        const uint8_t* src = stream + f * pitch + off;
+        if constexpr (DMA) {
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(wave_raw + i * 1024), 16, 0, 0);
+        } else {
+            *reinterpret_cast<uint4*>(wave_raw + j) = *reinterpret_cast<const uint4*>(src);
+        }
+    }
+}
+
 // ---- K1, one acquisition per launch ------------------------------------------------------
 // Frame f -> workgroup (f / FPW) mod grid: at any moment the grid reads one contiguous window of
 // the stream.  (The scan kernel below walks several acquisitions per launch; for a single one
@@ -85,185 +108,25 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_kernel(const uint8_t* __res
                                                             const float* __restrict__ window,
                                                             double* __restrict__ partial)
 {
-    constexpr int P = G::P, T = G::T, N = G::N, NPASS = G::NPASS;
-    constexpr int FPW = WG / T;
-    constexpr int NSLAB = DBUF ? 2 : 1;
-    constexpr bool BLOCK_SYNC = (T > 64);
-    static_assert(WG % T == 0 && WG % 64 == 0, "");
+    constexpr bool STRIDED = false;
+    constexpr long pitch = 2L * G::N;     // (named by the discarded strided branches only)
+#include "k1_body.inc"
+}
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    cf* const slab_base = reinterpret_cast<cf*>(smem);                        // [NSLAB][FPW][LDS_CPX]
-    uint8_t* const raw_base = smem + NSLAB * FPW * G::LDS_CPX * sizeof(cf);  // [WG/64][RAWD][128 P]
-
-    const int tid = threadIdx.x;
-    const int fs = tid / T, t = tid % T;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    constexpr int RAW_SLOT = kRawChunk * P;           // bytes one wave stages per frame
-    constexpr int PIECES = P / 8;                     // DMA instructions per wave per frame
-    uint8_t* const wave_raw = raw_base + wave * (RAWD * RAW_SLOT);
-
-    // First thing: get the first frames' bytes moving (HBM latency overlaps the
-    // constant loads below).  RAWREG keeps the next frame's 2P bytes per lane in
-    // VGPRs instead of issuing LDS-DMA (two global_load_dwordx4 cost a few issue
-    // cycles, an LDS-DMA instruction ~100-200).
-    const long stride = static_cast<long>(gridDim.x) * FPW;
-    long fb = static_cast<long>(blockIdx.x) * FPW;
-    if (fb < nframes) {
-#pragma unroll
-        for (int d = 0; d < RAWD; ++d)
-            stage_raw<G, DMA, long>(stream, fb + d * stride, nframes, wave_raw + d * RAW_SLOT, wave, lane);
-    }
-
-    // Loop-invariant per-thread constants: twiddles, sign, window.
-    cf tw[NPASS - 1][P - 1];
-    load_twiddles<G, 1, TWLDS>(t, twN, tw);
-    cf* const twtable = reinterpret_cast<cf*>(raw_base + (WG / 64) * RAWD * (kRawChunk * P));
-    if constexpr (TWLDS) {
-        fill_twlds<G, 1>(tid, WG, twN, twtable);
-        exchange_sync<true>();
-    }
-    const float sgn = (t & 1) ? -1.0f : 1.0f;
-    float wsgn[P];
-    if constexpr (WINDOW) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) wsgn[a] = window[t + T * a] * sgn;
-    }
-    // ACCB (tuning variants only): |X|^2 is first summed over ACCB frames in float32, then added to the double
-    // accumulators.  1 .. 99: one float per bin (two v_fma_f32; round 3's variant 22); 100 + n (round 6, VERDICT r05 item
-    // 4 i): PACKED, (re^2, im^2) kept apart in one register pair per bin -- ONE v_pk_fma_f32 per bin and frame -- over n
-    // frames.  Both depart from the reference's "square and sum in double" (datastore.cxx:83-85); neither is shipped.
-    constexpr bool ACCP = ACCB >= 100;
-    constexpr int ACCN = ACCP ? ACCB - 100 : ACCB;
-    double acc[P];
-    float acc32[ACCB > 0 && !ACCP ? P : 1];
-    cf acc32p[ACCP ? P : 1];
-#pragma unroll
-    for (int a = 0; a < P; ++a) acc[a] = 0.0;
-    if constexpr (ACCP) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) acc32p[a] = cf{0.0f, 0.0f};
-    } else if constexpr (ACCB > 0) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) acc32[a] = 0.0f;
-    }
-
-    PhaseClock clk;
-    clk.start();
-    for (int it = 0; fb < nframes; fb += stride, ++it) {
-        const bool active = (fb + fs) < nframes;
-        cf* const slab = slab_base + ((DBUF ? (it & 1) : 0) * FPW + fs) * G::LDS_CPX;
-        uint8_t* const ring_slot = wave_raw + (it % RAWD) * RAW_SLOT;
-        cf x[P];
-
-        {
-            // this frame's bytes have landed: every iteration issues exactly PIECES DMA
-            // instructions per wave, so all but the newest (RAWD-1) frames' worth are done
-            if constexpr (DMA && !(ABL & 8))
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RAWD - 1) * PIECES) : "memory");
-            exchange_sync<false>();
-            RPF_STAMP(clk, 0);                   // waiting for the staged bytes
-            phase_unpack<G, WINDOW>(ring_slot + 2 * lane, sgn, wsgn, x);
-            // The slot is refilled next: its ds_read_u16 must have RETURNED first (a DMA
-            // that hits in L2/MALL can land before queued LDS reads execute -- seen as
-            // sporadic 1e-3 errors), so wait for this wave's LDS reads, not just issue.
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            exchange_sync<false>();
-            RPF_STAMP(clk, 1);                   // unpack
-            // the slot has been consumed: refill it with the frame RAWD iterations ahead
-            if constexpr (!(ABL & 8))
-                stage_raw<G, DMA, long>(stream, fb + RAWD * stride, nframes, ring_slot, wave, lane);
-            RPF_STAMP(clk, 3);                   // DMA issue
-        }
-
-        // single slab: every wave must be done with the previous frame's slab
-        if constexpr (!DBUF) exchange_sync<BLOCK_SYNC>();
-        RPF_STAMP(clk, 2);                       // top-of-frame barrier
-        middle_passes<G, 1, ABL, TWLDS>(t, x, tw, slab, clk, twtable);   // stamps 4J..4J+3
-        if constexpr (!(ABL & 4)) phase_fetch<G, NPASS>(t, x, slab);
-        asm volatile("" : "+v"(x[0]));
-        RPF_STAMP(clk, 12);                      // last fetch
-        if constexpr (!(ABL & 2)) phase_last<G>(x);
-        RPF_STAMP(clk, 13);                      // last butterfly
-        if constexpr (ACCP) {
-            if (active) {
-#pragma unroll
-                for (int a = 0; a < P; ++a)
-                    asm("v_pk_fma_f32 %0, %1, %1, %0" : "+v"(acc32p[a]) : "v"(x[a]));
-            }
-            if ((it % ACCN) == ACCN - 1) {
-#pragma unroll
-                for (int a = 0; a < P; ++a) {
-                    acc[a] += static_cast<double>(acc32p[a].x) + static_cast<double>(acc32p[a].y);
-                    acc32p[a] = cf{0.0f, 0.0f};
-                }
-            }
-        } else if constexpr (ACCB > 0) {
-            if (active) {
-#pragma unroll
-                for (int a = 0; a < P; ++a)
-                    acc32[a] = __builtin_fmaf(x[a].x, x[a].x, __builtin_fmaf(x[a].y, x[a].y, acc32[a]));
-            }
-            if ((it % ACCB) == ACCB - 1) {
-#pragma unroll
-                for (int a = 0; a < P; ++a) {
-                    acc[a] += static_cast<double>(acc32[a]);
-                    acc32[a] = 0.0f;
-                }
-            }
-        } else if constexpr (ABL & 1) {
-#pragma unroll
-            for (int a = 0; a < P; ++a) asm volatile("" ::"v"(x[a]));
-        } else {
-            if (active) phase_accumulate(x, acc, P);
-        }
-        RPF_STAMP(clk, 14);                      // accumulate
-    }
-    clk.publish(lane);
-    if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // trailing (clamped) prefetches
-    if constexpr (ACCP) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) acc[a] += static_cast<double>(acc32p[a].x) + static_cast<double>(acc32p[a].y);
-    } else if constexpr (ACCB > 0) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) acc[a] += static_cast<double>(acc32[a]);
-    }
-
-    // One partial spectrum per workgroup (the FPW frame slots are summed here);
-    // every workgroup writes its partial, zeros included.  The accumulators go
-    // through LDS (now free) so that the bin-scattered registers leave as fully
-    // coalesced 512-byte rows: stage at a padded bin index (one spare double per
-    // 16, conflict-free for the stride-16 bin pattern of bin_of), then stream out.
-    exchange_sync<true>();
-    double* const stage = reinterpret_cast<double*>(smem);          // [FPW][N + N/16]
-    constexpr int SN = N + N / 16;
-    static_assert(sizeof(double) * SN <= sizeof(cf) * G::LDS_CPX + 2 * N, "stage fits the LDS");
-#pragma unroll
-    for (int a = 0; a < P; ++a) {
-        const int bin = bin_of<G>(t, a);
-        stage[fs * SN + bin + (bin >> 4)] = acc[a];
-    }
-    exchange_sync<true>();
-    if constexpr (PF32) {
-        for (int bin = tid; bin < N; bin += WG) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = 0; k < FPW; ++k) v += stage[k * SN + bin + (bin >> 4)];
-            reinterpret_cast<float*>(partial)[static_cast<size_t>(blockIdx.x) * N + bin] = static_cast<float>(v);
-        }
-    } else {
-        // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
-        // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one
-        typedef double d2 __attribute__((ext_vector_type(2)));
-        for (int bin = 2 * tid; bin < N; bin += 2 * WG) {
-            d2 v = {0.0, 0.0};
-#pragma unroll
-            for (int k = 0; k < FPW; ++k) {
-                v.x += stage[k * SN + bin + (bin >> 4)];
-                v.y += stage[k * SN + bin + 1 + (bin >> 4)];
-            }
-            *reinterpret_cast<d2*>(partial + static_cast<size_t>(blockIdx.x) * N + bin) = v;
-        }
-    }
+// Overlapped frames (frame step S < N): frame f = bytes [f * pitch, f * pitch + 2N), pitch = 2S.  Frame f still goes
+// to workgroup (f / FPW) mod grid, so neighbouring frames -- which share most of their bytes -- are staged by the
+// same workgroup a few iterations apart and the shared bytes come back from L2.  A separate instantiation: the
+// plain kernel keeps its compile-time 2N.
+template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
+          int RAWD = 2, int ABL = 0, bool TWLDS = false>
+__global__ __launch_bounds__(WG, OCC) void fft_accum_strided_kernel(const uint8_t* __restrict__ stream,
+                                                                    long nframes, long pitch,
+                                                                    const cf* __restrict__ twN,
+                                                                    const float* __restrict__ window,
+                                                                    double* __restrict__ partial)
+{
+    constexpr bool STRIDED = true;
+#include "k1_body.inc"
 }
 
 
@@ -901,12 +764,14 @@ __global__ __launch_bounds__(PAIRS* GROUPS) void reduce_kernel(
 // ---------------------------------------------------------------- dispatch --
 using SingleFn = void (*)(const uint8_t*, long, const cf*, const float*, double*);
 using ScanFn = void (*)(const cf*, const float*, double*, const HopArgs);
+using StridedFn = void (*)(const uint8_t*, long, long, const cf*, const float*, double*);
 
 struct Variant {
     int N, vid, P, WG, fpw, lds_bytes;
     bool partial_f32;
     SingleFn single[2][2];   // [window][dma]: one acquisition per launch
     ScanFn scan[2][2];       // several hops per launch
+    StridedFn strided[2][2]; // one acquisition of overlapped frames (frame pitch a kernel argument)
 };
 
 // OCC (OCCW for the windowed kernels) = waves per SIMD the register budget
@@ -929,7 +794,11 @@ Variant make_variant(int vid)
                    {{fft_accum_scan_kernel<G, WG, OCC, false, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS>,
                      fft_accum_scan_kernel<G, WG, OCC, false, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS>},
                     {fft_accum_scan_kernel<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS>,
-                     fft_accum_scan_kernel<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS>}}};
+                     fft_accum_scan_kernel<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS>}},
+                   {{fft_accum_strided_kernel<G, WG, OCC, false, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS>,
+                     fft_accum_strided_kernel<G, WG, OCC, false, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS>},
+                    {fft_accum_strided_kernel<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS>,
+                     fft_accum_strided_kernel<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS>}}};
 }
 
 // the matrix-pipe first pass (N = 4096, rectangular window, LDS-DMA staging only; the other three
@@ -1062,9 +931,11 @@ hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, La
     const Variant* v = find_variant(N, vid);
     if (!v) return hipErrorInvalidValue;
     int per_cu = 1 << 30;
-    for (int scan = 0; scan < 2; ++scan) {          // the single-acquisition and the scan instantiation share one grid
-        const void* fn = scan ? reinterpret_cast<const void*>(v->scan[window ? 1 : 0][use_dma ? 1 : 0])
-                              : reinterpret_cast<const void*>(v->single[window ? 1 : 0][use_dma ? 1 : 0]);
+    for (int kind = 0; kind < 3; ++kind) {    // the single-acquisition, scan and strided instantiations share one grid
+        const int w = window ? 1 : 0, d = use_dma ? 1 : 0;
+        const void* fn = kind == 2 ? reinterpret_cast<const void*>(v->strided[w][d])
+                       : kind == 1 ? reinterpret_cast<const void*>(v->scan[w][d])
+                                   : reinterpret_cast<const void*>(v->single[w][d]);
         hipError_t err = hipFuncSetAttribute(fn,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, v->lds_bytes);
         if (err != hipSuccess) return err;
@@ -1087,12 +958,16 @@ hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, La
 
 hipError_t launch_fft_accum(int N, int vid, bool window, bool use_dma, const uint8_t* d_stream,
                             long nframes, const cf* d_twiddles, const float* d_window,
-                            double* d_partial, int grid, hipStream_t stream, LaunchInfo* li)
+                            double* d_partial, int grid, hipStream_t stream, LaunchInfo* li, long pitch)
 {
     const Variant* v = find_variant(N, vid);
-    if (!v || grid < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(v->single[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->WG), v->lds_bytes, stream,
-                       d_stream, nframes, d_twiddles, d_window, d_partial);
+    if (!v || grid < 1 || pitch < 0 || pitch > 2L * N || (pitch & 1)) return hipErrorInvalidValue;
+    if (pitch == 0 || pitch == 2L * N)
+        hipLaunchKernelGGL(v->single[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->WG), v->lds_bytes, stream,
+                           d_stream, nframes, d_twiddles, d_window, d_partial);
+    else
+        hipLaunchKernelGGL(v->strided[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->WG), v->lds_bytes, stream,
+                           d_stream, nframes, pitch, d_twiddles, d_window, d_partial);
     if (li) {
         li->grid = grid;
         li->block = v->WG;

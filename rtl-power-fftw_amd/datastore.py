@@ -19,12 +19,16 @@ class Params:
 
     def __init__(self, N=512, buffers=5, buf_length=BASE_BUF * DEFAULT_BUF_MULTIPLIER,
                  repeats=None, window=False, sample_rate=2000000, cfreq=1420405752,
-                 linear=False, baseline=False):
+                 linear=False, baseline=False, frame_step=None):
         self.N = N
+        # frame step S in complex samples (rpf_config::frame_step): frame f = samples [f S, f S + N); None = N
+        self.frame_step = N if frame_step is None else frame_step
         self.buffers = buffers
         self.buf_length = buf_length
-        # params.h:56: repeats = buf_length/(2*N) unless -n/-t say otherwise
-        self.repeats = buf_length // (2 * N) if repeats is None else repeats
+        # params.h:56: repeats = buf_length/(2*N) unless -n/-t say otherwise -- a sample budget, which overlapped
+        # frames turn into more frames from the same samples
+        self.repeats = (frames_for_budget(buf_length // (2 * N), N, self.frame_step) if repeats is None
+                        else repeats)
         self.window = window
         self.sample_rate = sample_rate
         self.cfreq = cfreq
@@ -32,16 +36,35 @@ class Params:
         self.baseline = baseline
 
 
+def frames_for_budget(r0, N, step):
+    """R = floor((R0 - 1) N / S) + 1: the frames at step S the samples of R0 side-by-side frames hold (R0 for S = N)."""
+    if r0 < 1 or not step:
+        return r0
+    return (r0 - 1) * N // step + 1
+
+
+def frames_in(nbytes, N, step):
+    """frames(B) = B < 2N ? 0 : (B - 2N) / (2S) + 1 (rpf_frames_in)."""
+    return 0 if nbytes < 2 * N else (nbytes - 2 * N) // (2 * step) + 1
+
+
+def frame_span(frames, N, step):
+    """Bytes `frames` frames span: 2N + 2S (frames - 1) (rpf_frame_span)."""
+    return 0 if frames < 1 else 2 * N + 2 * step * (frames - 1)
+
+
 class Datastore:
     """``Datastore(params, window_values)``: buffer pool + FFT/accumulate worker."""
 
-    def __init__(self, params, window_values=None, device=0, flags=0):
+    def __init__(self, params, window_values=None, device=0, flags=0, struct_size=None):
+        """struct_size: rpf_config.struct_size to pass (default sizeof; _lib.CONFIG_SIZE_V2_0 = a caller built
+        against the config without frame_step)."""
         self.params = params
         self._lib = _lib.load()
         self._handle = ctypes.c_void_p()
         self._window = None
         cfg = _lib.rpf_config()
-        cfg.struct_size = ctypes.sizeof(_lib.rpf_config)
+        cfg.struct_size = ctypes.sizeof(_lib.rpf_config) if struct_size is None else struct_size
         cfg.N = params.N
         if params.window:
             if window_values is None or len(window_values) != params.N:
@@ -54,6 +77,7 @@ class Datastore:
         cfg.buffer_capacity = params.buf_length
         cfg.device = device
         cfg.flags = flags
+        cfg.frame_step = getattr(params, "frame_step", params.N)
         rc = self._lib.rpf_engine_create(ctypes.byref(cfg), ctypes.byref(self._handle))
         if rc != 0:
             self._handle = ctypes.c_void_p()
@@ -190,6 +214,14 @@ class Datastore:
         H, ptrs, nb, rep, done = self._hop_arrays(d_stream_ptrs, nbytes, repeats)
         self._check(self._lib.rpf_device_fused_hops(self._handle, ptrs, nb, rep, H, ctypes.c_void_p(hip_stream), done))
         return list(done)
+
+    def frames_in(self, nbytes):
+        """rpf_frames_in: frames a stream of nbytes holds at this engine's frame step."""
+        return self._lib.rpf_frames_in(self._handle, nbytes)
+
+    def frame_span(self, frames):
+        """rpf_frame_span: bytes `frames` frames span at this engine's frame step."""
+        return self._lib.rpf_frame_span(self._handle, frames)
 
     def max_hops_per_launch(self):
         return self._lib.rpf_max_hops_per_launch()

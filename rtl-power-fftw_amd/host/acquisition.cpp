@@ -53,7 +53,7 @@ void Acquisition::run()
     }
     if (!tuned) throw TuneError(freq_);
     if (chatty()) std::cerr << "Device tuned to: " << tuned_freq_ << " Hz" << std::endl;
-    if (sharded_ && !source_.position(shard_.hop_base, 2 * static_cast<uint64_t>(options_.N) *
+    if (sharded_ && !source_.position(shard_.hop_base, 2 * static_cast<uint64_t>(options_.step()) *
                                                           static_cast<uint64_t>(shard_.first_frame)))
         throw RPFexception("This sample source cannot be split across devices.", ReturnValue::InvalidArgument);
 
@@ -73,7 +73,7 @@ void Acquisition::run()
     const clock::time_point deadline =
         clock::now() + std::chrono::milliseconds(static_cast<int64_t>(options_.integration_time * 1000));
 
-    const int64_t data_total = 2 * static_cast<int64_t>(options_.N) * shard_.repeats;     // :273
+    const int64_t data_total = options_.frame_span(shard_.repeats);     // :273 (2N x repeats at frame step N)
     int64_t data_read = 0;
     while (data_read < data_total) {
         Buffer buffer = data_.acquire();                        // :278-285

@@ -42,6 +42,14 @@ struct Params {
   int buf_length = 16384 * 100;
   bool window = false;
   int64_t repeats = buf_length / (2 * N);
+  // Frame step S in complex samples (rpf_config::frame_step, --frame-overlap): frame f = samples [f S, f S + N).
+  // 0 = N, frames side by side as in the reference.
+  int frame_step = 0;
+  int64_t step() const { return frame_step > 0 ? frame_step : N; }
+  // bytes `frames` frames span (rpf_frame_span): 2N + 2S (frames - 1)
+  int64_t frame_span(int64_t frames) const { return frames < 1 ? 0 : 2 * static_cast<int64_t>(N) + 2 * step() * (frames - 1); }
+  // a sample budget of r0 side-by-side frames as frames at step S: floor((r0 - 1) N / S) + 1 (r0 at S = N)
+  int64_t frames_for_budget(int64_t r0) const { return r0 < 1 ? r0 : (r0 - 1) * N / step() + 1; }
   int sample_rate = 2000000;
   int64_t cfreq = 1420405752;
   bool linear = false;
@@ -91,6 +99,7 @@ public:
     cfg.buffer_capacity = params.buf_length;
     cfg.device = device_override >= 0 ? device_override : params.device;
     cfg.flags = RPF_FLAG_NONE;
+    cfg.frame_step = params.frame_step;
     int rc = rpf_engine_create(&cfg, &engine_);
     if (rc != RPF_OK) throw RPFexception(rpf_last_global_error(), (ReturnValue)rc);
   }

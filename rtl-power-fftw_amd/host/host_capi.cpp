@@ -53,6 +53,26 @@ int rpf_host_parse(int argc, const char* const* argv, int* N, int* buffers, int*
     }
 }
 
+// Overlapped frames on top of a parsed command line and the Plan at `samplerate` (the -t conversion needs the rate):
+// frame step S, repeats R (sample budgets of -t and the default converted to frames at step S) and the complex
+// samples one acquisition reads (frame_span(R) / 2).  0 or the reference's exit code (message in `msg`).
+int rpf_host_parse_frames(int argc, const char* const* argv, int samplerate, int* N, int* step, long long* repeats,
+                          long long* samples_per_acq, char* msg, size_t cap)
+{
+    try {
+        Options o = parse_command_line(argc, argv);
+        Plan plan(o, samplerate);
+        *N = o.N;
+        *step = static_cast<int>(o.step());
+        *repeats = o.repeats;
+        *samples_per_acq = o.frame_span(o.repeats) / 2;
+        return 0;
+    } catch (RPFexception& e) {
+        copy_out(e.what(), msg, cap);
+        return static_cast<int>(e.returnValue());
+    }
+}
+
 // Plan on top of a parsed command line: returns hop count (<= cap) or -code.
 int rpf_host_plan(int argc, const char* const* argv, int samplerate, long long* repeats, int* buf_length,
                   long long* freqs, int cap)

@@ -55,6 +55,9 @@ const Spec kSpecs[] = {
     {0, "synthetic", Kind::Int64, "seed", "Use the built-in synthetic receiver instead of a dongle."},
     {0, "gpu", Kind::Int, "ordinal", "HIP device to run on."},
     {0, "gpus", Kind::Text, "a,b,...", "HIP devices to spread a scan over (one engine per listed device)."},
+    {0, "frame-overlap", Kind::Text, "percent",
+     "Overlap of consecutive FFT frames inside one acquisition (Welch averaging), 0 <= percent < 100; "
+     "not the hop overlap of -o. Default 0."},
     {0, "reduce", Kind::Text, "rccl|host", "With --gpus: where a scan's per-device spectra are added (default: rccl if it loads, else host)."},
     {'h', "help", Kind::Flag, "", "Displays usage information and exits."},
     {0, "version", Kind::Flag, "", "Displays version information and exits."},
@@ -248,8 +251,20 @@ Options parse_command_line(int argc, const char* const* argv)
         }
     }
 
+    if (p.has("frame-overlap")) {
+        // (parsed here, not by the type check above: a non-number is an invalid argument, exit 3, like a value
+        // out of range)
+        const std::string text = p.get("frame-overlap");
+        char* end = nullptr;
+        o.frame_overlap = std::strtod(text.c_str(), &end);
+        if (text.empty() || *end != '\0' || !(o.frame_overlap >= 0 && o.frame_overlap < 100))
+            throw RPFexception("Invalid frame overlap given to --frame-overlap: " + text + ".\n"
+                               "Expecting a percentage in [0, 100). Exiting.", ReturnValue::InvalidArgument);
+        const int64_t cut = static_cast<int64_t>(std::floor(static_cast<double>(o.N) * o.frame_overlap / 100));
+        o.frame_step = static_cast<int>(std::max<int64_t>(1, o.N - cut));
+    }
     if (p.has("repeats")) o.repeats = to_number<int64_t>(*find_spec("--repeats"), p.get("repeats"));
-    else o.repeats = o.buf_length / (2 * o.N);                        // params.cxx:214-217
+    else o.repeats = o.frames_for_budget(o.buf_length / (2 * o.N));  // params.cxx:214-217, as a sample budget
     if (p.has("time")) {
         o.integration_time = parse_time(p.get("time"));
         if (o.integration_time <= 0)

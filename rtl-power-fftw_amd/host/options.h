@@ -33,6 +33,7 @@ struct Options : Params {
     bool integration_time_isSet = false;
     bool buf_length_isSet = false;
     double min_overlap = 0;
+    double frame_overlap = 0;          // --frame-overlap percent: frame_step = N - floor(N p / 100), at least 1
     int ppm_error = 0;
     bool endless = false;
     bool strict_time = false;

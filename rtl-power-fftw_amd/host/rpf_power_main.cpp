@@ -100,7 +100,7 @@ std::vector<DeviceJob> device_jobs(int hops, int64_t repeats, int G, int d, std:
 // whole 16384-byte transfers, acquisition.cxx:288-300).
 uint64_t replay_bytes_per_hop(const Options& options)
 {
-    const int64_t total = 2 * static_cast<int64_t>(options.N) * options.repeats;
+    const int64_t total = options.frame_span(options.repeats);
     int64_t read = 0;
     while (read < total) read += next_read_size(total, read, options.buf_length);
     return static_cast<uint64_t>(read);

@@ -9,12 +9,12 @@ Plan::Plan(Options& o, int samplerate) : actual_samplerate(samplerate), options_
 {
     // -t: as many spectra as the true sample rate delivers in that time
     if (o.integration_time_isSet)
-        o.repeats = static_cast<int64_t>(std::ceil(samplerate * o.integration_time / o.N));
+        o.repeats = o.frames_for_budget(static_cast<int64_t>(std::ceil(samplerate * o.integration_time / o.N)));
 
     // Short acquisitions get the smallest buffer (a multiple of 16384 bytes) that
     // holds them; anything above ~1.6 MB keeps the 100 x 16384 default.
     if (!o.buf_length_isSet) {
-        const int64_t multiples = static_cast<int64_t>(std::ceil((2.0 * o.N * o.repeats) / base_buf));
+        const int64_t multiples = static_cast<int64_t>(std::ceil(static_cast<double>(o.frame_span(o.repeats)) / base_buf));
         if (multiples <= default_buf_multiplier)
             o.buf_length = static_cast<int>(base_buf * (multiples == 0 ? 1 : multiples));
     }
@@ -43,10 +43,10 @@ void Plan::print() const
 {
     const Options& o = options_;
     std::cerr << "Number of bins: " << o.N << std::endl;
-    std::cerr << "Total number of (complex) samples to collect: " << static_cast<int64_t>(o.N) * o.repeats << std::endl;
+    std::cerr << "Total number of (complex) samples to collect: " << o.frame_span(o.repeats) / 2 << std::endl;
     std::cerr << "Buffer length: " << o.buf_length << std::endl;
     std::cerr << "Number of averaged spectra: " << o.repeats << std::endl;
-    std::cerr << "Estimated time of measurements: " << static_cast<double>(o.N) * o.repeats / actual_samplerate
+    std::cerr << "Estimated time of measurements: " << static_cast<double>(o.frame_span(o.repeats) / 2) / actual_samplerate
               << " seconds" << std::endl;
     if (o.strict_time)
         std::cerr << "Acquisition will unconditionally terminate after " << o.integration_time << " seconds."
