@@ -3,6 +3,7 @@
 // `constexpr bool STRIDED` and, when it is true, has the kernel argument `long pitch`.  An include rather than a
 // force-inlined device function: the plain kernels then compile to the instruction stream they had before the
 // strided form existed (an inlined body changed their schedules).
+    RPF_SEAM_MARK(0);                            // (timing builds only)
     constexpr int P = G::P, T = G::T, N = G::N, NPASS = G::NPASS;
     constexpr int FPW = WG / T;
     constexpr int NSLAB = DBUF ? 2 : 1;
@@ -90,6 +91,9 @@
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             exchange_sync<false>();
             RPF_STAMP(clk, 1);                   // unpack
+#ifdef RPF_PHASE_TIMING
+            if (it == 0) RPF_SEAM_MARK(1);
+#endif
             // the slot has been consumed: refill it with the frame RAWD iterations ahead
             if constexpr (!(ABL & 8)) {
                 if constexpr (STRIDED)
@@ -143,7 +147,7 @@
         }
         RPF_STAMP(clk, 14);                      // accumulate
     }
-    clk.publish(lane);
+    RPF_SEAM_MARK(2);
     if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // trailing (clamped) prefetches
     if constexpr (ACCP) {
 #pragma unroll
@@ -177,15 +181,18 @@
         }
     } else {
         // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
-        // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one
-        typedef double d2 __attribute__((ext_vector_type(2)));
+        // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
+        // Written through (store_partial2): 32 KB per workgroup that K3 reads from another XCD.
         for (int bin = 2 * tid; bin < N; bin += 2 * WG) {
-            d2 v = {0.0, 0.0};
+            partial2_t v = {0.0, 0.0};
 #pragma unroll
             for (int k = 0; k < FPW; ++k) {
                 v.x += stage[k * SN + bin + (bin >> 4)];
                 v.y += stage[k * SN + bin + 1 + (bin >> 4)];
             }
-            *reinterpret_cast<d2*>(partial + static_cast<size_t>(blockIdx.x) * N + bin) = v;
+            store_partial2(partial + static_cast<size_t>(blockIdx.x) * N + bin, v);
         }
     }
+    RPF_SEAM_DRAIN();
+    RPF_SEAM_MARK(3);
+    clk.publish(lane);                           // (timing builds: its atomics after the marks)

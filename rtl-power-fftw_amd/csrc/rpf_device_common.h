@@ -39,13 +39,49 @@ struct PhaseClock {
     }
 };
 #define RPF_STAMP(clk, i) (clk).stamp(i)
+// Seam marks (tools/gpu_seam.py --phases): thread 0 of each K1 workgroup writes the 100 MHz realtime clock at
+// kernel start (0), once its first frame is unpacked (1), at the end of its frame loop (2) and once its partial
+// spectrum has left (3, after an s_waitcnt vmcnt(0) that only this build has).  Workgroups >= kSeamWgs are not marked.
+constexpr int kSeamWgs = 2048, kSeamMarks = 4;
+__device__ unsigned long long g_seam_marks[kSeamWgs][kSeamMarks];
+#define RPF_SEAM_MARK(k)                                                                               \
+    do {                                                                                               \
+        if (threadIdx.x == 0 && blockIdx.x < kSeamWgs)                                                 \
+            g_seam_marks[blockIdx.x][k] = __builtin_amdgcn_s_memrealtime();                            \
+    } while (0)
+#define RPF_SEAM_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #else
 struct PhaseClock {
     __device__ __forceinline__ void start() {}
     __device__ __forceinline__ void publish(int) {}
 };
 #define RPF_STAMP(clk, i) ((void)0)
+#define RPF_SEAM_MARK(k) ((void)0)
+#define RPF_SEAM_DRAIN() ((void)0)
 #endif
+
+// Cache policy of the partial-spectrum flush (K1's last stores, and the scan kernel's per-hop hand-over):
+// 0 plain, 1 sc1 (write-through: the bytes leave the XCD's L2 as they are written, so the end-of-kernel
+// write-back finds clean lines -- and the workgroups that finish a round early publish during the tail),
+// 2 sc1 nt.  A/B in profiles/seam_after.txt; other values than the default are for A/B builds only.
+#ifndef RPF_PARTIAL_STORE
+#define RPF_PARTIAL_STORE 1
+#endif
+// The s_nop: a VALU write to the data registers of a store of more than 8 bytes needs wait states after it, and the
+// compiler's hazard check does not look inside inline assembly (without it the next v_add overwrote the data of the
+// scan kernel's N = 64 hand-over before the store had read it).
+typedef double partial2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void store_partial2(double* p, partial2_t v)
+{
+#if RPF_PARTIAL_STORE == 0
+    *reinterpret_cast<partial2_t*>(p) = v;
+#elif RPF_PARTIAL_STORE == 1
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v));
+#else
+    asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(v));
+#endif
+}
+
 
 // Orders LDS traffic between the threads that exchange data.  A frame that spans
 // several wavefronts needs s_barrier; it is issued raw, after waiting for this

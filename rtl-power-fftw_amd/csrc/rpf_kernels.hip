@@ -595,16 +595,16 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_scan_kernel(const cf* __res
             }
         } else {
             // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
-            // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one
-            typedef double d2 __attribute__((ext_vector_type(2)));
+            // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
+            // Written through (store_partial2), as K1's flush.
             for (int bin = 2 * ftid; bin < N; bin += 2 * WG) {
-                d2 v = {0.0, 0.0};
+                partial2_t v = {0.0, 0.0};
 #pragma unroll
                 for (int k = 0; k < FPW; ++k) {
                     v.x += stage[k * SN + bin + (bin >> 4)];
                     v.y += stage[k * SN + bin + 1 + (bin >> 4)];
                 }
-                *reinterpret_cast<d2*>(partial + slot * N + bin) = v;
+                store_partial2(partial + slot * N + bin, v);
             }
         }
         if (it >= count) break;
@@ -712,6 +712,20 @@ __global__ __launch_bounds__(WG, OCC) void bluestein_kernel(const uint8_t* __res
 // the GROUPS group sums are added in group order.  blockIdx.y = hop.
 // skip (may be null): a device word; non-zero = the partial spectra are not a result (the fused four-step
 // kernel gave up) and `out` is left as it is.
+// RPF_REDUCE_LOAD (A/B builds): cache policy of K3's partial-spectrum loads, 0 plain, 1 nt.
+#ifndef RPF_REDUCE_LOAD
+#define RPF_REDUCE_LOAD 0
+#endif
+template <typename V>
+__device__ __forceinline__ V load_partial2(const V* p)
+{
+#if RPF_REDUCE_LOAD == 1
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
+
 template <typename PT, int PAIRS, int GROUPS, int UNROLL>
 __global__ __launch_bounds__(PAIRS* GROUPS) void reduce_kernel(
     const PT* __restrict__ partial, const SlotRanges slots, int N, double* __restrict__ out,
@@ -733,7 +747,7 @@ __global__ __launch_bounds__(PAIRS* GROUPS) void reduce_kernel(
             pt2 v[UNROLL];
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u)
-                v[u] = *reinterpret_cast<const pt2*>(p + static_cast<size_t>(sl + u * GROUPS) * stride);
+                v[u] = load_partial2(reinterpret_cast<const pt2*>(p + static_cast<size_t>(sl + u * GROUPS) * stride));
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
                 s.x += v[u].x;
@@ -741,7 +755,7 @@ __global__ __launch_bounds__(PAIRS* GROUPS) void reduce_kernel(
             }
         }
         for (; sl < nslots; sl += GROUPS) {
-            const pt2 v = *reinterpret_cast<const pt2*>(p + static_cast<size_t>(sl) * stride);
+            const pt2 v = load_partial2(reinterpret_cast<const pt2*>(p + static_cast<size_t>(sl) * stride));
             s.x += v.x;
             s.y += v.y;
         }
@@ -921,6 +935,18 @@ extern "C" int rpf_debug_phase_cycles(unsigned long long* out16, unsigned long l
         unsigned long long z[kPhaseSlots] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), z, sizeof(z));
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_waves), z, sizeof(unsigned long long));
+    }
+    return 0;
+}
+
+// the seam marks of the K1 launches since the last reset (RPF_SEAM_MARK): out[kSeamWgs][kSeamMarks]
+extern "C" int rpf_debug_seam_marks(unsigned long long* out, int* nwgs, int reset)
+{
+    *nwgs = kSeamWgs;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_seam_marks), sizeof(g_seam_marks)) != hipSuccess) return 1;
+    if (reset) {
+        static unsigned long long z[kSeamWgs][kSeamMarks];
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_seam_marks), z, sizeof(z));
     }
     return 0;
 }
