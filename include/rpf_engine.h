@@ -31,7 +31,8 @@ extern "C" {
 #endif
 
 #define RPF_ABI_VERSION 2   /* 2: rpf_accumulate_device_hops, rpf_device_fused_hops, rpf_scan_reducer_*;
-                               additive within 2: rpf_config::frame_step, rpf_frames_in, rpf_frame_span */
+                               additive within 2: rpf_config::frame_step, rpf_frames_in, rpf_frame_span;
+                               RPF_FLAG_SAMPLE_FORMAT, RPF_FLAG_CATCH_ALL, rpf_sample_bytes, rpf_sample_format */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -98,6 +99,20 @@ typedef struct rpf_config {
  * rpf_engine_create fail with RPF_ERR_INVALID_ARGUMENT.  Experimental variants
  * exist only in the separate -DRPF_TUNING build used by tools/. */
 #define RPF_FLAG_VARIANT(k) (((uint32_t)(k) & 0xffu) << 8)
+/* Sample format of every stream the engine reads, in bits 16..19 of `flags` (zero = cu8, so a caller that never heard
+ * of formats gets what it always got).  The sample is converted to float32 exactly (every value of all three formats
+ * is a float32), (-1)^n is exact and the window multiplies once, with one rounding -- datastore.cxx:73-77 with
+ * `v - 127` replaced by `v` for the signed formats.  Any other value: RPF_ERR_INVALID_ARGUMENT from
+ * rpf_engine_create, before any device is touched.
+ * The LDS-resident kernel (powers of two 64 .. 8192) reads all three natively; at every other size a cs8 / cs16
+ * engine runs on the catch-all Stockham path (rpf_supported_n(N) holds for all three formats), which is several
+ * times slower than the tuned kernel a cu8 engine gets at that size (README.md, "Sample formats"). */
+#define RPF_FORMAT_CU8  0   /* unsigned 8-bit I,Q; x = v - 127   (the reference; the default) */
+#define RPF_FORMAT_CS8  1   /* signed 8-bit I,Q;   x = v                                       */
+#define RPF_FORMAT_CS16 2   /* signed 16-bit little-endian I,Q; x = v                          */
+#define RPF_FLAG_SAMPLE_FORMAT(f) (((uint32_t)(f) & 0xfu) << 16)
+/* Any N, any format on the catch-all Stockham path (A/B measurement, and the comparator of the format tests). */
+#define RPF_FLAG_CATCH_ALL 16u
 
 /* ABI version of the loaded library. */
 int rpf_abi_version(void);
@@ -211,6 +226,15 @@ int rpf_max_hops_per_launch(void);
  * the general entry point). */
 int64_t rpf_frames_in(const rpf_engine* e, size_t nbytes);
 size_t rpf_frame_span(const rpf_engine* e, int64_t frames);
+/* Bytes per complex sample, b: 2 (cu8, cs8) or 4 (cs16), and the engine's RPF_FORMAT_*.  EVERY byte count of this
+ * interface that is written 2N / 2S above is bN / bS: frames(nbytes) = nbytes < bN ? 0 : (nbytes - bN) / (bS) + 1,
+ * the span bN + bS (frames - 1), the frame quota and the trailing partial frame of rpf_finish, the hop lengths of
+ * rpf_accumulate_device_hops.  rpf_buffer_submit wants nbytes % b == 0 (a sample never straddles two buffers; frames
+ * still may) and rpf_engine_create buffer_capacity % b == 0, else RPF_ERR_INVALID_ARGUMENT.  Device streams: address a
+ * multiple of b, else RPF_ERR_INVALID_ARGUMENT; 16-byte aligned for the LDS-DMA path, other alignments stage through
+ * VGPRs. */
+int rpf_sample_bytes(const rpf_engine* e);
+int rpf_sample_format(const rpf_engine* e);
 
 /* Datastore::pwr as it sits in HBM after rpf_finish: copied (device to device, or peer to peer when
  * dst_device is another device) into d_dst[N]; synchronises hip_stream before returning. */

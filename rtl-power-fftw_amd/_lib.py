@@ -52,6 +52,19 @@ FLAG_NO_LDS_DMA = 1
 FLAG_FOURSTEP_FUSED = 2
 FLAG_NO_MIXED_RADIX = 4
 FLAG_NO_FOURSTEP_FUSED = 8
+FLAG_CATCH_ALL = 16
+
+# sample formats (RPF_FORMAT_*), carried in bits 16..19 of rpf_config.flags
+FORMAT_CU8 = 0
+FORMAT_CS8 = 1
+FORMAT_CS16 = 2
+FORMATS = {"cu8": FORMAT_CU8, "cs8": FORMAT_CS8, "cs16": FORMAT_CS16}
+SAMPLE_BYTES = {"cu8": 2, "cs8": 2, "cs16": 4}
+
+
+def FLAG_SAMPLE_FORMAT(f):
+    return (int(f) & 0xF) << 16
+
 
 # every symbol include/rpf_engine.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
@@ -86,6 +99,8 @@ _SYMBOLS = [
     ("rpf_max_hops_per_launch", ctypes.c_int, []),
     ("rpf_frames_in", ctypes.c_int64, [_P, ctypes.c_size_t]),
     ("rpf_frame_span", ctypes.c_size_t, [_P, ctypes.c_int64]),
+    ("rpf_sample_bytes", ctypes.c_int, [_P]),
+    ("rpf_sample_format", ctypes.c_int, [_P]),
     ("rpf_copy_power_device", ctypes.c_int, [_P, _P, _P, ctypes.c_int]),
     ("rpf_scan_reducer_create", ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.POINTER(_P)]),

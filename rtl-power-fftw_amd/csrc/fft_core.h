@@ -292,6 +292,27 @@ RPF_HD cf iq_pair_plus_2p23(uint32_t iq2)
 }
 constexpr float kTwo23 = 8388608.0f;
 
+// Sample formats (rpf_engine.h RPF_FORMAT_*): what one complex sample is in the stream.  A template parameter of
+// everything that touches raw bytes, defaulted to cu8 so that the cu8 instantiations are what they were.
+constexpr int kFmtCu8 = 0;    // unsigned 8-bit I, Q; x = v - 127
+constexpr int kFmtCs8 = 1;    // signed 8-bit I, Q; x = v
+constexpr int kFmtCs16 = 2;   // signed 16-bit little-endian I, Q; x = v
+constexpr int sample_bytes_of(int fmt) { return fmt == kFmtCs16 ? 4 : 2; }
+
+// One sample of a signed format as floats: every int8 / int16 value is a float32 exactly.  raw = the sample's
+// bytes, little-endian (cs8: I | Q << 8; cs16: I | Q << 16).  On the device a sign-extending field extract and
+// a convert per component; no offset to remove afterwards.
+template <int FMT>
+RPF_HD cf iq_signed(uint32_t raw)
+{
+    static_assert(FMT == kFmtCs8 || FMT == kFmtCs16, "");
+    if constexpr (FMT == kFmtCs8) {
+        return cf{static_cast<float>(static_cast<int8_t>(raw & 0xffu)), static_cast<float>(static_cast<int8_t>((raw >> 8) & 0xffu))};
+    } else {
+        return cf{static_cast<float>(static_cast<int16_t>(raw & 0xffffu)), static_cast<float>(static_cast<int16_t>(raw >> 16))};
+    }
+}
+
 // Raw-byte staging is wavefront-local: a wave stages exactly the samples its own
 // 64 threads unpack, "a-major": bytes [128 a, 128 a + 128) of the wave's 128*P-byte
 // raw area hold sample n = t + T a of its 64 threads, so lane l reads its P samples
@@ -299,22 +320,44 @@ constexpr float kTwo23 = 8388608.0f;
 // raw_source maps byte j of that area back to the stream: which of the
 // workgroup's frame slots, and which byte of that frame.  16-byte pieces (j % 16
 // == 0) are contiguous and 16-byte aligned in the source because T % 8 == 0.
+// (cs16, 4 bytes per sample: rows of 256 bytes, lane l at 4 l + 256 a, a 256*P-byte area.)
 constexpr int kRawChunk = 128;
-template <class G>
+constexpr int raw_chunk_of(int fmt) { return 64 * sample_bytes_of(fmt); }
+template <class G, int FMT = kFmtCu8>
 RPF_HD void raw_source(int wave_in_wg, int j, int* slot, int* byte_in_frame)
 {
-    const int a = j / kRawChunk;
-    const int tid = wave_in_wg * 64 + ((j % kRawChunk) >> 1);
-    *slot = tid / G::T;
-    *byte_in_frame = 2 * (tid % G::T + G::T * a) + (j & 1);
+    if constexpr (FMT == kFmtCs16) {
+        const int a = j / 256;
+        const int tid = wave_in_wg * 64 + ((j % 256) >> 2);
+        *slot = tid / G::T;
+        *byte_in_frame = 4 * (tid % G::T + G::T * a) + (j & 3);
+    } else {
+        const int a = j / kRawChunk;
+        const int tid = wave_in_wg * 64 + ((j % kRawChunk) >> 1);
+        *slot = tid / G::T;
+        *byte_in_frame = 2 * (tid % G::T + G::T * a) + (j & 1);
+    }
 }
 
 // Unpack the P samples of one thread (datastore.cxx:73-77).  `lane_raw` points at
 // this lane's column of its wave's raw area.  sgn = (-1)^t (n = t + T a, T even).
 // wsgn: per-register window values already multiplied by sgn (WINDOW only).
-template <class G, bool WINDOW>
+template <class G, bool WINDOW, int FMT = kFmtCu8>
 RPF_HD void phase_unpack(const uint8_t* lane_raw, float sgn, const float* wsgn, cf* x)
 {
+    if constexpr (FMT != kFmtCu8) {
+        // v is exact, * sgn exact, * (+-w) rounds once
+#pragma unroll
+        for (int a = 0; a < G::P; ++a) {
+            uint32_t raw;
+            if constexpr (FMT == kFmtCs16) raw = *reinterpret_cast<const uint32_t*>(lane_raw + raw_chunk_of(FMT) * a);
+            else raw = *reinterpret_cast<const uint16_t*>(lane_raw + raw_chunk_of(FMT) * a);
+            const cf f = iq_signed<FMT>(raw);
+            if constexpr (WINDOW) x[a] = f * wsgn[a];
+            else x[a] = f * sgn;
+        }
+        return;
+    }
     // (2^23 + v) * sgn - (2^23 + 127) * sgn = (v - 127) * sgn, every step exact
     const float off = -(kTwo23 + 127.0f) * sgn;
 #pragma unroll

@@ -17,8 +17,9 @@
     const int tid = threadIdx.x;
     const int fs = tid / T, t = tid % T;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    constexpr int RAW_SLOT = kRawChunk * P;           // bytes one wave stages per frame
-    constexpr int PIECES = P / 8;                     // DMA instructions per wave per frame
+    constexpr int RAW_SLOT = raw_chunk_of(FMT) * P;   // bytes one wave stages per frame (FMT: the sample format)
+    constexpr int PIECES = P / 8 * (sample_bytes_of(FMT) / 2);   // DMA instructions per wave per frame
+    static_assert((RAWD - 1) * PIECES <= 63, "the counted wait below: vmcnt is a 6-bit field");
     uint8_t* const wave_raw = raw_base + wave * (RAWD * RAW_SLOT);
 
     // First thing: get the first frames' bytes moving (HBM latency overlaps the
@@ -31,15 +32,15 @@
 #pragma unroll
         for (int d = 0; d < RAWD; ++d)
             if constexpr (STRIDED)
-                stage_raw_pitched<G, DMA>(stream, fb + d * stride, nframes, pitch, wave_raw + d * RAW_SLOT, wave, lane);
+                stage_raw_pitched<G, DMA, FMT>(stream, fb + d * stride, nframes, pitch, wave_raw + d * RAW_SLOT, wave, lane);
             else
-                stage_raw<G, DMA, long>(stream, fb + d * stride, nframes, wave_raw + d * RAW_SLOT, wave, lane);
+                stage_raw<G, DMA, long, FMT>(stream, fb + d * stride, nframes, wave_raw + d * RAW_SLOT, wave, lane);
     }
 
     // Loop-invariant per-thread constants: twiddles, sign, window.
     cf tw[NPASS - 1][P - 1];
     load_twiddles<G, 1, TWLDS>(t, twN, tw);
-    cf* const twtable = reinterpret_cast<cf*>(raw_base + (WG / 64) * RAWD * (kRawChunk * P));
+    cf* const twtable = reinterpret_cast<cf*>(raw_base + (WG / 64) * RAWD * RAW_SLOT);
     if constexpr (TWLDS) {
         fill_twlds<G, 1>(tid, WG, twN, twtable);
         exchange_sync<true>();
@@ -84,7 +85,7 @@
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RAWD - 1) * PIECES) : "memory");
             exchange_sync<false>();
             RPF_STAMP(clk, 0);                   // waiting for the staged bytes
-            phase_unpack<G, WINDOW>(ring_slot + 2 * lane, sgn, wsgn, x);
+            phase_unpack<G, WINDOW, FMT>(ring_slot + sample_bytes_of(FMT) * lane, sgn, wsgn, x);
             // The slot is refilled next: its ds_read_u16 must have RETURNED first (a DMA
             // that hits in L2/MALL can land before queued LDS reads execute -- seen as
             // sporadic 1e-3 errors), so wait for this wave's LDS reads, not just issue.
@@ -97,9 +98,9 @@
             // the slot has been consumed: refill it with the frame RAWD iterations ahead
             if constexpr (!(ABL & 8)) {
                 if constexpr (STRIDED)
-                    stage_raw_pitched<G, DMA>(stream, fb + RAWD * stride, nframes, pitch, ring_slot, wave, lane);
+                    stage_raw_pitched<G, DMA, FMT>(stream, fb + RAWD * stride, nframes, pitch, ring_slot, wave, lane);
                 else
-                    stage_raw<G, DMA, long>(stream, fb + RAWD * stride, nframes, ring_slot, wave, lane);
+                    stage_raw<G, DMA, long, FMT>(stream, fb + RAWD * stride, nframes, ring_slot, wave, lane);
             }
             RPF_STAMP(clk, 3);                   // DMA issue
         }

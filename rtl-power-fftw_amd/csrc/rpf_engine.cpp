@@ -71,6 +71,8 @@ struct rpf_engine {
     // configuration (Params fields Datastore reads)
     int N = 0;
     int step = 0;                 // frame step S in complex samples (rpf_config::frame_step; N = frames side by side)
+    int format = RPF_FORMAT_CU8;  // sample format (RPF_FLAG_SAMPLE_FORMAT)
+    size_t sample_bytes = 2;      // bytes per complex sample, b: every byte count below is b x samples
     bool has_window = false;
     int n_buffers = 0;
     size_t buffer_capacity = 0;
@@ -180,17 +182,17 @@ int fail(rpf_engine* e, int rc, const std::string& msg)
     return rc;
 }
 
-// frames(B) of a stream of B bytes at frame step S: frame f is bytes [2fS, 2fS + 2N).
+// frames(B) of a stream of B bytes at frame step S: frame f is bytes [bfS, bfS + bN), b bytes per sample.
 int64_t frames_in(const rpf_engine* e, size_t nbytes)
 {
-    const size_t frame = 2 * static_cast<size_t>(e->N), step = 2 * static_cast<size_t>(e->step);
+    const size_t frame = e->sample_bytes * static_cast<size_t>(e->N), step = e->sample_bytes * static_cast<size_t>(e->step);
     return nbytes < frame ? 0 : static_cast<int64_t>((nbytes - frame) / step + 1);
 }
 
-// Bytes `frames` frames span: 2N + 2S (frames - 1).
+// Bytes `frames` frames span: bN + bS (frames - 1).
 size_t frame_span(const rpf_engine* e, int64_t frames)
 {
-    return frames < 1 ? 0 : 2 * static_cast<size_t>(e->N) + 2 * static_cast<size_t>(e->step) * static_cast<size_t>(frames - 1);
+    return frames < 1 ? 0 : e->sample_bytes * (static_cast<size_t>(e->N) + static_cast<size_t>(e->step) * static_cast<size_t>(frames - 1));
 }
 
 bool overlapped(const rpf_engine* e) { return e->step != e->N; }
@@ -248,10 +250,10 @@ int launch_fused_hops(rpf_engine* e, const uint8_t* const* d_frames, const int64
         const int64_t wanted = (nframes[0] + e->plan.fpw - 1) / e->plan.fpw;
         const int grid = static_cast<int>(std::min<int64_t>(e->plan.grid, wanted));
         // overlapped frames: the strided instantiation, LDS-DMA where every frame start is 16-byte aligned
-        const long pitch = 2L * e->step;
+        const long pitch = static_cast<long>(e->sample_bytes) * e->step;
         const bool dma1 = e->use_dma && (reinterpret_cast<uintptr_t>(d_frames[0]) % 16) == 0 && pitch % 16 == 0;
         HIP_TRY(e, rpf::launch_fft_accum(e->N, e->variant, e->has_window, dma1, d_frames[0], nframes[0], e->d_twiddles,
-                                         e->d_window, e->d_partial, grid, stream, &e->last, pitch));
+                                         e->d_window, e->d_partial, grid, stream, &e->last, pitch, e->format));
         for (int h = 1; h <= rpf::kMaxHops; ++h) slots->begin[h] = grid;
         *nslots = grid;
         return RPF_OK;
@@ -271,7 +273,7 @@ int launch_fused_hops(rpf_engine* e, const uint8_t* const* d_frames, const int64
     *nslots = slots->begin[H];
     if (grid == 0) return RPF_OK;           // no whole frame anywhere: every slot range is empty
     HIP_TRY(e, rpf::launch_fft_accum_hops(e->N, e->variant, e->has_window, dma, args, e->d_twiddles, e->d_window,
-                                          e->d_partial, grid, stream, &e->last));
+                                          e->d_partial, grid, stream, &e->last, e->format));
     return RPF_OK;
 }
 
@@ -367,7 +369,8 @@ int launch_transform(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hi
     }
     if (e->generic) {
         HIP_TRY(e, rpf::launch_generic(e->N, d_frames, nframes, e->d_window, e->d_chirp, e->d_bhat, e->d_tw_sub,
-                                       e->d_tw_sub2, e->gen_h, e->d_scratch, e->d_partial, /*accumulate=*/false, stream));
+                                       e->d_tw_sub2, e->gen_h, e->d_scratch, e->d_partial, /*accumulate=*/false, stream,
+                                       e->format));
         e->last = e->plan;
         *nslots = 1;
         return RPF_OK;
@@ -412,14 +415,14 @@ int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes,
 int launch_gathered(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out, bool accumulate,
                     hipStream_t stream)
 {
-    const size_t frame = 2 * static_cast<size_t>(e->N);
+    const size_t frame = e->sample_bytes * static_cast<size_t>(e->N);
     if (!e->d_gather) {
         e->gather_frames = std::max<int64_t>(1, static_cast<int64_t>(rpf::kGatherBytes / frame));
         void* p = nullptr;
         HIP_TRY(e, hipMalloc(&p, static_cast<size_t>(e->gather_frames) * frame));
         e->d_gather = static_cast<uint8_t*>(p);
     }
-    const long pitch = 2L * e->step;
+    const long pitch = static_cast<long>(e->sample_bytes) * e->step;
     for (int64_t f0 = 0; f0 < nframes; f0 += e->gather_frames) {
         const int64_t n = std::min(e->gather_frames, nframes - f0);
         HIP_TRY(e, rpf::launch_gather_frames(d_frames + f0 * pitch, n, pitch, static_cast<long>(frame), e->d_gather, stream));
@@ -543,7 +546,7 @@ void worker_main(rpf_engine* e)
         e->recycle_cv.notify_one();
     };
 
-    const size_t step_bytes = 2 * static_cast<size_t>(e->step);    // frame f starts at byte f * step_bytes
+    const size_t step_bytes = e->sample_bytes * static_cast<size_t>(e->step);    // frame f starts at byte f * step_bytes
     const size_t slot_bytes = e->coalesce * e->buffer_capacity;
     size_t carry = 0;             // bytes of an unfinished frame at the end of the previous slot
     const uint8_t* carry_src = nullptr;
@@ -811,6 +814,15 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
                     "Frame step must be between 1 and the number of bins (" + std::to_string(cfg->N) + "), or 0 for " +
                         std::to_string(cfg->N) + "; got " + std::to_string(frame_step) + ".");
     const int step = frame_step == 0 ? cfg->N : frame_step;
+    const int format = static_cast<int>((cfg->flags >> 16) & 0xfu);
+    if (format != RPF_FORMAT_CU8 && format != RPF_FORMAT_CS8 && format != RPF_FORMAT_CS16)
+        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
+                    "Sample format must be 0 (cu8), 1 (cs8) or 2 (cs16); got " + std::to_string(format) + ".");
+    const size_t sample_bytes = format == RPF_FORMAT_CS16 ? 4 : 2;
+    const bool native_k1 = rpf::kernel_supported(cfg->N, 0);
+    // The catch-all path is the one that reads every format at every N: it takes the engines that ask for it and the
+    // signed formats on every size K1 does not serve, whatever family that size runs on with cu8.
+    const bool catch_all = (cfg->flags & RPF_FLAG_CATCH_ALL) != 0 || (format != RPF_FORMAT_CU8 && !native_k1);
     const int variant = static_cast<int>((cfg->flags >> 8) & 0xffu);
     // (asking for the fused four-step kernel is asking for the four-step path)
     // 32768 is served twice, by the split form 2 x 16384 and by the four-step kernels.  Plain runs are faster on the
@@ -818,12 +830,13 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
     // window values next to its two-deep section pipeline (0.175, it was 0.27 before round 3's section sums), the
     // four-step kernels multiply them in as they unpack (0.21 - 0.22).  profiles/r04_sizes.txt.
     const bool windowed_32768 = cfg->N == 32768 && cfg->window != nullptr && variant == 0;
-    const bool mixed = rpf::mixed_supported(cfg->N, variant) && !windowed_32768 &&
+    const bool mixed = !catch_all && rpf::mixed_supported(cfg->N, variant) && !windowed_32768 &&
                        !(cfg->flags & (RPF_FLAG_NO_MIXED_RADIX | RPF_FLAG_FOURSTEP_FUSED));
-    const bool fourstep = !mixed && rpf::fourstep_supported(cfg->N) && variant == 0;
-    const bool bluestein = !mixed && rpf::bluestein_supported(cfg->N) && variant == 0;
-    const bool bigblu = !mixed && rpf::bigblu_supported(cfg->N) && variant == 0;
-    const bool tuned = fourstep || mixed || bluestein || bigblu || rpf::kernel_supported(cfg->N, variant);
+    const bool fourstep = !catch_all && !mixed && rpf::fourstep_supported(cfg->N) && variant == 0;
+    const bool bluestein = !catch_all && !mixed && rpf::bluestein_supported(cfg->N) && variant == 0;
+    const bool bigblu = !catch_all && !mixed && rpf::bigblu_supported(cfg->N) && variant == 0;
+    const bool tuned = !catch_all && (fourstep || mixed || bluestein || bigblu ||
+                                      (rpf::kernel_supported(cfg->N, variant) && (format == RPF_FORMAT_CU8 || variant == 0)));
     const bool generic = !tuned && variant == 0 && rpf::generic_supported(cfg->N);
     if (!tuned && !generic)
         return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
@@ -833,6 +846,9 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
         return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "Argument to 'buffers' must be a positive number.");
     if (cfg->buffer_capacity < 2 || (cfg->buffer_capacity % 2) != 0)
         return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "Buffer size must be a positive even number of bytes.");
+    if (static_cast<size_t>(cfg->buffer_capacity) % sample_bytes != 0)
+        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
+                    "Buffer size must be a multiple of the sample size (" + std::to_string(sample_bytes) + " bytes).");
 
     int ndev = 0;
     hipError_t err = hipGetDeviceCount(&ndev);
@@ -847,6 +863,8 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
     rpf_engine* e = new rpf_engine();
     e->N = cfg->N;
     e->step = step;
+    e->format = format;
+    e->sample_bytes = sample_bytes;
     e->has_window = cfg->window != nullptr;
     e->n_buffers = cfg->n_buffers;
     e->buffer_capacity = static_cast<size_t>(cfg->buffer_capacity);
@@ -997,9 +1015,9 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
         if (e->has_window)
             CREATE_TRY(hipMemcpy(e->d_window, window_t.data(), sizeof(float) * window_t.size(), hipMemcpyHostToDevice));
     } else {
-        CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, true, e->device, &e->plan));
+        CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, true, e->device, &e->plan, e->format));
         rpf::LaunchInfo tmp;
-        CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, false, e->device, &tmp));
+        CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, false, e->device, &tmp, e->format));
         e->plan.grid = std::min(e->plan.grid, tmp.grid);
         partial_slots = e->plan.grid + rpf::kMaxHops;    // a workgroup leaves one partial per hop it touches
     }
@@ -1058,7 +1076,7 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
         e->empty_buffers.push_back(&b);
     }
     // device staging ring: head room for a carried partial frame + one buffer
-    e->head_room = ((2 * static_cast<size_t>(e->N)) + 255) / 256 * 256;
+    e->head_room = ((e->sample_bytes * static_cast<size_t>(e->N)) + 255) / 256 * 256;
     // a slot (= one transform launch) holds as many buffers as fit 32 MB, at least one -- more than the pool has where the
     // buffers are small: they return to the producer when their copy lands, not when the slot is launched
     e->coalesce = std::max<size_t>(1, (32u << 20) / e->buffer_capacity);
@@ -1151,6 +1169,9 @@ int rpf_buffer_submit(rpf_engine* e, uint8_t* buf, size_t nbytes)
     if (!b) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_buffer_submit: not an engine buffer");
     if (nbytes > e->buffer_capacity || (nbytes % 2) != 0)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_buffer_submit: size must be even and <= capacity");
+    if (nbytes % e->sample_bytes != 0)     // a sample never straddles two buffers (frames may)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_buffer_submit: size must be a multiple of the sample size (" +
+                                                     std::to_string(e->sample_bytes) + " bytes)");
     if (!e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_buffer_submit: no acquisition running");
     b->size = nbytes;   // buffer.resize(dataNeeded), acquisition.cxx:302
     // acquisition.cxx:320-323
@@ -1271,8 +1292,9 @@ int rpf_accumulate(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t 
     std::vector<HostBuffer> pieces;
     for (const auto& r : e->registered) {
         if (stream >= r.first && stream + nbytes <= r.first + r.second) {
-            const size_t piece = std::min<size_t>(e->coalesce * e->buffer_capacity, static_cast<size_t>(8) << 20) & ~static_cast<size_t>(1);
-            const size_t even = nbytes & ~static_cast<size_t>(1);
+            const size_t whole = ~(e->sample_bytes - 1);       // (2 or 4: whole samples)
+            const size_t piece = std::min<size_t>(e->coalesce * e->buffer_capacity, static_cast<size_t>(8) << 20) & whole;
+            const size_t even = nbytes & whole;
             pieces.reserve(even / piece + 1);
             for (size_t at = 0; at < even; at += piece) {
                 HostBuffer hb;
@@ -1294,7 +1316,7 @@ int rpf_accumulate(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t 
         uint8_t* buf = nullptr;
         rc = rpf_buffer_acquire(e, &buf, nullptr);
         if (rc != RPF_OK) break;
-        const size_t n = std::min(cap, (nbytes - pos) & ~static_cast<size_t>(1));
+        const size_t n = std::min(cap, (nbytes - pos) & ~(e->sample_bytes - 1));
         if (n == 0) {
             rpf_buffer_unget(e, buf);
             break;
@@ -1320,8 +1342,8 @@ int rpf_accumulate_device(rpf_engine* e, const void* d_stream, size_t nbytes, in
     if (e->worker_running)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: acquisition running");
     if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
-    if (reinterpret_cast<uintptr_t>(d_stream) & 1)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: d_stream must be at least 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
     if (reinterpret_cast<uintptr_t>(d_pwr_out) & 15)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: d_pwr_out must be 16-byte aligned");
     DeviceScope on_device(e->device);
@@ -1343,8 +1365,8 @@ int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t
 {
     if (!e || !d_stream) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: NULL argument");
     if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: acquisition running");
-    if (reinterpret_cast<uintptr_t>(d_stream) & 1)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: d_stream must be at least 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
     if (overlapped(e) && !is_k1(e))
         return fail(e, RPF_ERR_INVALID_ARGUMENT,
                     "rpf_device_fused: overlapped frames (frame step < N) on this size need rpf_accumulate_device");
@@ -1398,8 +1420,8 @@ static int check_hops(rpf_engine* e, const char* who, const void* const* d_strea
     for (int h = 0; h < H; ++h) {
         if (repeats[h] < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
         if (!d_streams[h] && nbytes[h]) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL stream");
-        if (reinterpret_cast<uintptr_t>(d_streams[h]) & 1)
-            return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": streams must be at least 2-byte aligned");
+        if (reinterpret_cast<uintptr_t>(d_streams[h]) & (e->sample_bytes - 1))
+            return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": streams must be at least 2-byte aligned (4-byte for 16-bit samples)");
         (*frames)[h] = std::min<int64_t>(frames_in(e, nbytes[h]), repeats[h]);
     }
     return RPF_OK;
@@ -1408,6 +1430,10 @@ static int check_hops(rpf_engine* e, const char* who, const void* const* d_strea
 int rpf_max_hops_per_launch(void) { return rpf::kMaxHops; }
 
 int64_t rpf_frames_in(const rpf_engine* e, size_t nbytes) { return e ? frames_in(e, nbytes) : 0; }
+
+int rpf_sample_bytes(const rpf_engine* e) { return e ? static_cast<int>(e->sample_bytes) : 0; }
+
+int rpf_sample_format(const rpf_engine* e) { return e ? e->format : -1; }
 
 size_t rpf_frame_span(const rpf_engine* e, int64_t frames) { return e ? frame_span(e, frames) : 0; }
 

@@ -10,7 +10,8 @@
 // other than memory, and is exact to the same float32 bar.  Lengths that are not powers of two
 // go through Bluestein's identity (bluestein_tables.h) on top of it.
 //
-//   gen_load      u8 IQ -> (v - 127) * (-1)^n [* window]  (Bluestein: * g[n], zero-padded to M)
+//   gen_load      u8 IQ -> (v - 127) * (-1)^n [* window]  (Bluestein: * g[n], zero-padded to M); signed 8- and
+//                 16-bit IQ: v instead of v - 127
 //   gen_radix4/2  y[q + s (R p + r)] = W_n^{p r} * sum_k x[q + s (p + k n/R)] W_R^{k r}
 //   gen_mul_conj  Bluestein: z = conj(A * bhat)
 //   gen_accum     pwr[k] += sum over the batch of |X[k]|^2, in double, one writer per bin
@@ -45,7 +46,8 @@ __device__ __forceinline__ cf tw_lookup(const TwoLevel& t, unsigned idx)
 }
 
 // BLU: mult = g (N complex: (-1)^n, window and chirp folded in); else window (N floats) or null.
-template <bool BLU>
+// FMT: the sample format (fft_core.h); the only place this path reads samples.
+template <bool BLU, int FMT = kFmtCu8>
 __global__ __launch_bounds__(kThreads) void gen_load_kernel(const uint8_t* __restrict__ stream, int N, int M,
                                                            long total, const float* __restrict__ window,
                                                            const cf* __restrict__ g, cf* __restrict__ out)
@@ -56,8 +58,15 @@ __global__ __launch_bounds__(kThreads) void gen_load_kernel(const uint8_t* __res
     const int n = static_cast<int>(i - f * M);
     cf v = cf{0.0f, 0.0f};
     if (n < N) {
-        const uint32_t iq = *reinterpret_cast<const uint16_t*>(stream + (f * N + n) * 2);
-        const cf x = iq_plus_2p23(iq) - (kTwo23 + 127.0f);            // exact (datastore.cxx:75)
+        cf x;
+        if constexpr (FMT == kFmtCu8) {
+            const uint32_t iq = *reinterpret_cast<const uint16_t*>(stream + (f * N + n) * 2);
+            x = iq_plus_2p23(iq) - (kTwo23 + 127.0f);                  // exact (datastore.cxx:75)
+        } else if constexpr (FMT == kFmtCs8) {
+            x = iq_signed<FMT>(*reinterpret_cast<const uint16_t*>(stream + (f * N + n) * 2));
+        } else {
+            x = iq_signed<FMT>(*reinterpret_cast<const uint32_t*>(stream + (f * N + n) * 4));
+        }
         if constexpr (BLU) {
             v = cmul(x, g[n]);
         } else {
@@ -211,14 +220,14 @@ static cf* run_fft(cf* d_a, cf* d_b, long M, int frames, const cf* d_t0, const c
     return src;
 }
 
-// Frames [0, nframes) of d_stream (frame f = bytes [2N f, 2N (f+1))) -> d_pwr[N]
+// Frames [0, nframes) of d_stream (frame f = bytes [bN f, bN (f+1)), b = bytes per sample of `fmt`) -> d_pwr[N]
 // (overwritten unless accumulate).  d_window: N floats or null (power-of-two N);
 // d_g / d_bhat: bluestein_tables.h's tables (other N).  d_scratch: generic_scratch_bytes(N).
 hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const float* d_window, const cf* d_g,
                           const cf* d_bhat, const cf* d_t0, const cf* d_t1, int h, cf* d_scratch, double* d_pwr,
-                          bool accumulate, hipStream_t stream)
+                          bool accumulate, hipStream_t stream, int fmt)
 {
-    if (!generic_supported(N) || nframes < 1) return hipErrorInvalidValue;
+    if (!generic_supported(N) || nframes < 1 || fmt < kFmtCu8 || fmt > kFmtCs16) return hipErrorInvalidValue;
     const long M = generic_length(N);
     const bool blu = M != N;
     const int batch = generic_batch(N);
@@ -227,15 +236,15 @@ hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const fl
     bool acc = accumulate;
     for (long done = 0; done < nframes; done += batch) {
         const int nb = static_cast<int>(std::min<long>(batch, nframes - done));
-        const uint8_t* src = d_stream + static_cast<size_t>(done) * 2 * N;
+        const uint8_t* src = d_stream + static_cast<size_t>(done) * sample_bytes_of(fmt) * N;
         const long total = static_cast<long>(nb) * M;
         const unsigned blocks = static_cast<unsigned>((total + kThreads - 1) / kThreads);
-        if (blu)
-            hipLaunchKernelGGL(gen_load_kernel<true>, dim3(blocks), dim3(kThreads), 0, stream, src, N, static_cast<int>(M),
-                               total, d_window, d_g, d_a);
-        else
-            hipLaunchKernelGGL(gen_load_kernel<false>, dim3(blocks), dim3(kThreads), 0, stream, src, N, static_cast<int>(M),
-                               total, d_window, d_g, d_a);
+        using LoadFn = void (*)(const uint8_t*, int, int, long, const float*, const cf*, cf*);
+        static const LoadFn load[3][2] = {{gen_load_kernel<false, kFmtCu8>, gen_load_kernel<true, kFmtCu8>},
+                                          {gen_load_kernel<false, kFmtCs8>, gen_load_kernel<true, kFmtCs8>},
+                                          {gen_load_kernel<false, kFmtCs16>, gen_load_kernel<true, kFmtCs16>}};
+        hipLaunchKernelGGL(load[fmt][blu ? 1 : 0], dim3(blocks), dim3(kThreads), 0, stream, src, N, static_cast<int>(M), total,
+                           d_window, d_g, d_a);
         cf* res = run_fft(d_a, d_b, M, nb, d_t0, d_t1, h, stream);
         if (blu) {
             hipLaunchKernelGGL(gen_mul_conj_kernel, dim3(blocks), dim3(kThreads), 0, stream, res, d_bhat, static_cast<int>(M),

@@ -26,23 +26,26 @@ bool kernel_supported(int N, int vid = 0);
 
 // Persistent-grid geometry for N on `device`: li->grid is the number of
 // workgroups that are simultaneously resident (occupancy x CU count).
-hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, LaunchInfo* li);
+// fmt: the sample format (fft_core.h kFmt*); the signed formats have variant 0 only and may come out with another
+// grid than cu8 (cs16 stages twice the bytes in LDS) -- li says what was chosen.
+hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, LaunchInfo* li, int fmt = kFmtCu8);
 
 // Fused unpack + FFT + |X|^2 accumulate over frames [0, nframes) of d_stream
-// (frame f = bytes [pitch f, pitch f + 2N); pitch 0 = 2N).  Writes one partial spectrum of N doubles
+// (frame f = bytes [pitch f, pitch f + bN); pitch 0 = bN; b = 2, or 4 for 16-bit samples: `fmt`; written for b = 2 below).  Writes one partial spectrum of N doubles
 // per workgroup to d_partial (every workgroup writes, zeros included).
 // `grid` is the number of workgroups to launch (<= the planned grid).  pitch: even, <= 2N; any pitch
 // but 2N runs the strided instantiation (use_dma then also needs pitch % 16 == 0).
 hipError_t launch_fft_accum(int N, int vid, bool window, bool use_dma, const uint8_t* d_stream,
                             long nframes, const cf* d_twiddles, const float* d_window,
-                            double* d_partial, int grid, hipStream_t stream, LaunchInfo* li, long pitch = 0);
+                            double* d_partial, int grid, hipStream_t stream, LaunchInfo* li, long pitch = 0,
+                            int fmt = kFmtCu8);
 // The same over the hops of `hops` (hop_partition.h: frame f of hop h = bytes [2N f, 2N (f+1)) of
 // hops.stream[h]) in ONE launch.  Workgroup w writes one partial spectrum of N doubles per hop it
 // touches, at slot hops.slot_bias[h] + w of d_partial.  `grid` is what partition_hops returned
 // for (li->fpw, the planned grid).
 hipError_t launch_fft_accum_hops(int N, int vid, bool window, bool use_dma, const HopArgs& hops,
                                  const cf* d_twiddles, const float* d_window, double* d_partial, int grid,
-                                 hipStream_t stream, LaunchInfo* li);
+                                 hipStream_t stream, LaunchInfo* li, int fmt = kFmtCu8);
 
 // d_out[bin] = (accumulate ? d_out[bin] : 0) + sum_{s < nslots} d_partial[s*stride + bin],
 // summed in a fixed order (deterministic).
@@ -138,7 +141,7 @@ void generic_twiddle_tables(int N, std::vector<cf>& t0, std::vector<cf>& t1, int
 // d_g (N) / d_bhat (M): bluestein_tables.h's tables (other N).
 hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const float* d_window, const cf* d_g,
                           const cf* d_bhat, const cf* d_t0, const cf* d_t1, int h, cf* d_scratch, double* d_pwr,
-                          bool accumulate, hipStream_t stream);
+                          bool accumulate, hipStream_t stream, int fmt = kFmtCu8);
 
 // ---- overlapped frames on the other kernel families (rpf_frames.hip) --------------------------------
 // d_dst[f * frame_bytes .. (f+1) * frame_bytes) = d_src[f * pitch .. f * pitch + frame_bytes) for f < nframes:

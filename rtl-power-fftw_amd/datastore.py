@@ -19,15 +19,21 @@ class Params:
 
     def __init__(self, N=512, buffers=5, buf_length=BASE_BUF * DEFAULT_BUF_MULTIPLIER,
                  repeats=None, window=False, sample_rate=2000000, cfreq=1420405752,
-                 linear=False, baseline=False, frame_step=None):
+                 linear=False, baseline=False, frame_step=None, sample_format="cu8"):
         self.N = N
+        # what one complex sample of the stream is: "cu8" (the reference's), "cs8", "cs16" (RPF_FORMAT_*)
+        if sample_format not in _lib.FORMATS:
+            raise RPFError("Unknown sample format '%s' (one of: cu8, cs8, cs16)." % (sample_format,),
+                           ReturnValue.InvalidArgument)
+        self.sample_format = sample_format
         # frame step S in complex samples (rpf_config::frame_step): frame f = samples [f S, f S + N); None = N
         self.frame_step = N if frame_step is None else frame_step
         self.buffers = buffers
         self.buf_length = buf_length
         # params.h:56: repeats = buf_length/(2*N) unless -n/-t say otherwise -- a sample budget, which overlapped
         # frames turn into more frames from the same samples
-        self.repeats = (frames_for_budget(buf_length // (2 * N), N, self.frame_step) if repeats is None
+        self.repeats = (frames_for_budget(buf_length // (_lib.SAMPLE_BYTES[sample_format] * N), N, self.frame_step)
+                        if repeats is None
                         else repeats)
         self.window = window
         self.sample_rate = sample_rate
@@ -43,14 +49,15 @@ def frames_for_budget(r0, N, step):
     return (r0 - 1) * N // step + 1
 
 
-def frames_in(nbytes, N, step):
-    """frames(B) = B < 2N ? 0 : (B - 2N) / (2S) + 1 (rpf_frames_in)."""
-    return 0 if nbytes < 2 * N else (nbytes - 2 * N) // (2 * step) + 1
+def frames_in(nbytes, N, step, sample_bytes=2):
+    """frames(B) = B < bN ? 0 : (B - bN) / (bS) + 1 (rpf_frames_in); b = sample_bytes."""
+    b = sample_bytes
+    return 0 if nbytes < b * N else (nbytes - b * N) // (b * step) + 1
 
 
-def frame_span(frames, N, step):
-    """Bytes `frames` frames span: 2N + 2S (frames - 1) (rpf_frame_span)."""
-    return 0 if frames < 1 else 2 * N + 2 * step * (frames - 1)
+def frame_span(frames, N, step, sample_bytes=2):
+    """Bytes `frames` frames span: bN + bS (frames - 1) (rpf_frame_span); b = sample_bytes."""
+    return 0 if frames < 1 else sample_bytes * (N + step * (frames - 1))
 
 
 class Datastore:
@@ -76,7 +83,7 @@ class Datastore:
         cfg.n_buffers = params.buffers
         cfg.buffer_capacity = params.buf_length
         cfg.device = device
-        cfg.flags = flags
+        cfg.flags = flags | _lib.FLAG_SAMPLE_FORMAT(_lib.FORMATS[getattr(params, "sample_format", "cu8")])
         cfg.frame_step = getattr(params, "frame_step", params.N)
         rc = self._lib.rpf_engine_create(ctypes.byref(cfg), ctypes.byref(self._handle))
         if rc != 0:
@@ -222,6 +229,16 @@ class Datastore:
     def frame_span(self, frames):
         """rpf_frame_span: bytes `frames` frames span at this engine's frame step."""
         return self._lib.rpf_frame_span(self._handle, frames)
+
+    @property
+    def sample_bytes(self):
+        """rpf_sample_bytes: bytes per complex sample of this engine's format (2, 2, 4)."""
+        return self._lib.rpf_sample_bytes(self._handle)
+
+    @property
+    def sample_format(self):
+        """rpf_sample_format: the engine's RPF_FORMAT_* value."""
+        return self._lib.rpf_sample_format(self._handle)
 
     def max_hops_per_launch(self):
         return self._lib.rpf_max_hops_per_launch()

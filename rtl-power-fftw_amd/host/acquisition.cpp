@@ -53,7 +53,7 @@ void Acquisition::run()
     }
     if (!tuned) throw TuneError(freq_);
     if (chatty()) std::cerr << "Device tuned to: " << tuned_freq_ << " Hz" << std::endl;
-    if (sharded_ && !source_.position(shard_.hop_base, 2 * static_cast<uint64_t>(options_.step()) *
+    if (sharded_ && !source_.position(shard_.hop_base, static_cast<uint64_t>(options_.sample_bytes()) * static_cast<uint64_t>(options_.step()) *
                                                           static_cast<uint64_t>(shard_.first_frame)))
         throw RPFexception("This sample source cannot be split across devices.", ReturnValue::InvalidArgument);
 

@@ -46,8 +46,11 @@ struct Params {
   // 0 = N, frames side by side as in the reference.
   int frame_step = 0;
   int64_t step() const { return frame_step > 0 ? frame_step : N; }
-  // bytes `frames` frames span (rpf_frame_span): 2N + 2S (frames - 1)
-  int64_t frame_span(int64_t frames) const { return frames < 1 ? 0 : 2 * static_cast<int64_t>(N) + 2 * step() * (frames - 1); }
+  // What one complex sample of the stream is (RPF_FORMAT_*, --format): cu8, the reference's, unless told otherwise.
+  int sample_format = RPF_FORMAT_CU8;
+  int64_t sample_bytes() const { return sample_format == RPF_FORMAT_CS16 ? 4 : 2; }
+  // bytes `frames` frames span (rpf_frame_span): bN + bS (frames - 1), b bytes per sample
+  int64_t frame_span(int64_t frames) const { return frames < 1 ? 0 : sample_bytes() * (static_cast<int64_t>(N) + step() * (frames - 1)); }
   // a sample budget of r0 side-by-side frames as frames at step S: floor((r0 - 1) N / S) + 1 (r0 at S = N)
   int64_t frames_for_budget(int64_t r0) const { return r0 < 1 ? r0 : (r0 - 1) * N / step() + 1; }
   int sample_rate = 2000000;
@@ -98,7 +101,7 @@ public:
     cfg.n_buffers = params.buffers;
     cfg.buffer_capacity = params.buf_length;
     cfg.device = device_override >= 0 ? device_override : params.device;
-    cfg.flags = RPF_FLAG_NONE;
+    cfg.flags = RPF_FLAG_NONE | RPF_FLAG_SAMPLE_FORMAT(params.sample_format);
     cfg.frame_step = params.frame_step;
     int rc = rpf_engine_create(&cfg, &engine_);
     if (rc != RPF_OK) throw RPFexception(rpf_last_global_error(), (ReturnValue)rc);

@@ -65,7 +65,7 @@ int rpf_host_parse_frames(int argc, const char* const* argv, int samplerate, int
         *N = o.N;
         *step = static_cast<int>(o.step());
         *repeats = o.repeats;
-        *samples_per_acq = o.frame_span(o.repeats) / 2;
+        *samples_per_acq = o.frame_span(o.repeats) / o.sample_bytes();
         return 0;
     } catch (RPFexception& e) {
         copy_out(e.what(), msg, cap);

@@ -51,7 +51,9 @@ const Spec kSpecs[] = {
     {'t', "time", Kind::Text, "seconds", "Integration time (incompatible with -n)."},
     {'w', "window", Kind::Text, "file|-", "Use window function, from file or stdin."},
     // additive (not in the reference)
-    {0, "input", Kind::Text, "file|-", "Replay interleaved 8-bit IQ samples from a file or stdin."},
+    {0, "input", Kind::Text, "file|-", "Replay interleaved IQ samples (see --format) from a file or stdin."},
+    {0, "format", Kind::Text, "cu8|cs8|cs16",
+     "Sample format of --input: cu8 (unsigned 8-bit, the default), cs8 (signed 8-bit), cs16 (signed 16-bit little-endian)."},
     {0, "synthetic", Kind::Int64, "seed", "Use the built-in synthetic receiver instead of a dongle."},
     {0, "gpu", Kind::Int, "ordinal", "HIP device to run on."},
     {0, "gpus", Kind::Text, "a,b,...", "HIP devices to spread a scan over (one engine per listed device)."},
@@ -263,8 +265,21 @@ Options parse_command_line(int argc, const char* const* argv)
         const int64_t cut = static_cast<int64_t>(std::floor(static_cast<double>(o.N) * o.frame_overlap / 100));
         o.frame_step = static_cast<int>(std::max<int64_t>(1, o.N - cut));
     }
+    if (p.has("format")) {
+        const std::string text = p.get("format");
+        if (text == "cu8") o.sample_format = RPF_FORMAT_CU8;
+        else if (text == "cs8") o.sample_format = RPF_FORMAT_CS8;
+        else if (text == "cs16") o.sample_format = RPF_FORMAT_CS16;
+        else
+            throw RPFexception("Unknown sample format given to --format: " + text + ".\n"
+                               "Expecting one of cu8, cs8, cs16. Exiting.", ReturnValue::InvalidArgument);
+        // the format describes a replayed file; a dongle and the synthetic receiver deliver cu8
+        if (o.sample_format != RPF_FORMAT_CU8 && !p.has("input"))
+            throw RPFexception("Option --format " + text + " needs --input: a dongle and --synthetic deliver cu8 "
+                               "(one of cu8, cs8, cs16). Exiting.", ReturnValue::InvalidArgument);
+    }
     if (p.has("repeats")) o.repeats = to_number<int64_t>(*find_spec("--repeats"), p.get("repeats"));
-    else o.repeats = o.frames_for_budget(o.buf_length / (2 * o.N));  // params.cxx:214-217, as a sample budget
+    else o.repeats = o.frames_for_budget(o.buf_length / (o.sample_bytes() * o.N));  // params.cxx:214-217, as a sample budget
     if (p.has("time")) {
         o.integration_time = parse_time(p.get("time"));
         if (o.integration_time <= 0)

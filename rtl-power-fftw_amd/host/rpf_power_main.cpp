@@ -359,7 +359,7 @@ int run(int argc, char** argv)
 
     std::unique_ptr<SampleSource> source;
     RtlSdrSource* dongle = nullptr;
-    if (!options.input_file.empty()) source.reset(new FileSource(options.input_file));
+    if (!options.input_file.empty()) source.reset(new FileSource(options.input_file, static_cast<size_t>(options.sample_bytes())));
     else if (options.synthetic) source.reset(new SyntheticSource(options.synthetic_seed));
     else source.reset(dongle = new RtlSdrSource(options.dev_index));   // rtl_power_fftw.cxx:65
 

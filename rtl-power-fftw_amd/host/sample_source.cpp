@@ -11,7 +11,7 @@
 
 namespace rpf_host {
 
-FileSource::FileSource(const std::string& path) : path_(path)
+FileSource::FileSource(const std::string& path, size_t sample_bytes) : path_(path), sample_bytes_(sample_bytes)
 {
     if (path == "-") {
         file_ = stdin;
@@ -34,7 +34,7 @@ bool FileSource::read(Buffer& buffer)
     // frame.  Those bytes are data, not dropped samples.
     const size_t got = std::fread(buffer.data(), 1, buffer.size(), file_);
     if (got < buffer.size()) exhausted_ = true;
-    const size_t usable = got & ~static_cast<size_t>(1);
+    const size_t usable = got - got % sample_bytes_;          // whole samples only
     if (usable == 0) return false;
     buffer.resize(usable);
     return true;
@@ -43,7 +43,7 @@ bool FileSource::read(Buffer& buffer)
 std::unique_ptr<SampleSource> FileSource::clone() const
 {
     if (!owns_) return nullptr;                  // stdin cannot be read twice
-    std::unique_ptr<SampleSource> copy(new FileSource(path_));
+    std::unique_ptr<SampleSource> copy(new FileSource(path_, sample_bytes_));
     copy->set_sample_rate(rate_);
     return copy;
 }

@@ -45,10 +45,11 @@ protected:
     int64_t frequency_ = 0;
 };
 
-// Interleaved u8 I/Q from a file or stdin ("-"); a short read ends the data.
+// Interleaved I/Q from a file or stdin ("-"), `sample_bytes` bytes per complex sample (2: cu8 / cs8, 4: cs16); a
+// short read ends the data.
 class FileSource : public SampleSource {
 public:
-    explicit FileSource(const std::string& path);
+    explicit FileSource(const std::string& path, size_t sample_bytes = 2);
     ~FileSource() override;
     bool read(Buffer& buffer) override;
     bool retry_after_short_read() const override { return false; }
@@ -60,6 +61,7 @@ private:
     std::FILE* file_ = nullptr;
     bool owns_ = false;
     bool exhausted_ = false;
+    size_t sample_bytes_ = 2;
 };
 
 // The integer-only receiver model of rtl-power-fftw_amd/synth.py (noise_tones_iq):

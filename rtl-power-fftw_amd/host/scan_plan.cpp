@@ -43,10 +43,10 @@ void Plan::print() const
 {
     const Options& o = options_;
     std::cerr << "Number of bins: " << o.N << std::endl;
-    std::cerr << "Total number of (complex) samples to collect: " << o.frame_span(o.repeats) / 2 << std::endl;
+    std::cerr << "Total number of (complex) samples to collect: " << o.frame_span(o.repeats) / o.sample_bytes() << std::endl;
     std::cerr << "Buffer length: " << o.buf_length << std::endl;
     std::cerr << "Number of averaged spectra: " << o.repeats << std::endl;
-    std::cerr << "Estimated time of measurements: " << static_cast<double>(o.frame_span(o.repeats) / 2) / actual_samplerate
+    std::cerr << "Estimated time of measurements: " << static_cast<double>(o.frame_span(o.repeats) / o.sample_bytes()) / actual_samplerate
               << " seconds" << std::endl;
     if (o.strict_time)
         std::cerr << "Acquisition will unconditionally terminate after " << o.integration_time << " seconds."

@@ -19,13 +19,14 @@ def shard_frames(total_frames, world_size, rank):
     return first, end - first
 
 
-def frame_byte_range(first, count, N, step=None):
+def frame_byte_range(first, count, N, step=None, sample_bytes=2):
     """(offset, length) in bytes of frames [first, first + count) of one hop at frame step S (None: N) -- frame f is
-    bytes [2 f S, 2 f S + 2N) -- for callers that split one hop's frames: the piece a shard reads."""
+    bytes [b f S, b f S + bN), b = sample_bytes -- for callers that split one hop's frames: the piece a shard reads."""
     step = N if step is None else step
+    b = sample_bytes
     if count < 1:
-        return 2 * step * first, 0
-    return 2 * step * first, 2 * N + 2 * step * (count - 1)
+        return b * step * first, 0
+    return b * step * first, b * (N + step * (count - 1))
 
 
 def shard_hops(n_hops, frames_per_hop, world_size, rank):

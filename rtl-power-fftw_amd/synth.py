@@ -58,6 +58,50 @@ def noise_tones_iq(seed, nsamples, chunk=1 << 22, first=0):
     return out
 
 
+# ---- signed sample formats (rpf_engine.h RPF_FORMAT_CS8 / RPF_FORMAT_CS16); all return uint8 byte arrays ----
+def to_cs8(u8_stream):
+    """The cs8 stream that says what the cu8 stream `u8_stream` says: v - 127 per byte, as signed bytes.  A cu8
+    byte of 255 (= +128) has no cs8 counterpart: clamp the input to <= 254 first."""
+    u = np.asarray(u8_stream, dtype=np.uint8)
+    if u.size and int(u.max()) > 254:
+        raise ValueError("to_cs8: a cu8 byte of 255 (+128) does not fit a signed byte; clamp to 254 first")
+    return (u.astype(np.int16) - 127).astype(np.int8).view(np.uint8)
+
+
+def to_cs16(cs8_stream, shift=0):
+    """The cs16 (little-endian) stream holding the values of `cs8_stream` times 2**shift (shift <= 8)."""
+    v = np.asarray(cs8_stream, dtype=np.uint8).view(np.int8).astype(np.int32) << shift
+    assert 0 <= shift <= 8
+    return v.astype("<i2").view(np.uint8)
+
+
+def cs16_values(cs16_stream):
+    """The int16 values of a cs16 byte stream (I0, Q0, I1, Q1, ...)."""
+    return np.asarray(cs16_stream, dtype=np.uint8).view("<i2")
+
+
+_TONE8_C16 = np.array([3000, 2121, 0, -2121, -3000, -2121, 0, 2121], dtype=np.int64)
+_TONE8_S16 = np.array([0, 2121, 3000, 2121, 0, -2121, -3000, -2121], dtype=np.int64)
+
+
+def noise_tones_cs16(seed, nsamples, chunk=1 << 21):
+    """Full-range 16-bit stream (both bytes of every value random): approximately Gaussian noise (sum of four
+    uniform 16-bit words, sigma ~ 6000) plus a complex tone of period 8 and amplitude 3000, clipped to int16.
+    4 * nsamples bytes, cs16 little-endian.  Integer arithmetic only, like noise_tones_iq."""
+    out = np.empty(2 * nsamples, dtype="<i2")
+    pos = 0
+    while pos < nsamples:
+        n = min(chunk, nsamples - pos)
+        # two 64-bit words per complex sample: word 2k -> I noise, word 2k + 1 -> Q noise
+        w = splitmix64(seed, 2 * n, offset=2 * pos).view(np.uint16).reshape(n, 2, 4).astype(np.int64)
+        noise = (w.sum(axis=2) - 131070) * 10392 // 65536          # sigma 65536 / sqrt(3) * 10392 / 65536 ~ 6000
+        k = np.arange(pos, pos + n, dtype=np.int64)
+        out[2 * pos: 2 * (pos + n): 2] = np.clip(noise[:, 0] + _TONE8_C16[k % 8], -32768, 32767)
+        out[2 * pos + 1: 2 * (pos + n) + 1: 2] = np.clip(noise[:, 1] + _TONE8_S16[k % 8], -32768, 32767)
+        pos += n
+    return out.view(np.uint8)
+
+
 def _wrap64(v):
     """A 64-bit pattern as the signed Python int torch's int64 holds."""
     v &= (1 << 64) - 1
