@@ -32,7 +32,8 @@ extern "C" {
 
 #define RPF_ABI_VERSION 2   /* 2: rpf_accumulate_device_hops, rpf_device_fused_hops, rpf_scan_reducer_*;
                                additive within 2: rpf_config::frame_step, rpf_frames_in, rpf_frame_span;
-                               RPF_FLAG_SAMPLE_FORMAT, RPF_FLAG_CATCH_ALL, rpf_sample_bytes, rpf_sample_format */
+                               RPF_FLAG_SAMPLE_FORMAT, RPF_FLAG_CATCH_ALL, rpf_sample_bytes, rpf_sample_format;
+                               RPF_FLAG_BIN_STATS, rpf_has_bin_stats, rpf_get_bin_stats, rpf_accumulate_device_stats */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -113,6 +114,26 @@ typedef struct rpf_config {
 #define RPF_FLAG_SAMPLE_FORMAT(f) (((uint32_t)(f) & 0xfu) << 16)
 /* Any N, any format on the catch-all Stockham path (A/B measurement, and the comparator of the format tests). */
 #define RPF_FLAG_CATCH_ALL 16u
+/* Per-bin statistics beside the power.  With re, im the float32 outputs of frame f's transform converted to double:
+ *   p     = fma(im, im, re * re)                 the frame's power in the bin, correctly rounded (re * re is exact)
+ *   S1[k] = the power accumulator, unchanged:    acc = fma(im, im, fma(re, re, acc))
+ *   S2[k] = sum over the frames of p^2:          s2 = fma(p, p, s2)
+ *   PK[k] = the largest p (peak hold), from 0
+ * and across frame slots, workgroups, batches and launches S1 and S2 add in double, PK takes the maximum.  From them,
+ * with M = repeats_done, the spectral kurtosis estimator SK[k] = (M+1)/(M-1) (M S2[k] / S1[k]^2 - 1) (NaN for M < 2 or
+ * S1[k] = 0; rtl-power-fftw_amd/stats.py and host/datastore.h compute it): 1 for Gaussian noise, towards 0 for a steady
+ * carrier, above 1 for anything intermittent.
+ * An engine created with the flag keeps S2 and PK beside the power on the buffer-queue path (rpf_begin .. rpf_finish,
+ * rpf_accumulate; rpf_get_bin_stats) and in rpf_accumulate_device_stats; rpf_get_power, rpf_accumulate and
+ * rpf_accumulate_device keep their meaning and return S1.  Served natively by the LDS-resident kernel (powers of two
+ * 64 .. 8192, all three sample formats, any frame step) with two more register accumulators per bin; at every other size
+ * a stats engine runs on the catch-all Stockham path, as a cs8 / cs16 engine does (README.md, "Per-bin statistics").
+ * Without the flag nothing changes: same kernels, same scratch, same results.
+ * RPF_ERR_INVALID_ARGUMENT from rpf_engine_create, before any device is touched: together with RPF_FLAG_FOURSTEP_FUSED
+ * or with RPF_FLAG_VARIANT(k), k != 0.  On a stats engine rpf_device_fused, rpf_device_fused_hops and rpf_device_reduce
+ * return RPF_ERR_INVALID_ARGUMENT; rpf_accumulate_device_hops runs hop by hop (never the one-launch scan) and returns the
+ * power alone; rpf_scan_reducer_* carry the power alone (a maximum beside RCCL's sum is not built). */
+#define RPF_FLAG_BIN_STATS 32u
 
 /* ABI version of the loaded library. */
 int rpf_abi_version(void);
@@ -155,6 +176,11 @@ int rpf_finish(rpf_engine* e, int64_t* repeats_done);
 /* Datastore::pwr (datastore.h:53) -- raw accumulated |X|^2 per bin, bin N/2 =
  * DC; the DC interpolation of acquisition.cxx:377 is the caller's.  */
 int rpf_get_power(const rpf_engine* e, double* out /* N */);
+/* 1 if the engine was created with RPF_FLAG_BIN_STATS. */
+int rpf_has_bin_stats(const rpf_engine* e);
+/* S2 and PK of the last acquisition (RPF_FLAG_BIN_STATS), valid after rpf_finish like rpf_get_power; either pointer
+ * may be NULL.  RPF_ERR_INVALID_ARGUMENT on an engine without the flag.  Bin N/2 = DC, no interpolation. */
+int rpf_get_bin_stats(const rpf_engine* e, double* sum_sq /* N or NULL */, double* peak /* N or NULL */);
 /* Datastore::repeats_done (datastore.h:38). */
 int64_t rpf_get_repeats_done(const rpf_engine* e);
 /* Datastore::queue_histogram (datastore.h:47), cumulative over the engine's
@@ -189,6 +215,13 @@ int rpf_stream_unregister(rpf_engine* e, const void* stream);
  * full-size parity tests; does not touch the buffer queues. */
 int rpf_accumulate_device(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
                           double* d_pwr_out, void* hip_stream, int64_t* repeats_done);
+
+/* rpf_accumulate_device with the statistics (RPF_FLAG_BIN_STATS engines; else RPF_ERR_INVALID_ARGUMENT): d_out[3 x N]
+ * = S1, S2, PK over the same frames, overwritten (zeros for a stream without a whole frame).  Same stream, alignment
+ * and no-synchronise rules; K1 and ONE reduce launch for the three planes.  d_out[0 .. N) is bit for bit what
+ * rpf_accumulate_device of the same engine writes. */
+int rpf_accumulate_device_stats(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
+                                double* d_out /* 3 x N: S1, S2, PK */, void* hip_stream, int64_t* repeats_done);
 
 /* The two halves of rpf_accumulate_device as separate enqueues, so that a
  * benchmark can bracket the dominant kernel alone with events on `hip_stream`:

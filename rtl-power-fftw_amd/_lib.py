@@ -53,6 +53,7 @@ FLAG_FOURSTEP_FUSED = 2
 FLAG_NO_MIXED_RADIX = 4
 FLAG_NO_FOURSTEP_FUSED = 8
 FLAG_CATCH_ALL = 16
+FLAG_BIN_STATS = 32
 
 # sample formats (RPF_FORMAT_*), carried in bits 16..19 of rpf_config.flags
 FORMAT_CU8 = 0
@@ -87,6 +88,10 @@ _SYMBOLS = [
                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_accumulate_device", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P, _P,
                                              ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_has_bin_stats", ctypes.c_int, [_P]),
+    ("rpf_get_bin_stats", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    ("rpf_accumulate_device_stats", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P, _P,
+                                                   ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_device_fused", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P,
                                         ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_device_reduce", ctypes.c_int, [_P, _P, _P]),

@@ -445,6 +445,26 @@ RPF_HD void phase_accumulate(const cf* x, double* acc, int P)
     }
 }
 
+// Per-bin statistics (RPF_FLAG_BIN_STATS) beside the power: with p = re^2 + im^2 of this frame, correctly rounded
+// (re^2 is exact in double, so one fma rounds once), s2 += p^2 and pk = max(pk, p).  acc takes exactly the
+// instruction sequence of phase_accumulate, so S1 of a stats run is S1 of a plain one.
+RPF_HD void phase_accumulate_stats(const cf* x, double* acc, double* s2, double* pk, int P)
+{
+#pragma unroll
+    for (int a = 0; a < P; ++a) {
+        const double re = static_cast<double>(x[a].x);
+        const double im = static_cast<double>(x[a].y);
+        acc[a] = __builtin_fma(im, im, __builtin_fma(re, re, acc[a]));
+        const double p = __builtin_fma(im, im, re * re);
+        s2[a] = __builtin_fma(p, p, s2[a]);
+        pk[a] = __builtin_fmax(pk[a], p);
+    }
+}
+// How two partial results of statistics plane `plane` (0 S1, 1 S2, 2 PK) combine: frame slots of a workgroup,
+// workgroups, batches, launches.
+constexpr int kStatsPlanes = 3;
+RPF_HD double stats_combine(int plane, double a, double b) { return plane == 2 ? __builtin_fmax(a, b) : a + b; }
+
 // Index into the master twiddle table W_N^k (k in [0,N)) of the pass-J twiddle
 // W_{L_{J-1}}^{m r}:  k = m * r * P^(J-1).
 template <class G, int J>

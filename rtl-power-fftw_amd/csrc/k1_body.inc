@@ -2,7 +2,9 @@
 // 2N f) and fft_accum_strided_kernel (frame f at byte f * pitch, overlapped frames).  The includer declares
 // `constexpr bool STRIDED` and, when it is true, has the kernel argument `long pitch`.  An include rather than a
 // force-inlined device function: the plain kernels then compile to the instruction stream they had before the
-// strided form existed (an inlined body changed their schedules).
+// strided form existed (an inlined body changed their schedules).  `STATS` (a template argument of both, false
+// everywhere but in rpf_kernels_stats*.hip) adds the per-bin statistics; with it false nothing below changes what the
+// plain kernels compile to (tools/kernel_streams.py compares the instruction streams of two builds).
     RPF_SEAM_MARK(0);                            // (timing builds only)
     constexpr int P = G::P, T = G::T, N = G::N, NPASS = G::NPASS;
     constexpr int FPW = WG / T;
@@ -62,6 +64,14 @@
     cf acc32p[ACCP ? P : 1];
 #pragma unroll
     for (int a = 0; a < P; ++a) acc[a] = 0.0;
+    // STATS: the sum of the squared powers and the peak power of every bin beside acc (fft_core.h,
+    // phase_accumulate_stats); the peak starts from 0, which no power is below.
+    static_assert(!STATS || (ACCB == 0 && !PF32 && ABL == 0), "the tuning paths do not combine with the statistics");
+    double acc_s2[STATS ? P : 1], acc_pk[STATS ? P : 1];
+    if constexpr (STATS) {
+#pragma unroll
+        for (int a = 0; a < P; ++a) acc_s2[a] = acc_pk[a] = 0.0;
+    }
     if constexpr (ACCP) {
 #pragma unroll
         for (int a = 0; a < P; ++a) acc32p[a] = cf{0.0f, 0.0f};
@@ -143,6 +153,8 @@
         } else if constexpr (ABL & 1) {
 #pragma unroll
             for (int a = 0; a < P; ++a) asm volatile("" ::"v"(x[a]));
+        } else if constexpr (STATS) {
+            if (active) phase_accumulate_stats(x, acc, acc_s2, acc_pk, P);     // (an inactive slot leaves the peak alone)
         } else {
             if (active) phase_accumulate(x, acc, P);
         }
@@ -167,31 +179,57 @@
     double* const stage = reinterpret_cast<double*>(smem);          // [FPW][N + N/16]
     constexpr int SN = N + N / 16;
     static_assert(sizeof(double) * SN <= sizeof(cf) * G::LDS_CPX + 2 * N, "stage fits the LDS");
+    if constexpr (STATS) {
+        // Three planes per workgroup, partial[(3 w + plane) N ..): S1, S2, PK, one after the other through the same
+        // staging area; the frame slots combine by +, +, max (stats_combine), plane 0 exactly as the plain flush.
 #pragma unroll
-    for (int a = 0; a < P; ++a) {
-        const int bin = bin_of<G>(t, a);
-        stage[fs * SN + bin + (bin >> 4)] = acc[a];
-    }
-    exchange_sync<true>();
-    if constexpr (PF32) {
-        for (int bin = tid; bin < N; bin += WG) {
-            double v = 0.0;
+        for (int plane = 0; plane < kStatsPlanes; ++plane) {
+            if (plane > 0) exchange_sync<true>();         // every wave has read the previous plane
+            const double* const src = plane == 0 ? acc : plane == 1 ? acc_s2 : acc_pk;
 #pragma unroll
-            for (int k = 0; k < FPW; ++k) v += stage[k * SN + bin + (bin >> 4)];
-            reinterpret_cast<float*>(partial)[static_cast<size_t>(blockIdx.x) * N + bin] = static_cast<float>(v);
+            for (int a = 0; a < P; ++a) {
+                const int bin = bin_of<G>(t, a);
+                stage[fs * SN + bin + (bin >> 4)] = src[a];
+            }
+            exchange_sync<true>();
+            double* const out = partial + (static_cast<size_t>(blockIdx.x) * kStatsPlanes + plane) * N;
+            for (int bin = 2 * tid; bin < N; bin += 2 * WG) {
+                partial2_t v = {0.0, 0.0};
+#pragma unroll
+                for (int k = 0; k < FPW; ++k) {
+                    v.x = stats_combine(plane, v.x, stage[k * SN + bin + (bin >> 4)]);
+                    v.y = stats_combine(plane, v.y, stage[k * SN + bin + 1 + (bin >> 4)]);
+                }
+                store_partial2(out + bin, v);
+            }
         }
     } else {
-        // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
-        // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
-        // Written through (store_partial2): 32 KB per workgroup that K3 reads from another XCD.
-        for (int bin = 2 * tid; bin < N; bin += 2 * WG) {
-            partial2_t v = {0.0, 0.0};
 #pragma unroll
-            for (int k = 0; k < FPW; ++k) {
-                v.x += stage[k * SN + bin + (bin >> 4)];
-                v.y += stage[k * SN + bin + 1 + (bin >> 4)];
+        for (int a = 0; a < P; ++a) {
+            const int bin = bin_of<G>(t, a);
+            stage[fs * SN + bin + (bin >> 4)] = acc[a];
+        }
+        exchange_sync<true>();
+        if constexpr (PF32) {
+            for (int bin = tid; bin < N; bin += WG) {
+                double v = 0.0;
+#pragma unroll
+                for (int k = 0; k < FPW; ++k) v += stage[k * SN + bin + (bin >> 4)];
+                reinterpret_cast<float*>(partial)[static_cast<size_t>(blockIdx.x) * N + bin] = static_cast<float>(v);
             }
-            store_partial2(partial + static_cast<size_t>(blockIdx.x) * N + bin, v);
+        } else {
+            // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
+            // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
+            // Written through (store_partial2): 32 KB per workgroup that K3 reads from another XCD.
+            for (int bin = 2 * tid; bin < N; bin += 2 * WG) {
+                partial2_t v = {0.0, 0.0};
+#pragma unroll
+                for (int k = 0; k < FPW; ++k) {
+                    v.x += stage[k * SN + bin + (bin >> 4)];
+                    v.y += stage[k * SN + bin + 1 + (bin >> 4)];
+                }
+                store_partial2(partial + static_cast<size_t>(blockIdx.x) * N + bin, v);
+            }
         }
     }
     RPF_SEAM_DRAIN();

@@ -72,8 +72,10 @@ __device__ __forceinline__ void stage_raw_pitched(const uint8_t* __restrict__ st
 // the stream.  (The scan kernel below walks several acquisitions per launch; for a single one
 // this plain form measured 1.2 us per launch faster on the same box -- A/B in
 // profiles/r03_k1_fixed_cost.txt -- so rpf_accumulate / rpf_accumulate_device keep it.)
+// STATS (RPF_FLAG_BIN_STATS, instantiated in rpf_kernels_stats*.hip only): two more double accumulators per bin, the
+// sum of the squared powers and the largest power, and three partial planes per workgroup (k1_body.inc).
 template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
-          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8>
+          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8, bool STATS = false>
 __global__ __launch_bounds__(WG, OCC) void fft_accum_kernel(const uint8_t* __restrict__ stream,
                                                             long nframes,
                                                             const cf* __restrict__ twN,
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_kernel(const uint8_t* __res
 // same workgroup a few iterations apart and the shared bytes come back from L2.  A separate instantiation: the
 // plain kernel keeps its compile-time 2N.
 template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
-          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8>
+          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8, bool STATS = false>
 __global__ __launch_bounds__(WG, OCC) void fft_accum_strided_kernel(const uint8_t* __restrict__ stream,
                                                                     long nframes, long pitch,
                                                                     const cf* __restrict__ twN,
@@ -405,6 +407,10 @@ struct Variant {
 
 // The instantiations for the signed sample formats (rpf_kernels_formats.hip): variant 0 of every K1 size, or null.
 const Variant* find_format_variant(int N, int fmt);
+// The instantiations with per-bin statistics (rpf_kernels_stats.hip: cu8; rpf_kernels_stats_formats.hip: cs8, cs16):
+// variant 0 of every K1 size, the single-acquisition and strided kernels only (scan entries null), or null.
+const Variant* find_stats_variant(int N, int fmt);
+const Variant* find_stats_format_variant(int N, int fmt);
 
 namespace {
 

@@ -80,6 +80,7 @@ struct rpf_engine {
     uint32_t flags = 0;
     bool use_dma = true;
     int variant = 0;
+    bool stats = false;           // RPF_FLAG_BIN_STATS: S2 and PK kept beside the power on every path
 
     // Datastore public state
     int64_t repeats = 0;        // params.repeats of the running acquisition
@@ -91,6 +92,7 @@ struct rpf_engine {
     std::condition_variable status_change;      // :46
     std::vector<int> queue_histogram;           // :47
     std::vector<double> pwr;                    // :53
+    std::vector<double> sum_sq, peak;           // stats engines: S2[N], PK[N] of the last acquisition
 
     std::vector<HostBuffer> pool;
     uint8_t* pool_base = nullptr;        // the pool as ONE pinned allocation: neighbouring buffers can travel in one copy
@@ -141,7 +143,7 @@ struct rpf_engine {
     int64_t gather_frames = 0;            // ... frames it holds (kGatherBytes / 2N, at least one)
     float* d_window = nullptr;
     double* d_partial = nullptr;
-    double* d_pwr = nullptr;
+    double* d_pwr = nullptr;              // N doubles; a stats engine's: 3 N, the planes S1 (= pwr), S2, PK
     size_t head_room = 0;                 // >= 2N, multiple of 256
     size_t coalesce = 1;                  // host buffers one staging slot holds (= one transform launch)
     std::vector<StagingSlot> staging;
@@ -253,11 +255,12 @@ int launch_fused_hops(rpf_engine* e, const uint8_t* const* d_frames, const int64
         const long pitch = static_cast<long>(e->sample_bytes) * e->step;
         const bool dma1 = e->use_dma && (reinterpret_cast<uintptr_t>(d_frames[0]) % 16) == 0 && pitch % 16 == 0;
         HIP_TRY(e, rpf::launch_fft_accum(e->N, e->variant, e->has_window, dma1, d_frames[0], nframes[0], e->d_twiddles,
-                                         e->d_window, e->d_partial, grid, stream, &e->last, pitch, e->format));
+                                         e->d_window, e->d_partial, grid, stream, &e->last, pitch, e->format, e->stats));
         for (int h = 1; h <= rpf::kMaxHops; ++h) slots->begin[h] = grid;
         *nslots = grid;
         return RPF_OK;
     }
+    if (e->stats) return fail(e, RPF_ERR_INVALID_ARGUMENT, "the one-launch scan does not keep per-bin statistics");
     rpf::HopArgs args;
     bool interleave_single = false;
 #ifdef RPF_TUNING
@@ -370,7 +373,7 @@ int launch_transform(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hi
     if (e->generic) {
         HIP_TRY(e, rpf::launch_generic(e->N, d_frames, nframes, e->d_window, e->d_chirp, e->d_bhat, e->d_tw_sub,
                                        e->d_tw_sub2, e->gen_h, e->d_scratch, e->d_partial, /*accumulate=*/false, stream,
-                                       e->format));
+                                       e->format, e->stats));
         e->last = e->plan;
         *nslots = 1;
         return RPF_OK;
@@ -407,13 +410,13 @@ int launch_transform(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hi
 }
 
 int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out, bool accumulate,
-                        hipStream_t stream, unsigned* slot_verdict);
+                        hipStream_t stream, unsigned* slot_verdict, bool want_stats);
 
 // Overlapped frames on a family that reads frames side by side: chunks of at most kGatherBytes of frames are gathered
 // into e->d_gather (rpf_frames.hip) and the size's unchanged transform + reduce runs over each, the chunks after the
 // first adding into d_out.  (Four-step sizes are on the two-kernel path here: rpf_engine_create.)
 int launch_gathered(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out, bool accumulate,
-                    hipStream_t stream)
+                    hipStream_t stream, bool want_stats)
 {
     const size_t frame = e->sample_bytes * static_cast<size_t>(e->N);
     if (!e->d_gather) {
@@ -426,7 +429,7 @@ int launch_gathered(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, dou
     for (int64_t f0 = 0; f0 < nframes; f0 += e->gather_frames) {
         const int64_t n = std::min(e->gather_frames, nframes - f0);
         HIP_TRY(e, rpf::launch_gather_frames(d_frames + f0 * pitch, n, pitch, static_cast<long>(frame), e->d_gather, stream));
-        const int rc = launch_side_by_side(e, e->d_gather, n, d_out, accumulate || f0 > 0, stream, nullptr);
+        const int rc = launch_side_by_side(e, e->d_gather, n, d_out, accumulate || f0 > 0, stream, nullptr, want_stats);
         if (rc != RPF_OK) return rc;
     }
     return RPF_OK;
@@ -436,17 +439,19 @@ int launch_gathered(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, dou
 // slot_verdict: the queue path's pinned word for this launch -- if a fused launch gives up, K3 leaves d_out as it
 // is, the word becomes 1 and the worker re-runs the bytes on K2a/K2b (recover_fused); null (the device-resident
 // entries): d_out is NaN-filled and the launch counted in h_fused_words[3].
+// want_stats (stats engines only): d_out is three planes of N, S1, S2, PK, combined with what it holds by +, +, max
+// when `accumulate`; without it a stats engine's launch leaves S1 alone in d_out[N] (the same kernels, K3 over plane 0).
 int launch_frames(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out,
-                  bool accumulate, hipStream_t stream, unsigned* slot_verdict = nullptr)
+                  bool accumulate, hipStream_t stream, unsigned* slot_verdict = nullptr, bool want_stats = false)
 {
     if (nframes <= 0) return RPF_OK;
-    if (overlapped(e) && !is_k1(e)) return launch_gathered(e, d_frames, nframes, d_out, accumulate, stream);
-    return launch_side_by_side(e, d_frames, nframes, d_out, accumulate, stream, slot_verdict);
+    if (overlapped(e) && !is_k1(e)) return launch_gathered(e, d_frames, nframes, d_out, accumulate, stream, want_stats);
+    return launch_side_by_side(e, d_frames, nframes, d_out, accumulate, stream, slot_verdict, want_stats);
 }
 
 // launch_frames for frames the transform reads where they lie (K1 at any frame step; the other families at step N)
 int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out, bool accumulate,
-                        hipStream_t stream, unsigned* slot_verdict)
+                        hipStream_t stream, unsigned* slot_verdict, bool want_stats)
 {
     if (e->fused && !slot_verdict) note_device_path_aborts(e);
     int nslots = 0;
@@ -455,6 +460,15 @@ int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes,
     e->last_slots = nslots;
     e->last_hops = 0;
     const bool fused = e->last_was_fused;
+    if (e->stats) {
+        // three planes per slot (K1: one slot per workgroup; the catch-all path: one slot)
+        if (want_stats)
+            HIP_TRY(e, rpf::launch_reduce_stats(e->d_partial, nslots, e->N, d_out, accumulate, stream));
+        else
+            HIP_TRY(e, rpf::launch_reduce(e->d_partial, nslots, e->N, d_out, accumulate, stream, false,
+                                          static_cast<size_t>(rpf::kStatsPlanes) * e->N));
+        return RPF_OK;
+    }
     HIP_TRY(e, rpf::launch_reduce(e->d_partial, nslots, e->N, d_out, accumulate, stream,
                                   e->plan.partial_f32, e->bigblu ? static_cast<size_t>(e->blu_M) : 0,
                                   fused && slot_verdict ? rpf::fourstep_fused_abort_word(e->d_fused_ctl) : nullptr));
@@ -624,7 +638,7 @@ void worker_main(rpf_engine* e)
         nframes = std::min<int64_t>(nframes, e->repeats - frames_issued);    // datastore.cxx:67
         if (ok() && nframes > 0) {
             if (cur->verdict) *cur->verdict = 0;
-            int rc = launch_frames(e, dst - carry, nframes, e->d_pwr, /*accumulate=*/true, e->compute_stream, cur->verdict);
+            int rc = launch_frames(e, dst - carry, nframes, e->d_pwr, /*accumulate=*/true, e->compute_stream, cur->verdict, e->stats);
             if (rc != RPF_OK) {
                 e->worker_rc = rc;
                 e->worker_error = e->last_error;
@@ -747,6 +761,11 @@ void worker_main(rpf_engine* e)
         s.launched_fused = false;
     }
     WORKER_TRY(hipMemcpy(e->pwr.data(), e->d_pwr, sizeof(double) * e->N, hipMemcpyDeviceToHost), "hipMemcpy(pwr)");
+    if (e->stats) {
+        WORKER_TRY(hipMemcpy(e->sum_sq.data(), e->d_pwr + e->N, sizeof(double) * e->N, hipMemcpyDeviceToHost), "hipMemcpy(sum_sq)");
+        WORKER_TRY(hipMemcpy(e->peak.data(), e->d_pwr + 2 * static_cast<size_t>(e->N), sizeof(double) * e->N, hipMemcpyDeviceToHost),
+                   "hipMemcpy(peak)");
+    }
     e->repeats_done = frames_issued;
 #undef WORKER_TRY
 }
@@ -819,10 +838,18 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
         return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
                     "Sample format must be 0 (cu8), 1 (cs8) or 2 (cs16); got " + std::to_string(format) + ".");
     const size_t sample_bytes = format == RPF_FORMAT_CS16 ? 4 : 2;
+    const bool stats = (cfg->flags & RPF_FLAG_BIN_STATS) != 0;
+    if (stats && (cfg->flags & RPF_FLAG_FOURSTEP_FUSED))
+        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
+                    "RPF_FLAG_BIN_STATS does not combine with RPF_FLAG_FOURSTEP_FUSED: the statistics run on K1 or on the catch-all path.");
+    if (stats && ((cfg->flags >> 8) & 0xffu) != 0)
+        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
+                    "RPF_FLAG_BIN_STATS does not combine with a kernel variant other than 0.");
     const bool native_k1 = rpf::kernel_supported(cfg->N, 0);
     // The catch-all path is the one that reads every format at every N: it takes the engines that ask for it and the
     // signed formats on every size K1 does not serve, whatever family that size runs on with cu8.
-    const bool catch_all = (cfg->flags & RPF_FLAG_CATCH_ALL) != 0 || (format != RPF_FORMAT_CU8 && !native_k1);
+    // ... and so do the statistics: a stats engine at any size K1 does not serve runs there.
+    const bool catch_all = (cfg->flags & RPF_FLAG_CATCH_ALL) != 0 || ((format != RPF_FORMAT_CU8 || stats) && !native_k1);
     const int variant = static_cast<int>((cfg->flags >> 8) & 0xffu);
     // (asking for the fused four-step kernel is asking for the four-step path)
     // 32768 is served twice, by the split form 2 x 16384 and by the four-step kernels.  Plain runs are faster on the
@@ -872,6 +899,11 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
     e->flags = cfg->flags;
     e->use_dma = !(cfg->flags & RPF_FLAG_NO_LDS_DMA);
     e->variant = variant;
+    e->stats = stats;
+    if (stats) {
+        e->sum_sq.assign(e->N, 0.0);
+        e->peak.assign(e->N, 0.0);
+    }
     e->fourstep = fourstep;
     e->mixed = mixed;
     e->bluestein = bluestein;
@@ -938,7 +970,7 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
         e->plan.block = 256;
         e->plan.fpw = rpf::generic_batch(e->N);
         e->plan.lds_bytes = 0;
-        partial_slots = 1;
+        partial_slots = e->stats ? rpf::kStatsPlanes : 1;
     } else if (e->mixed) {
         CREATE_TRY(rpf::plan_mixed(e->N, e->variant, e->has_window, e->device, &e->plan));
         partial_slots = e->plan.grid;
@@ -1015,15 +1047,17 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
         if (e->has_window)
             CREATE_TRY(hipMemcpy(e->d_window, window_t.data(), sizeof(float) * window_t.size(), hipMemcpyHostToDevice));
     } else {
-        CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, true, e->device, &e->plan, e->format));
+        CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, true, e->device, &e->plan, e->format, e->stats));
         rpf::LaunchInfo tmp;
-        CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, false, e->device, &tmp, e->format));
+        CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, false, e->device, &tmp, e->format, e->stats));
         e->plan.grid = std::min(e->plan.grid, tmp.grid);
         partial_slots = e->plan.grid + rpf::kMaxHops;    // a workgroup leaves one partial per hop it touches
+        if (e->stats) partial_slots = static_cast<size_t>(e->plan.grid) * rpf::kStatsPlanes;   // three planes per workgroup, no scans
     }
     CREATE_TRY(hipMalloc(&e->d_partial, sizeof(double) * partial_len * partial_slots));
-    CREATE_TRY(hipMalloc(&e->d_pwr, sizeof(double) * e->N));
-    CREATE_TRY(hipMemset(e->d_pwr, 0, sizeof(double) * e->N));
+    const size_t pwr_planes = e->stats ? rpf::kStatsPlanes : 1;
+    CREATE_TRY(hipMalloc(&e->d_pwr, sizeof(double) * e->N * pwr_planes));
+    CREATE_TRY(hipMemset(e->d_pwr, 0, sizeof(double) * e->N * pwr_planes));
     if (e->fused) {
         // Prove once that the eight teams assemble on this device (one round per team on a dummy
         // stream); if they do not, this engine uses the two-kernel path.
@@ -1121,7 +1155,11 @@ int rpf_begin(rpf_engine* e, int64_t repeats)
     HIP_TRY(e, on_device.status());
     // acquisition.cxx:252-254
     std::fill(e->pwr.begin(), e->pwr.end(), 0.0);
-    HIP_TRY(e, hipMemsetAsync(e->d_pwr, 0, sizeof(double) * e->N, e->compute_stream));
+    if (e->stats) {
+        std::fill(e->sum_sq.begin(), e->sum_sq.end(), 0.0);
+        std::fill(e->peak.begin(), e->peak.end(), 0.0);
+    }
+    HIP_TRY(e, hipMemsetAsync(e->d_pwr, 0, sizeof(double) * e->N * (e->stats ? rpf::kStatsPlanes : 1), e->compute_stream));
     {
         std::lock_guard<std::mutex> lock(e->status_mutex);
         e->acquisition_finished = false;
@@ -1217,6 +1255,20 @@ int rpf_get_power(const rpf_engine* e, double* out)
         return fail(const_cast<rpf_engine*>(e), RPF_ERR_INVALID_ARGUMENT,
                     "rpf_get_power: acquisition still running (call rpf_finish first)");
     std::memcpy(out, e->pwr.data(), sizeof(double) * e->N);
+    return RPF_OK;
+}
+
+int rpf_has_bin_stats(const rpf_engine* e) { return e && e->stats ? 1 : 0; }
+
+int rpf_get_bin_stats(const rpf_engine* e, double* sum_sq, double* peak)
+{
+    if (!e) return RPF_ERR_INVALID_ARGUMENT;
+    rpf_engine* me = const_cast<rpf_engine*>(e);
+    if (!e->stats) return fail(me, RPF_ERR_INVALID_ARGUMENT, "rpf_get_bin_stats: the engine was created without RPF_FLAG_BIN_STATS");
+    if (e->worker_running)
+        return fail(me, RPF_ERR_INVALID_ARGUMENT, "rpf_get_bin_stats: acquisition still running (call rpf_finish first)");
+    if (sum_sq) std::memcpy(sum_sq, e->sum_sq.data(), sizeof(double) * e->N);
+    if (peak) std::memcpy(peak, e->peak.data(), sizeof(double) * e->N);
     return RPF_OK;
 }
 
@@ -1360,10 +1412,40 @@ int rpf_accumulate_device(rpf_engine* e, const void* d_stream, size_t nbytes, in
                          /*accumulate=*/false, s);
 }
 
+int rpf_accumulate_device_stats(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
+                                double* d_out, void* hip_stream, int64_t* repeats_done)
+{
+    if (!e || !d_out || (!d_stream && nbytes))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: NULL argument");
+    if (!e->stats)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: the engine was created without RPF_FLAG_BIN_STATS");
+    if (e->worker_running)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: acquisition running");
+    if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
+    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: d_out must be 16-byte aligned");
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    int64_t nframes = frames_in(e, nbytes);
+    nframes = std::min(nframes, repeats);
+    if (repeats_done) *repeats_done = nframes;
+    if (nframes == 0) {
+        HIP_TRY(e, hipMemsetAsync(d_out, 0, sizeof(double) * e->N * rpf::kStatsPlanes, s));
+        return RPF_OK;
+    }
+    return launch_frames(e, static_cast<const uint8_t*>(d_stream), nframes, d_out, /*accumulate=*/false, s, nullptr,
+                         /*want_stats=*/true);
+}
+
 int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
                      void* hip_stream, int64_t* repeats_done)
 {
     if (!e || !d_stream) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: NULL argument");
+    if (e->stats)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: not on an engine with RPF_FLAG_BIN_STATS (use rpf_accumulate_device_stats)");
     if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: acquisition running");
     if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
@@ -1392,6 +1474,8 @@ int rpf_device_reduce(rpf_engine* e, double* d_pwr_out, void* hip_stream)
     if (!e || !d_pwr_out) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: NULL argument");
     if (reinterpret_cast<uintptr_t>(d_pwr_out) & 15)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: d_pwr_out must be 16-byte aligned");
+    if (e->stats)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: not on an engine with RPF_FLAG_BIN_STATS (use rpf_accumulate_device_stats)");
     if (e->last_slots < 1 && e->last_hops < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: nothing to reduce");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
@@ -1453,8 +1537,9 @@ int rpf_accumulate_device_hops(rpf_engine* e, const void* const* d_streams, cons
     if (repeats_done)
         for (int h = 0; h < n_hops; ++h) repeats_done[h] = frames[h];
     const size_t N = static_cast<size_t>(e->N);
-    if (!is_k1(e) || overlapped(e)) {
-        // the other kernel families -- and overlapped frames (the scan kernel reads frames side by side) -- run one
+    if (!is_k1(e) || overlapped(e) || e->stats) {
+        // the other kernel families -- and overlapped frames (the scan kernel reads frames side by side), and stats
+        // engines (the scan kernel keeps no statistics; what comes back here is the power alone) -- run one
         // acquisition per launch set
         for (int h = 0; h < n_hops; ++h) {
             if (frames[h] == 0) {
@@ -1492,6 +1577,8 @@ int rpf_device_fused_hops(rpf_engine* e, const void* const* d_streams, const siz
     std::vector<int64_t> frames;
     int rc = check_hops(e, "rpf_device_fused_hops", d_streams, nbytes, repeats, n_hops, &frames);
     if (rc != RPF_OK) return rc;
+    if (e->stats)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused_hops: not on an engine with RPF_FLAG_BIN_STATS");
     if (!is_k1(e) || n_hops > rpf::kMaxHops || overlapped(e))
         return fail(e, RPF_ERR_INVALID_ARGUMENT,
                     "rpf_device_fused_hops: needs a size the LDS-resident kernel serves, frames side by side (frame step N) "

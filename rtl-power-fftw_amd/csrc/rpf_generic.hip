@@ -140,6 +140,26 @@ __global__ __launch_bounds__(kThreads) void gen_accum_kernel(const cf* __restric
     pwr[k] = s;
 }
 
+// The same with the per-bin statistics (RPF_FLAG_BIN_STATS): out[0][k] as above, instruction for instruction,
+// out[1][k] (+)= sum_f p^2 and out[2][k] = max(out[2][k], max_f p) with p = |X[f][k]|^2 rounded once (fft_core.h,
+// phase_accumulate_stats).  One writer per bin.
+__global__ __launch_bounds__(kThreads) void gen_accum_stats_kernel(const cf* __restrict__ X, int N, int M, int frames,
+                                                                  double* __restrict__ out, int accumulate)
+{
+    const int k = blockIdx.x * kThreads + threadIdx.x;
+    if (k >= N) return;
+    double s = accumulate ? out[k] : 0.0;
+    double s2 = accumulate ? out[N + k] : 0.0;
+    double pk = accumulate ? out[2 * static_cast<size_t>(N) + k] : 0.0;
+    for (int f = 0; f < frames; ++f) {
+        const cf v = X[static_cast<size_t>(f) * M + k];
+        phase_accumulate_stats(&v, &s, &s2, &pk, 1);
+    }
+    out[k] = s;
+    out[N + k] = s2;
+    out[2 * static_cast<size_t>(N) + k] = pk;
+}
+
 int ilog2i(long v)
 {
     int l = 0;
@@ -221,11 +241,11 @@ static cf* run_fft(cf* d_a, cf* d_b, long M, int frames, const cf* d_t0, const c
 }
 
 // Frames [0, nframes) of d_stream (frame f = bytes [bN f, bN (f+1)), b = bytes per sample of `fmt`) -> d_pwr[N]
-// (overwritten unless accumulate).  d_window: N floats or null (power-of-two N);
+// (overwritten unless accumulate; three planes of N with `stats`: rpf_kernels.h).  d_window: N floats or null (power-of-two N);
 // d_g / d_bhat: bluestein_tables.h's tables (other N).  d_scratch: generic_scratch_bytes(N).
 hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const float* d_window, const cf* d_g,
                           const cf* d_bhat, const cf* d_t0, const cf* d_t1, int h, cf* d_scratch, double* d_pwr,
-                          bool accumulate, hipStream_t stream, int fmt)
+                          bool accumulate, hipStream_t stream, int fmt, bool stats)
 {
     if (!generic_supported(N) || nframes < 1 || fmt < kFmtCu8 || fmt > kFmtCs16) return hipErrorInvalidValue;
     const long M = generic_length(N);
@@ -252,8 +272,8 @@ hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const fl
             cf* other = (res == d_a) ? d_b : d_a;
             res = run_fft(res, other, M, nb, d_t0, d_t1, h, stream);
         }
-        hipLaunchKernelGGL(gen_accum_kernel, dim3((N + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, res, N,
-                           static_cast<int>(M), nb, d_pwr, acc ? 1 : 0);
+        hipLaunchKernelGGL(stats ? gen_accum_stats_kernel : gen_accum_kernel, dim3((N + kThreads - 1) / kThreads),
+                           dim3(kThreads), 0, stream, res, N, static_cast<int>(M), nb, d_pwr, acc ? 1 : 0);
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
         acc = true;

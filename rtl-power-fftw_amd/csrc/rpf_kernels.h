@@ -28,7 +28,9 @@ bool kernel_supported(int N, int vid = 0);
 // workgroups that are simultaneously resident (occupancy x CU count).
 // fmt: the sample format (fft_core.h kFmt*); the signed formats have variant 0 only and may come out with another
 // grid than cu8 (cs16 stages twice the bytes in LDS) -- li says what was chosen.
-hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, LaunchInfo* li, int fmt = kFmtCu8);
+// stats: the kernels with per-bin statistics (RPF_FLAG_BIN_STATS; variant 0 only), which may run at a lower occupancy.
+hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, LaunchInfo* li, int fmt = kFmtCu8,
+                       bool stats = false);
 
 // Fused unpack + FFT + |X|^2 accumulate over frames [0, nframes) of d_stream
 // (frame f = bytes [pitch f, pitch f + bN); pitch 0 = bN; b = 2, or 4 for 16-bit samples: `fmt`; written for b = 2 below).  Writes one partial spectrum of N doubles
@@ -38,7 +40,15 @@ hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, La
 hipError_t launch_fft_accum(int N, int vid, bool window, bool use_dma, const uint8_t* d_stream,
                             long nframes, const cf* d_twiddles, const float* d_window,
                             double* d_partial, int grid, hipStream_t stream, LaunchInfo* li, long pitch = 0,
-                            int fmt = kFmtCu8);
+                            int fmt = kFmtCu8, bool stats = false);
+// stats: workgroup w writes THREE planes of N doubles, d_partial[(3 w + plane) N ..): plane 0 the power sum S1 (the
+// plain kernel's, instruction for instruction), plane 1 S2 = sum of the squared frame powers, plane 2 PK = the largest
+// frame power.  d_partial then holds 3 x grid x N doubles.
+// K3 for the statistics: d_out[plane * N + bin] for the three planes in ONE launch -- planes 0 and 1 summed over the
+// slots exactly as launch_reduce sums them (same order, bit for bit), plane 2 their maximum; accumulate: combined with
+// what d_out holds (+, +, max) instead of overwriting it.  Slot s, plane p lies at d_partial[(3 s + p) N ..).
+hipError_t launch_reduce_stats(const double* d_partial, int nslots, int N, double* d_out, bool accumulate,
+                               hipStream_t stream);
 // The same over the hops of `hops` (hop_partition.h: frame f of hop h = bytes [2N f, 2N (f+1)) of
 // hops.stream[h]) in ONE launch.  Workgroup w writes one partial spectrum of N doubles per hop it
 // touches, at slot hops.slot_bias[h] + w of d_partial.  `grid` is what partition_hops returned
@@ -141,7 +151,9 @@ void generic_twiddle_tables(int N, std::vector<cf>& t0, std::vector<cf>& t1, int
 // d_g (N) / d_bhat (M): bluestein_tables.h's tables (other N).
 hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const float* d_window, const cf* d_g,
                           const cf* d_bhat, const cf* d_t0, const cf* d_t1, int h, cf* d_scratch, double* d_pwr,
-                          bool accumulate, hipStream_t stream, int fmt = kFmtCu8);
+                          bool accumulate, hipStream_t stream, int fmt = kFmtCu8, bool stats = false);
+// stats: d_pwr is three planes, d_pwr[plane * N + bin] = S1, S2, PK (launch_fft_accum), combined over the batches --
+// and with what d_pwr holds when `accumulate` -- by +, +, max.
 
 // ---- overlapped frames on the other kernel families (rpf_frames.hip) --------------------------------
 // d_dst[f * frame_bytes .. (f+1) * frame_bytes) = d_src[f * pitch .. f * pitch + frame_bytes) for f < nframes:

@@ -470,8 +470,9 @@ const Variant kVariants[] = {
 #endif  // RPF_TUNING
 };
 
-const Variant* find_variant(int N, int vid, int fmt = kFmtCu8)
+const Variant* find_variant(int N, int vid, int fmt = kFmtCu8, bool stats = false)
 {
+    if (stats) return vid == 0 ? find_stats_variant(N, fmt) : nullptr;
     if (fmt != kFmtCu8) return vid == 0 ? find_format_variant(N, fmt) : nullptr;
     for (const Variant& v : kVariants)
         if (v.N == N && v.vid == vid) return &v;
@@ -538,9 +539,9 @@ extern "C" int rpf_debug_seam_marks(unsigned long long* out, int* nwgs, int rese
 }
 #endif
 
-hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, LaunchInfo* li, int fmt)
+hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, LaunchInfo* li, int fmt, bool stats)
 {
-    const Variant* v = find_variant(N, vid, fmt);
+    const Variant* v = find_variant(N, vid, fmt, stats);
     if (!v) return hipErrorInvalidValue;
     int per_cu = 1 << 30;
     for (int kind = 0; kind < 3; ++kind) {    // the single-acquisition, scan and strided instantiations share one grid
@@ -548,6 +549,7 @@ hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, La
         const void* fn = kind == 2 ? reinterpret_cast<const void*>(v->strided[w][d])
                        : kind == 1 ? reinterpret_cast<const void*>(v->scan[w][d])
                                    : reinterpret_cast<const void*>(v->single[w][d]);
+        if (!fn) continue;                    // (the statistics kernels have no scan form)
         hipError_t err = hipFuncSetAttribute(fn,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, v->lds_bytes);
         if (err != hipSuccess) return err;
@@ -570,9 +572,9 @@ hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, La
 
 hipError_t launch_fft_accum(int N, int vid, bool window, bool use_dma, const uint8_t* d_stream,
                             long nframes, const cf* d_twiddles, const float* d_window,
-                            double* d_partial, int grid, hipStream_t stream, LaunchInfo* li, long pitch, int fmt)
+                            double* d_partial, int grid, hipStream_t stream, LaunchInfo* li, long pitch, int fmt, bool stats)
 {
-    const Variant* v = find_variant(N, vid, fmt);
+    const Variant* v = find_variant(N, vid, fmt, stats);
     const long sb = sample_bytes_of(fmt);
     if (!v || grid < 1 || pitch < 0 || pitch > sb * N || (pitch % sb)) return hipErrorInvalidValue;
     if (pitch == 0 || pitch == sb * N)

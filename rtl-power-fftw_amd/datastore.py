@@ -19,8 +19,10 @@ class Params:
 
     def __init__(self, N=512, buffers=5, buf_length=BASE_BUF * DEFAULT_BUF_MULTIPLIER,
                  repeats=None, window=False, sample_rate=2000000, cfreq=1420405752,
-                 linear=False, baseline=False, frame_step=None, sample_format="cu8"):
+                 linear=False, baseline=False, frame_step=None, sample_format="cu8", bin_stats=False):
         self.N = N
+        # per-bin statistics beside the power (RPF_FLAG_BIN_STATS): Datastore.sum_sq, Datastore.peak
+        self.bin_stats = bool(bin_stats)
         # what one complex sample of the stream is: "cu8" (the reference's), "cs8", "cs16" (RPF_FORMAT_*)
         if sample_format not in _lib.FORMATS:
             raise RPFError("Unknown sample format '%s' (one of: cu8, cs8, cs16)." % (sample_format,),
@@ -84,12 +86,19 @@ class Datastore:
         cfg.buffer_capacity = params.buf_length
         cfg.device = device
         cfg.flags = flags | _lib.FLAG_SAMPLE_FORMAT(_lib.FORMATS[getattr(params, "sample_format", "cu8")])
+        if getattr(params, "bin_stats", False):
+            cfg.flags |= _lib.FLAG_BIN_STATS
         cfg.frame_step = getattr(params, "frame_step", params.N)
         rc = self._lib.rpf_engine_create(ctypes.byref(cfg), ctypes.byref(self._handle))
         if rc != 0:
             self._handle = ctypes.c_void_p()
             raise RPFError(self._lib.rpf_last_global_error().decode(), rc)
         self.pwr = np.zeros(params.N, dtype=np.float64)
+        # stats engines (Params(bin_stats=True) or _lib.FLAG_BIN_STATS): S2 and PK of the last acquisition, else None
+        self.sum_sq = self.peak = None
+        if self.has_bin_stats:
+            self.sum_sq = np.zeros(params.N, dtype=np.float64)
+            self.peak = np.zeros(params.N, dtype=np.float64)
         self.repeats_done = 0
 
     # -- lifetime ---------------------------------------------------------
@@ -144,7 +153,24 @@ class Datastore:
         self.repeats_done = done.value
         self._check(self._lib.rpf_get_power(self._handle,
                                             self.pwr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        self._fetch_bin_stats()
         return self.repeats_done
+
+    @property
+    def has_bin_stats(self):
+        """rpf_has_bin_stats: does the engine keep S2 and PK beside the power?"""
+        return bool(self._lib.rpf_has_bin_stats(self._handle))
+
+    def _fetch_bin_stats(self):
+        if self.sum_sq is not None:
+            dp = ctypes.POINTER(ctypes.c_double)
+            self._check(self._lib.rpf_get_bin_stats(self._handle, self.sum_sq.ctypes.data_as(dp),
+                                                    self.peak.ctypes.data_as(dp)))
+
+    def spectral_kurtosis(self):
+        """SK of the last acquisition (stats.spectral_kurtosis of pwr, sum_sq, repeats_done)."""
+        from . import stats
+        return stats.spectral_kurtosis(self.pwr, self.sum_sq, self.repeats_done)
 
     @property
     def queue_histogram(self):
@@ -167,6 +193,7 @@ class Datastore:
             self.params.repeats if repeats is None else repeats,
             self.pwr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(done)))
         self.repeats_done = done.value
+        self._fetch_bin_stats()
         return self.pwr.copy(), self.repeats_done
 
     def register_stream(self, stream):
@@ -185,6 +212,14 @@ class Datastore:
         self._check(self._lib.rpf_accumulate_device(
             self._handle, ctypes.c_void_p(d_stream_ptr), nbytes, repeats,
             ctypes.c_void_p(d_pwr_ptr), ctypes.c_void_p(hip_stream), ctypes.byref(done)))
+        return done.value
+
+    def accumulate_device_stats(self, d_stream_ptr, nbytes, repeats, d_out_ptr, hip_stream=0):
+        """rpf_accumulate_device_stats: as accumulate_device, d_out = 3 x N device doubles (S1, S2, PK)."""
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_accumulate_device_stats(
+            self._handle, ctypes.c_void_p(d_stream_ptr), nbytes, repeats,
+            ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(hip_stream), ctypes.byref(done)))
         return done.value
 
     def device_fused(self, d_stream_ptr, nbytes, repeats, hip_stream=0):

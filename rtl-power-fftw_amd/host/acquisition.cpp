@@ -127,11 +127,17 @@ void Acquisition::print_summary() const
 
 void write_text_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp)
 {
+    write_text_header(out, start_stamp, end_stamp, false);
+}
+
+void write_text_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, bool stats)
+{
     out << "# rtl-power-fftw output" << std::endl;
     out << "# Acquisition start: " << start_stamp << std::endl;
     out << "# Acquisition end: " << end_stamp << std::endl;
     out << "#" << std::endl;
-    out << "# frequency [Hz] power spectral density [dB/Hz]" << std::endl;
+    out << "# frequency [Hz] power spectral density [dB/Hz]" << (stats ? " peak hold [dB/Hz] spectral kurtosis" : "")
+        << std::endl;
 }
 
 namespace {
@@ -169,6 +175,29 @@ void write_spectrum_text(std::ostream& out, std::vector<double>& pwr, int N, int
     out.flush();
 }
 
+void write_spectrum_text_stats(std::ostream& out, std::vector<double>& pwr, const std::vector<double>& sum_sq,
+                               std::vector<double>& peak, int N, int64_t repeats_done, int64_t tuned_freq,
+                               int samplerate, bool linear, const std::vector<double>* baseline)
+{
+    // the kurtosis of every bin from the sums as accumulated; its DC bin, like the other two columns', is the mean
+    // of its neighbours
+    std::vector<double> sk(N);
+    for (int i = 0; i < N; ++i) sk[i] = spectral_kurtosis(pwr[i], sum_sq[i], repeats_done);
+    interpolate_dc(sk, N);
+    interpolate_dc(pwr, N);
+    interpolate_dc(peak, N);
+    const int freq_digits = static_cast<int>(
+        std::ceil(std::floor(std::log10(static_cast<double>(tuned_freq))) - std::log10(samplerate / N) + 1 + 2));
+    for (int i = 0; i < N; ++i) {
+        const double freq = tuned_freq + (i - N / 2.0) * samplerate / N;
+        out << std::setprecision(freq_digits) << freq << " " << std::setprecision(6)
+            << bin_value(pwr, i, N, repeats_done, samplerate, linear, baseline) << " "
+            << bin_value(peak, i, N, 1, samplerate, linear, baseline) << " " << sk[i] << std::endl;
+    }
+    out << std::endl;
+    out.flush();
+}
+
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,
                          const std::vector<double>* baseline, std::vector<float>& row)
 {
@@ -182,9 +211,13 @@ void Acquisition::write_data(std::ostream& out) const
 {
     const std::vector<double>* baseline = options_.baseline ? &aux_.baseline_values : nullptr;
     if (!options_.matrixMode) {
-        write_text_header(out, start_stamp_, end_stamp_);
-        write_spectrum_text(out, data_.pwr, options_.N, data_.repeats_done, tuned_freq_, actual_samplerate_,
-                            options_.linear, baseline);
+        write_text_header(out, start_stamp_, end_stamp_, options_.bin_stats);
+        if (options_.bin_stats)
+            write_spectrum_text_stats(out, data_.pwr, data_.sum_sq, data_.peak, options_.N, data_.repeats_done, tuned_freq_,
+                                      actual_samplerate_, options_.linear, baseline);
+        else
+            write_spectrum_text(out, data_.pwr, options_.N, data_.repeats_done, tuned_freq_, actual_samplerate_,
+                                options_.linear, baseline);
         return;
     }
     append_matrix_row(options_, meta_, data_.pwr, data_.repeats_done, tuned_freq_, actual_samplerate_, baseline);

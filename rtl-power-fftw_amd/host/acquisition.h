@@ -98,6 +98,15 @@ void write_text_header(std::ostream& out, const std::string& start_stamp, const 
 // Mutates pwr[N/2] (DC interpolation) exactly like the reference.
 void write_spectrum_text(std::ostream& out, std::vector<double>& pwr, int N, int64_t repeats_done,
                          int64_t tuned_freq, int samplerate, bool linear, const std::vector<double>* baseline);
+// The same with the statistics columns of --stats: after the power column the peak hold, PK / N / samplerate (no
+// division by repeats_done) through the power column's linear / dB / baseline handling and precision, and the
+// spectral kurtosis (datastore.h), dimensionless: never dB, no baseline, "nan" where undefined.  The DC bin of both
+// is the mean of its neighbours, as the power's.  Mutates pwr[N/2] and peak[N/2]; sum_sq is left alone.
+void write_spectrum_text_stats(std::ostream& out, std::vector<double>& pwr, const std::vector<double>& sum_sq,
+                               std::vector<double>& peak, int N, int64_t repeats_done, int64_t tuned_freq,
+                               int samplerate, bool linear, const std::vector<double>* baseline);
+// `stats`: the last '#' line names the two columns of --stats too
+void write_text_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, bool stats);
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,
                          const std::vector<double>* baseline, std::vector<float>& row);
 // Matrix mode: append one float32 row to options.bin_file and keep the row/column

@@ -9,6 +9,7 @@
 #ifndef RPF_HOST_DATASTORE_H
 #define RPF_HOST_DATASTORE_H
 
+#include <cmath>
 #include <cstdint>
 #include <iostream>
 #include <stdexcept>
@@ -58,7 +59,18 @@ struct Params {
   bool linear = false;
   bool baseline = false;
   int device = 0;          // additive: HIP device ordinal
+  // Per-bin statistics beside the power (RPF_FLAG_BIN_STATS, --stats): Datastore::sum_sq, Datastore::peak.
+  bool bin_stats = false;
 };
+
+// The spectral kurtosis estimator (Nita & Gary) from S1 = sum of the frame powers and S2 = sum of their squares over
+// M frames: SK = (M+1)/(M-1) (M S2 / S1^2 - 1), in double, in exactly this order of operations (stats.py's
+// spectral_kurtosis does the same ones); NaN for M < 2 or S1 = 0.
+inline double spectral_kurtosis(double s1, double s2, int64_t M) {
+  if (M < 2 || s1 == 0.0) return std::nan("");
+  const double m = static_cast<double>(M);
+  return ((m + 1.0) / (m - 1.0)) * (m * s2 / (s1 * s1) - 1.0);
+}
 
 // A filled/empty hand-off buffer: what `Buffer&` is in acquisition.cxx:283,302-304
 // (data()/size()/resize()), backed by engine-owned pinned memory.
@@ -84,6 +96,7 @@ public:
   const Params& params;
   int64_t repeats_done = 0;          // datastore.h:38
   std::vector<double> pwr;           // datastore.h:53 (valid after finish())
+  std::vector<double> sum_sq, peak;  // params.bin_stats: S2 and PK of the acquisition (valid after finish()), else empty
 
   // datastore.cxx:23-34
   // device_override >= 0: HIP device for this instance (one Datastore per device in a
@@ -101,7 +114,11 @@ public:
     cfg.n_buffers = params.buffers;
     cfg.buffer_capacity = params.buf_length;
     cfg.device = device_override >= 0 ? device_override : params.device;
-    cfg.flags = RPF_FLAG_NONE | RPF_FLAG_SAMPLE_FORMAT(params.sample_format);
+    cfg.flags = RPF_FLAG_NONE | RPF_FLAG_SAMPLE_FORMAT(params.sample_format) | (params.bin_stats ? RPF_FLAG_BIN_STATS : 0u);
+    if (params.bin_stats) {
+      sum_sq.assign(params.N, 0.0);
+      peak.assign(params.N, 0.0);
+    }
     cfg.frame_step = params.frame_step;
     int rc = rpf_engine_create(&cfg, &engine_);
     if (rc != RPF_OK) throw RPFexception(rpf_last_global_error(), (ReturnValue)rc);
@@ -132,6 +149,7 @@ public:
   void finish() {
     check(rpf_finish(engine_, &repeats_done));
     check(rpf_get_power(engine_, pwr.data()));
+    if (params.bin_stats) check(rpf_get_bin_stats(engine_, sum_sq.data(), peak.data()));
     // 65536 ... 262144 bins: a launch of the persistent four-step kernel that could not get the whole device (another
     // process on it) gives up; the engine has run those bytes through its two-kernel path and keeps to it -- the
     // acquisition is complete and right, the operator is told once why the rest of the run is a few per cent slower

@@ -144,6 +144,34 @@ long rpf_host_format_text(double* pwr, int N, long long repeats_done, long long 
     return copy_out(os.str(), out, cap);
 }
 
+// The --stats writer (write_spectrum_text_stats); pwr and peak come back with their DC bins interpolated.
+long rpf_host_format_text_stats(double* pwr, const double* sum_sq, double* peak, int N, long long repeats_done,
+                                long long tuned_freq, int samplerate, int linear, const double* baseline, char* out,
+                                size_t cap)
+{
+    std::vector<double> p(pwr, pwr + N), s2(sum_sq, sum_sq + N), pk(peak, peak + N), b;
+    if (baseline) b.assign(baseline, baseline + N);
+    std::ostringstream os;
+    write_spectrum_text_stats(os, p, s2, pk, N, repeats_done, tuned_freq, samplerate, linear != 0, baseline ? &b : nullptr);
+    std::memcpy(pwr, p.data(), sizeof(double) * N);
+    std::memcpy(peak, pk.data(), sizeof(double) * N);
+    return copy_out(os.str(), out, cap);
+}
+
+// The text header with (stats != 0) or without the statistics columns named.
+long rpf_host_format_header(const char* start_stamp, const char* end_stamp, int stats, char* out, size_t cap)
+{
+    std::ostringstream os;
+    write_text_header(os, start_stamp, end_stamp, stats != 0);
+    return copy_out(os.str(), out, cap);
+}
+
+// datastore.h's spectral_kurtosis, element by element.
+void rpf_host_spectral_kurtosis(const double* s1, const double* s2, long long M, double* out, int n)
+{
+    for (int i = 0; i < n; ++i) out[i] = spectral_kurtosis(s1[i], s2[i], M);
+}
+
 void rpf_host_format_matrix(double* pwr, int N, long long repeats_done, int samplerate, int linear,
                             const double* baseline, float* row_out)
 {

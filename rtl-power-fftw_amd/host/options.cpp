@@ -60,6 +60,9 @@ const Spec kSpecs[] = {
     {0, "frame-overlap", Kind::Text, "percent",
      "Overlap of consecutive FFT frames inside one acquisition (Welch averaging), 0 <= percent < 100; "
      "not the hop overlap of -o. Default 0."},
+    {0, "stats", Kind::Flag, "",
+     "Per-bin statistics: two more output columns, peak hold and the spectral kurtosis estimator "
+     "(not with -m, not with several --gpus)."},
     {0, "reduce", Kind::Text, "rccl|host", "With --gpus: where a scan's per-device spectra are added (default: rccl if it loads, else host)."},
     {'h', "help", Kind::Flag, "", "Displays usage information and exits."},
     {0, "version", Kind::Flag, "", "Displays version information and exits."},
@@ -311,6 +314,14 @@ Options parse_command_line(int argc, const char* const* argv)
                                ReturnValue::InvalidArgument);
         o.session_duration_isSet = true;
     }
+    o.bin_stats = p.has("stats");
+    // (both are follow-ups: extra matrix files; a maximum beside the sum in the scan reducer)
+    if (o.bin_stats && o.matrixMode)
+        throw RPFexception("Option --stats does not combine with -m (matrix mode): the statistics are two more columns "
+                           "of the text output. Exiting.", ReturnValue::InvalidArgument);
+    if (o.bin_stats && o.devices.size() > 1)
+        throw RPFexception("Option --stats does not combine with several devices in --gpus. Exiting.",
+                           ReturnValue::InvalidArgument);
     if (p.has("input")) o.input_file = p.get("input");
     o.synthetic = p.has("synthetic");
     if (p.has("synthetic")) o.synthetic_seed = static_cast<uint64_t>(to_number<int64_t>(*find_spec("--synthetic"), p.get("synthetic")));
