@@ -33,7 +33,8 @@ extern "C" {
 #define RPF_ABI_VERSION 2   /* 2: rpf_accumulate_device_hops, rpf_device_fused_hops, rpf_scan_reducer_*;
                                additive within 2: rpf_config::frame_step, rpf_frames_in, rpf_frame_span;
                                RPF_FLAG_SAMPLE_FORMAT, RPF_FLAG_CATCH_ALL, rpf_sample_bytes, rpf_sample_format;
-                               RPF_FLAG_BIN_STATS, rpf_has_bin_stats, rpf_get_bin_stats, rpf_accumulate_device_stats */
+                               RPF_FLAG_BIN_STATS, rpf_has_bin_stats, rpf_get_bin_stats, rpf_accumulate_device_stats;
+                               rpf_accumulate_device_series, rpf_accumulate_series, rpf_series_launches */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -250,6 +251,40 @@ int rpf_accumulate_device_hops(rpf_engine* e, const void* const* d_streams, cons
 int rpf_device_fused_hops(rpf_engine* e, const void* const* d_streams, const size_t* nbytes,
                           const int64_t* repeats, int n_hops, void* hip_stream, int64_t* repeats_done);
 int rpf_max_hops_per_launch(void);
+
+/* Spectrogram: the spectrum of one stream as it changes over time.  With F = rpf_frames_in(e, nbytes), L =
+ * frames_per_spectrum >= 1 and the cap max_spectra >= 0: K = min(max_spectra, F / L) spectra (integer division: a
+ * trailing group of fewer than L frames is dropped, as a trailing partial frame is); spectrum k is the sum of |X_f|^2
+ * over the frames f in [k L, (k + 1) L), every frame unpacked, windowed and transformed exactly as
+ * rpf_accumulate_device does it on this engine (format, frame step, window, (-1)^n).  Row k = d_out[k N .. k N + N)
+ * (device doubles, 16-byte aligned), bin N/2 = DC; rows < K are overwritten, rows >= K are not touched;
+ * *spectra_done = K (may be NULL).  Same stream, alignment and no-synchronise rules as rpf_accumulate_device.  K = 0 is
+ * RPF_OK and launches nothing.
+ * Powers of two 64 .. 8192 with the frames side by side (frame step N), all three sample formats, windowed or not,
+ * either staging: ONE persistent launch walks all K spectra -- a workgroup stores the spectra that lie inside its share
+ * of the frames straight into their rows and hands over the (at most two) it shares with its neighbours, which one
+ * small fix-up launch then adds in workgroup order -- so the per-launch fixed cost is paid once, not K times, and
+ * every row is bit-reproducible for a given grid, L and K.  (More than 2^31 / ceil(L / frames per workgroup) spectra:
+ * the fewest launches that hold them.)  Every other engine -- another size, frame step S != N, RPF_FLAG_CATCH_ALL --
+ * runs spectrum by spectrum through its single-acquisition path: row k is bit for bit what rpf_accumulate_device
+ * writes for that slice of the stream (a fused four-step launch that gives up NaN-fills its own row), correct at every
+ * size and fast at none.  rpf_series_launches tells the two apart.
+ * RPF_ERR_INVALID_ARGUMENT: frames_per_spectrum < 1, max_spectra < 0, a misaligned stream or output, an engine created
+ * with RPF_FLAG_BIN_STATS (time-resolved statistics are not built). */
+int rpf_accumulate_device_series(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
+                                 int64_t max_spectra, double* d_out /* K x N */, void* hip_stream, int64_t* spectra_done);
+/* The same calculation on a host stream, the counterpart of rpf_accumulate -- but not through the buffer queues: the
+ * worker thread, pwr and repeats_done are not touched.  The stream moves through engine-owned device memory in pieces
+ * that each hold a whole number of spectra (as many as fit in 64 MB; one, if a single spectrum is larger), the device
+ * entry runs per piece on the engine's stream and each piece's rows are copied back, so device memory stays bounded for
+ * any nbytes and K.  A stream pinned with rpf_stream_register is copied from where it lies.  Synchronises before it
+ * returns.  Not while an acquisition is running. */
+int rpf_accumulate_series(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
+                          int64_t max_spectra, double* out /* K x N, host */, int64_t* spectra_done);
+/* Transform-kernel launches the engine's last series call enqueued: 1 on the one-launch path (whatever K is), K on the
+ * spectrum-by-spectrum path, summed over the pieces of rpf_accumulate_series; 0 before any series call and for K = 0.
+ * rpf_last_launch_info reports the geometry of the last of them. */
+int rpf_series_launches(const rpf_engine* e);
 
 /* Pure helpers on the engine's N and frame step S, so that callers never re-derive the formula:
  * frames(nbytes) = nbytes < 2N ? 0 : (nbytes - 2N) / (2S) + 1, and the bytes `frames` frames span,

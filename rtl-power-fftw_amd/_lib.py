@@ -92,6 +92,11 @@ _SYMBOLS = [
     ("rpf_get_bin_stats", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     ("rpf_accumulate_device_stats", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P, _P,
                                                    ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_accumulate_device_series", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64, _P, _P,
+                                                    ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_accumulate_series", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_series_launches", ctypes.c_int, [_P]),
     ("rpf_device_fused", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P,
                                         ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_device_reduce", ctypes.c_int, [_P, _P, _P]),

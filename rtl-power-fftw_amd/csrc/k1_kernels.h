@@ -7,6 +7,7 @@
 
 #include "rpf_device_common.h"
 #include "rpf_kernels.h"
+#include "series_partition.h"
 
 namespace rpf {
 
@@ -152,6 +153,10 @@ struct HopLanes {
     }
 };
 
+// the output rows of a series launch (k1_scan_body.inc; the scan kernel has none and never asks)
+__device__ __forceinline__ double* series_rows(const HopArgs&) { return nullptr; }
+__device__ __forceinline__ double* series_rows(const SeriesArgs& a) { return a.out; }
+
 // DBUF: two slabs used alternately.  With one slab the pass-1 store of frame f+1
 // must wait (workgroup barrier at the top of the loop) until every wave has
 // finished reading frame f's slab; with two, the single barrier after the pass-1
@@ -180,215 +185,26 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_scan_kernel(const cf* __res
                                                             double* __restrict__ partial,
                                                             const HopArgs hops)
 {
-    constexpr int P = G::P, T = G::T, N = G::N, NPASS = G::NPASS;
-    constexpr int FPW = WG / T;
-    constexpr int NSLAB = DBUF ? 2 : 1;
-    constexpr bool BLOCK_SYNC = (T > 64);
-    static_assert(WG % T == 0 && WG % 64 == 0, "");
+    constexpr bool SERIES = false;
+    using TABLE = HopLanes;
+#include "k1_scan_body.inc"
+}
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    cf* const slab_base = reinterpret_cast<cf*>(smem);                        // [NSLAB][FPW][LDS_CPX]
-    uint8_t* const raw_base = smem + NSLAB * FPW * G::LDS_CPX * sizeof(cf);  // [WG/64][RAWD][128 P]
-
-    const int tid = threadIdx.x;
-    const int fs = tid / T, t = tid % T;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    constexpr int RAW_SLOT = raw_chunk_of(FMT) * P;   // bytes one wave stages per frame
-    constexpr int PIECES = P / 8 * (sample_bytes_of(FMT) / 2);   // DMA instructions per wave per frame
-    static_assert((RAWD - 1) * PIECES <= 63, "the counted wait below: vmcnt is a 6-bit field");
-    uint8_t* const wave_raw = raw_base + wave * (RAWD * RAW_SLOT);
-
-    // This workgroup's iterations: `count` of them, `step` apart from `first` on (hop_partition.h).
-    // The host launches at most one workgroup per iteration (launch_fft_accum checks it), so
-    // count >= 1 -- deliberately not tested here: a branch on q and r would put their scalar
-    // load in front of the table loads instead of beside them.
-    HopLanes tbl;
-    tbl.load(hops);
-    const int step = hops.step;
-    int first, count;
-    hop_share(static_cast<int>(blockIdx.x), hops.q, hops.r, step, &first, &count);
-
-    // First thing: get the first iterations' bytes moving (HBM latency overlaps the constant
-    // loads below).  The staging cursor `ahead` runs RAWD iterations in front of the compute
-    // cursor, across hop boundaries; every iteration issues PIECES DMAs.  The frame loop sees
-    // of it only a frame index that advances and a countdown: `ahead_run` stagings stay inside
-    // the hop the cursor stands in (scans have step = 1, an interleaved single acquisition
-    // never leaves its hop), then ahead_turn() moves the cursor on -- or, when nothing is left
-    // to stage, parks it on the launch's iteration 0 with no advance: the same 2N FPW bytes
-    // for every workgroup, an L2 hit, so the surplus (never read) stagings that keep the DMA
-    // count per iteration constant cost no memory traffic.
-    const int fstep = FPW * step;                  // frames between a workgroup's iterations
-    HopCursor ahead;
-    ahead.seek(tbl, first);
-    int ahead_fb = (ahead.j - ahead.begin) * FPW, ahead_fstep = fstep;
-    int ahead_left = count;                        // real iterations not staged yet
-    auto run_length = [&](const HopCursor& c, int left) {
-        const int in_hop = step == 1 ? c.end - c.j : left;
-        return in_hop < left ? in_hop : left;
-    };
-    int ahead_run = run_length(ahead, ahead_left);
-    ahead_left -= ahead_run;
-    auto ahead_turn = [&]() {
-        if (ahead_left > 0) {
-            ahead.seek(tbl, ahead.end);            // (step == 1 here: the next hop starts where this one ended)
-            ahead_fb = 0;
-            ahead_run = run_length(ahead, ahead_left);
-            ahead_left -= ahead_run;
-        } else {
-            ahead.seek(tbl, 0);
-            ahead_fb = 0;
-            ahead_fstep = 0;
-            ahead_run = 0x7fffffff;
-        }
-    };
-    auto stage_next = [&](uint8_t* dst) {
-        stage_raw<G, DMA, int, FMT>(ahead.stream, ahead_fb, ahead.nframes, dst, wave, lane);
-        ahead_fb += ahead_fstep;
-        if (--ahead_run == 0) ahead_turn();
-    };
-    if constexpr (!(ABL & 8)) {
-#pragma unroll
-        for (int d = 0; d < RAWD; ++d) stage_next(wave_raw + d * RAW_SLOT);
-    }
-
-    // Loop-invariant per-thread constants: twiddles, sign, window.
-    cf tw[NPASS - 1][P - 1];
-    load_twiddles<G, 1, TWLDS>(t, twN, tw);
-    cf* const twtable = reinterpret_cast<cf*>(raw_base + (WG / 64) * RAWD * RAW_SLOT);
-    if constexpr (TWLDS) {
-        fill_twlds<G, 1>(tid, WG, twN, twtable);
-        exchange_sync<true>();
-    }
-    const float sgn = (t & 1) ? -1.0f : 1.0f;
-    float wsgn[P];
-    if constexpr (WINDOW) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) wsgn[a] = window[t + T * a] * sgn;
-    }
-    double acc[P];
-    float acc32[ACCB > 0 ? P : 1];
-
-    PhaseClock clk;
-    clk.start();
-    HopCursor cur;
-    cur.seek(tbl, first);
-    int it = 0;                                    // iterations done: ring slot and slab parity
-    while (true) {
-        // ---- one segment: this workgroup's iterations inside hop cur.h ------------------------
-        const int seg = run_length(cur, count - it);
-#pragma unroll
-        for (int a = 0; a < P; ++a) acc[a] = 0.0;
-        if constexpr (ACCB > 0) {
-#pragma unroll
-            for (int a = 0; a < P; ++a) acc32[a] = 0.0f;
-        }
-        int fb = (cur.j - cur.begin) * FPW;        // slot-0 frame of the iteration, within the hop
-        for (int n = seg; n > 0; --n, ++it, fb += fstep) {
-            const bool active = (fb + fs) < cur.nframes;
-            cf* const slab = slab_base + ((DBUF ? (it & 1) : 0) * FPW + fs) * G::LDS_CPX;
-            uint8_t* const ring_slot = wave_raw + (it % RAWD) * RAW_SLOT;
-            cf x[P];
-
-            // this iteration's bytes have landed: every iteration issues exactly PIECES DMA
-            // instructions per wave, so all but the newest (RAWD-1) iterations' worth are done
-            if constexpr (DMA && !(ABL & 8))
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RAWD - 1) * PIECES) : "memory");
-            exchange_sync<false>();
-            RPF_STAMP(clk, 0);                   // waiting for the staged bytes
-            phase_unpack<G, WINDOW, FMT>(ring_slot + sample_bytes_of(FMT) * lane, sgn, wsgn, x);
-            // The slot is refilled next: its ds_read_u16 must have RETURNED first (a DMA
-            // that hits in L2/MALL can land before queued LDS reads execute -- seen as
-            // sporadic 1e-3 errors), so wait for this wave's LDS reads, not just issue.
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            exchange_sync<false>();
-            RPF_STAMP(clk, 1);                   // unpack
-            // the slot has been consumed: refill it with the iteration RAWD ahead
-            if constexpr (!(ABL & 8)) stage_next(ring_slot);
-            RPF_STAMP(clk, 3);                   // DMA issue
-
-            // single slab: every wave must be done with the previous frame's slab
-            if constexpr (!DBUF) exchange_sync<BLOCK_SYNC>();
-            RPF_STAMP(clk, 2);                       // top-of-frame barrier
-            middle_passes<G, 1, ABL, TWLDS>(t, x, tw, slab, clk, twtable);   // stamps 4J..4J+3
-            if constexpr (!(ABL & 4)) phase_fetch<G, NPASS>(t, x, slab);
-            asm volatile("" : "+v"(x[0]));
-            RPF_STAMP(clk, 12);                      // last fetch
-            if constexpr (!(ABL & 2)) phase_last<G>(x);
-            RPF_STAMP(clk, 13);                      // last butterfly
-            if constexpr (ACCB > 0) {
-                if (active) {
-#pragma unroll
-                    for (int a = 0; a < P; ++a)
-                        acc32[a] = __builtin_fmaf(x[a].x, x[a].x, __builtin_fmaf(x[a].y, x[a].y, acc32[a]));
-                }
-                if ((it % ACCB) == ACCB - 1) {
-#pragma unroll
-                    for (int a = 0; a < P; ++a) {
-                        acc[a] += static_cast<double>(acc32[a]);
-                        acc32[a] = 0.0f;
-                    }
-                }
-            } else if constexpr (ABL & 1) {
-#pragma unroll
-                for (int a = 0; a < P; ++a) asm volatile("" ::"v"(x[a]));
-            } else {
-                if (active) phase_accumulate(x, acc, P);
-            }
-            RPF_STAMP(clk, 14);                      // accumulate
-        }
-        if constexpr (ACCB > 0) {
-#pragma unroll
-            for (int a = 0; a < P; ++a) acc[a] += static_cast<double>(acc32[a]);
-        }
-
-        // ---- hand the segment over: one partial spectrum (the FPW frame slots summed) ----------
-        // The accumulators go through the slab (free between frames; the raw ring with its
-        // in-flight prefetches is not touched) so that the bin-scattered registers leave as
-        // fully coalesced 512-byte rows: stage at a padded bin index (one spare double per
-        // 16, conflict-free for the stride-16 bin pattern of bin_of), then stream out.
-        exchange_sync<true>();
-        double* const stage = reinterpret_cast<double*>(smem);          // [FPW][N + N/16]
-        constexpr int SN = N + N / 16;
-        static_assert(sizeof(double) * SN <= sizeof(cf) * G::LDS_CPX, "the stage stays inside the slab");
-        // (opaque copies of the thread indices: the hand-over runs once per hop, its sixteen
-        // stage addresses must not be hoisted into registers that live across the frame loop)
-        int ft = t, ftid = tid, ffs = fs;
-        asm volatile("" : "+v"(ft), "+v"(ftid), "+v"(ffs));
-#pragma unroll
-        for (int a = 0; a < P; ++a) {
-            const int bin = bin_of<G>(ft, a);
-            stage[ffs * SN + bin + (bin >> 4)] = acc[a];
-        }
-        exchange_sync<true>();
-        const size_t slot = static_cast<size_t>(tbl.slot_bias(cur.h) + static_cast<int>(blockIdx.x));
-        if constexpr (PF32) {
-            for (int bin = ftid; bin < N; bin += WG) {
-                double v = 0.0;
-#pragma unroll
-                for (int k = 0; k < FPW; ++k) v += stage[k * SN + bin + (bin >> 4)];
-                reinterpret_cast<float*>(partial)[slot * N + bin] = static_cast<float>(v);
-            }
-        } else {
-            // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
-            // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
-            // Written through (store_partial2), as K1's flush.
-            for (int bin = 2 * ftid; bin < N; bin += 2 * WG) {
-                partial2_t v = {0.0, 0.0};
-#pragma unroll
-                for (int k = 0; k < FPW; ++k) {
-                    v.x += stage[k * SN + bin + (bin >> 4)];
-                    v.y += stage[k * SN + bin + 1 + (bin >> 4)];
-                }
-                store_partial2(partial + slot * N + bin, v);
-            }
-        }
-        if (it >= count) break;
-        // next hop: the slab is reused by its first frame once every wave has read the stage
-        exchange_sync<true>();
-        cur.seek(tbl, cur.end);                    // (a segment that is not the last ends with its hop)
-    }
-    clk.publish(lane);
-    if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // trailing (repeated) prefetches
+// ---- K1, a uniform series of spectra per launch ---------------------------------------------
+// The scan kernel's frame loop and hand-over over an arithmetic table (series_partition.h): spectrum k = the L frames
+// from frame k L of one stream, as many spectra as the launch's 2^31 iterations hold.  A spectrum that lies inside one
+// workgroup's range goes straight to its row of hops.out; one that is cut leaves its segments in the partial slots
+// 2w / 2w + 1 for series_fixup_kernel.  Instantiated in rpf_kernels_series.hip only.
+template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
+          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8>
+__global__ __launch_bounds__(WG, OCC) void fft_accum_series_kernel(const cf* __restrict__ twN,
+                                                              const float* __restrict__ window,
+                                                              double* __restrict__ partial,
+                                                              const SeriesArgs hops)
+{
+    constexpr bool SERIES = true;
+    using TABLE = SeriesTable;
+#include "k1_scan_body.inc"
 }
 
 }  // namespace

@@ -152,6 +152,15 @@ struct rpf_engine {
     int last_slots = 0;                   // partial spectra left by the last transform
     rpf::SlotRanges last_ranges;          // ... and which of them belong to which hop (K1 hop launches)
     int last_hops = 0;                    // hops of the last rpf_device_fused_hops (0: a single-acquisition transform)
+    // series entries (rpf_accumulate_device_series, rpf_accumulate_series); all allocated at the first call that needs them
+    bool series_planned = false;
+    rpf::LaunchInfo series_plan;          // the series kernel's resident grid
+    double* d_series_partial = nullptr;   // its scratch: 2 x grid x N doubles, whatever K is
+    int series_launches = 0;              // transform-kernel launches of the last series call
+    uint8_t* d_series_in = nullptr;       // rpf_accumulate_series: one piece of the host stream ...
+    size_t series_in_bytes = 0;
+    double* d_series_out = nullptr;       // ... and its rows
+    size_t series_out_rows = 0;
 
     mutable std::string last_error;
 };
@@ -785,6 +794,9 @@ void release_device(rpf_engine* e)
     if (e->d_bhat) (void)hipFree(e->d_bhat);
     if (e->d_window) (void)hipFree(e->d_window);
     if (e->d_partial) (void)hipFree(e->d_partial);
+    if (e->d_series_partial) (void)hipFree(e->d_series_partial);
+    if (e->d_series_in) (void)hipFree(e->d_series_in);
+    if (e->d_series_out) (void)hipFree(e->d_series_out);
     if (e->d_pwr) (void)hipFree(e->d_pwr);
     for (auto& s : e->staging) {
         if (s.base) (void)hipFree(s.base);
@@ -1596,6 +1608,145 @@ int rpf_device_fused_hops(rpf_engine* e, const void* const* d_streams, const siz
     e->last_hops = n_hops;
     return RPF_OK;
 }
+
+// ---- spectrogram: consecutive L-frame spectra of one stream ----------------------------------------------------
+
+// The series kernel serves this engine: K1 (variant 0), frames side by side, and L small enough for its int frame index.
+static bool series_native(const rpf_engine* e, int64_t L)
+{
+    return is_k1(e) && !overlapped(e) && e->variant == 0 && !e->stats && L <= INT32_MAX - 64 &&
+           rpf::series_supported(e->N, e->format);
+}
+
+static int series_check(rpf_engine* e, const char* who, const void* stream, size_t nbytes, int64_t L, int64_t max_spectra,
+                        const void* out)
+{
+    if (!e || !out || (!stream && nbytes)) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+    if (e->stats)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": not on an engine with RPF_FLAG_BIN_STATS (time-resolved statistics are not built)");
+    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": acquisition running");
+    if (L < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": frames_per_spectrum must be at least 1");
+    if (max_spectra < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": max_spectra must not be negative");
+    return RPF_OK;
+}
+
+// K spectra of L frames from d_stream into d_out on `s`; counts the transform launches into e->series_launches.
+static int series_enqueue(rpf_engine* e, const uint8_t* d_stream, int64_t L, int64_t K, double* d_out, hipStream_t s)
+{
+    const size_t N = static_cast<size_t>(e->N);
+    if (!series_native(e, L)) {
+        // spectrum by spectrum through the engine's own single-acquisition path (any size, any frame step): spectrum k
+        // starts at frame k L = byte k L bS
+        const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
+        for (int64_t k = 0; k < K; ++k) {
+            const int rc = launch_frames(e, d_stream + static_cast<size_t>(k) * hop, L, d_out + static_cast<size_t>(k) * N,
+                                         /*accumulate=*/false, s);
+            if (rc != RPF_OK) return rc;
+            ++e->series_launches;
+        }
+        return RPF_OK;
+    }
+    if (!e->series_planned) {
+        HIP_TRY(e, rpf::plan_series(e->N, e->has_window, e->device, &e->series_plan, e->format));
+        HIP_TRY(e, hipMalloc(&e->d_series_partial, sizeof(double) * 2 * N * static_cast<size_t>(e->series_plan.grid)));
+        e->series_planned = true;
+    }
+    const long frame_bytes = static_cast<long>(e->sample_bytes) * e->N;
+    const bool dma = e->use_dma && (reinterpret_cast<uintptr_t>(d_stream) % 16) == 0;     // (bN is a multiple of 16)
+    const int64_t per_launch = rpf::series_max_spectra(L, e->series_plan.fpw);          // K ips fits an int
+    const int64_t launches = (K + per_launch - 1) / per_launch;
+    const int64_t share = (K + launches - 1) / launches;
+    for (int64_t k0 = 0; k0 < K; k0 += share) {
+        const int64_t kc = std::min(share, K - k0);
+        rpf::SeriesArgs args;
+        const int grid = rpf::partition_series(kc, L, e->series_plan.fpw, e->series_plan.grid, frame_bytes, &args);
+        if (grid < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_series: too many frames for one launch");
+        args.stream = d_stream + static_cast<size_t>(k0) * static_cast<size_t>(args.spectrum_bytes);
+        args.out = d_out + static_cast<size_t>(k0) * N;
+        HIP_TRY(e, rpf::launch_fft_accum_series(e->N, e->has_window, dma, args, e->d_twiddles, e->d_window,
+                                                e->d_series_partial, grid, s, &e->last, e->format));
+        ++e->series_launches;
+    }
+    return RPF_OK;
+}
+
+int rpf_accumulate_device_series(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
+                                 int64_t max_spectra, double* d_out, void* hip_stream, int64_t* spectra_done)
+{
+    const char* const who = "rpf_accumulate_device_series";
+    int rc = series_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out);
+    if (rc != RPF_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
+    e->series_launches = 0;
+    const int64_t K = std::min(max_spectra, frames_in(e, nbytes) / frames_per_spectrum);
+    if (spectra_done) *spectra_done = K;
+    if (K == 0) return RPF_OK;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    return series_enqueue(e, static_cast<const uint8_t*>(d_stream), frames_per_spectrum, K, d_out,
+                          static_cast<hipStream_t>(hip_stream));
+}
+
+int rpf_accumulate_series(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
+                          int64_t max_spectra, double* out, int64_t* spectra_done)
+{
+    int rc = series_check(e, "rpf_accumulate_series", stream, nbytes, frames_per_spectrum, max_spectra, out);
+    if (rc != RPF_OK) return rc;
+    e->series_launches = 0;
+    const int64_t L = frames_per_spectrum;
+    const int64_t K = std::min(max_spectra, frames_in(e, nbytes) / L);
+    if (spectra_done) *spectra_done = K;
+    if (K == 0) return RPF_OK;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    // A piece = the whole number of spectra whose frames span at most kSeriesPiece bytes, at least one spectrum;
+    // spectrum k starts at byte k L bS and p spectra span frame_span(p L) bytes.
+    constexpr size_t kSeriesPiece = static_cast<size_t>(64) << 20;
+    const size_t N = static_cast<size_t>(e->N);
+    const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
+    const int64_t fit = frames_in(e, kSeriesPiece) / L;
+    const int64_t per_piece = std::min(K, std::max<int64_t>(1, fit));
+    const size_t piece_bytes = frame_span(e, per_piece * L);
+    if (piece_bytes > e->series_in_bytes) {
+        HIP_TRY(e, hipStreamSynchronize(e->compute_stream));
+        if (e->d_series_in) (void)hipFree(e->d_series_in);
+        e->d_series_in = nullptr;
+        e->series_in_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->d_series_in, piece_bytes));
+        e->series_in_bytes = piece_bytes;
+    }
+    if (static_cast<size_t>(per_piece) > e->series_out_rows) {
+        HIP_TRY(e, hipStreamSynchronize(e->compute_stream));
+        if (e->d_series_out) (void)hipFree(e->d_series_out);
+        e->d_series_out = nullptr;
+        e->series_out_rows = 0;
+        HIP_TRY(e, hipMalloc(&e->d_series_out, sizeof(double) * N * static_cast<size_t>(per_piece)));
+        e->series_out_rows = static_cast<size_t>(per_piece);
+    }
+    // (a stream pinned with rpf_stream_register is copied from where it lies, asynchronously; a pageable one through
+    // the runtime's own staging)
+    hipStream_t s = e->compute_stream;
+    for (int64_t k0 = 0; k0 < K; k0 += per_piece) {
+        const int64_t kc = std::min(per_piece, K - k0);
+        HIP_TRY(e, hipMemcpyAsync(e->d_series_in, stream + static_cast<size_t>(k0) * hop, frame_span(e, kc * L),
+                                  hipMemcpyHostToDevice, s));
+        rc = series_enqueue(e, e->d_series_in, L, kc, e->d_series_out, s);
+        if (rc != RPF_OK) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        HIP_TRY(e, hipMemcpyAsync(out + static_cast<size_t>(k0) * N, e->d_series_out, sizeof(double) * N * static_cast<size_t>(kc),
+                                  hipMemcpyDeviceToHost, s));
+        HIP_TRY(e, hipStreamSynchronize(s));       // the piece's buffers are reused by the next one
+    }
+    return RPF_OK;
+}
+
+int rpf_series_launches(const rpf_engine* e) { return e ? e->series_launches : 0; }
 
 int rpf_stream_register(rpf_engine* e, const void* stream, size_t nbytes)
 {

@@ -9,6 +9,7 @@
 
 #include "fft_core.h"
 #include "hop_partition.h"
+#include "series_partition.h"
 
 namespace rpf {
 
@@ -56,6 +57,19 @@ hipError_t launch_reduce_stats(const double* d_partial, int nslots, int N, doubl
 hipError_t launch_fft_accum_hops(int N, int vid, bool window, bool use_dma, const HopArgs& hops,
                                  const cf* d_twiddles, const float* d_window, double* d_partial, int grid,
                                  hipStream_t stream, LaunchInfo* li, int fmt = kFmtCu8);
+
+// ---- a uniform series of spectra in ONE launch (rpf_kernels_series.hip, series_partition.h) ----
+// Variant 0 of every K1 size, all three sample formats.
+bool series_supported(int N, int fmt = kFmtCu8);
+// The series kernel's resident grid (it may differ from plan_launch's: another kernel, its own register count).
+hipError_t plan_series(int N, bool window, int device, LaunchInfo* li, int fmt = kFmtCu8);
+// args from partition_series (+ stream, out), `grid` what it returned for (li->fpw, the planned grid).  Spectrum k =
+// frames [k L, (k + 1) L) of args.stream (frames side by side) -> args.out[k N ..), overwritten; d_partial: scratch of
+// 2 x grid x N doubles.  Two enqueues: the persistent kernel, then the fix-up of the spectra cut by workgroup
+// boundaries (none with one workgroup).
+hipError_t launch_fft_accum_series(int N, bool window, bool use_dma, const SeriesArgs& args, const cf* d_twiddles,
+                                   const float* d_window, double* d_partial, int grid, hipStream_t stream,
+                                   LaunchInfo* li, int fmt = kFmtCu8);
 
 // d_out[bin] = (accumulate ? d_out[bin] : 0) + sum_{s < nslots} d_partial[s*stride + bin],
 // summed in a fixed order (deterministic).

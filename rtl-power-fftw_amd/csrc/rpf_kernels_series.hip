@@ -1,0 +1,158 @@
+// rpf_kernels_series.hip -- K1 for a uniform series of spectra (rpf_accumulate_device_series): fft_accum_series_kernel
+// (k1_kernels.h, k1_scan_body.inc) for variant 0 of every K1 size x {plain, windowed} x {LDS-DMA, VGPR staging} x
+// {cu8, cs8, cs16}, with the geometry of the size's scan-kernel entry, and the fix-up kernel that adds the segments of
+// the spectra a workgroup boundary cuts.  A translation unit of its own: it compiles beside the others and none of
+// their kernels moves.
+#include <algorithm>
+
+#include "k1_kernels.h"
+
+namespace rpf {
+
+namespace {
+
+using SeriesFn = void (*)(const cf*, const float*, double*, const SeriesArgs);
+
+struct SeriesVariant {
+    int N, WG, fpw, lds_bytes;
+    SeriesFn fn[2][2];       // [window][dma]
+};
+
+template <int N, int P, int OCC, int OCCW, int RAWD, bool TWLDS, int WGO, int FMT>
+SeriesVariant make_series()
+{
+    using G = Geom<N, P>;
+    constexpr int WG = WGO ? WGO : (G::T >= 256 ? G::T : 256);
+    constexpr int FPW = WG / G::T;
+    constexpr int LDS = FPW * (G::LDS_CPX * (int)sizeof(cf) + RAWD * sample_bytes_of(FMT) * N) +
+                        (TWLDS ? twlds_entries<G>() * (int)sizeof(cf) : 0);
+    return SeriesVariant{N, WG, FPW, LDS,
+                         {{fft_accum_series_kernel<G, WG, OCC, false, false, false, 0, false, RAWD, 0, TWLDS, FMT>,
+                           fft_accum_series_kernel<G, WG, OCC, false, true, false, 0, false, RAWD, 0, TWLDS, FMT>},
+                          {fft_accum_series_kernel<G, WG, OCCW, true, false, false, 0, false, RAWD, 0, TWLDS, FMT>,
+                           fft_accum_series_kernel<G, WG, OCCW, true, true, false, 0, false, RAWD, 0, TWLDS, FMT>}}};
+}
+
+template <int FMT>
+const SeriesVariant* find_in_table(int N)
+{
+    constexpr int R = FMT == kFmtCs16 ? 2 : 4;     // ring depth of the three smallest sizes (rpf_kernels_formats.hip)
+    // Template arguments after <N, P>: OCC, OCCW, RAWD, TWLDS, WGO, FMT -- the defaults of rpf_kernels.hip's kVariants
+    static const SeriesVariant table[] = {
+        make_series<64, 8, 4, 4, R, false, 0, FMT>(),       make_series<128, 16, 3, 3, R, false, 0, FMT>(),
+        make_series<256, 16, 3, 3, R, false, 0, FMT>(),     make_series<512, 8, 4, 4, 2, false, 0, FMT>(),
+        make_series<1024, 16, 3, 2, 2, true, 0, FMT>(),     make_series<2048, 16, 2, 2, 2, true, 512, FMT>(),
+        make_series<4096, 16, 2, 2, 2, true, 512, FMT>(),   make_series<8192, 16, 2, 2, 2, false, 0, FMT>(),
+    };
+    for (const SeriesVariant& v : table)
+        if (v.N == N) return &v;
+    return nullptr;
+}
+
+const SeriesVariant* find_series(int N, int fmt)
+{
+    return fmt == kFmtCu8    ? find_in_table<kFmtCu8>(N)
+           : fmt == kFmtCs8  ? find_in_table<kFmtCs8>(N)
+           : fmt == kFmtCs16 ? find_in_table<kFmtCs16>(N)
+                             : nullptr;
+}
+
+// The spectra that a workgroup boundary cuts.  blockIdx.y + 1 = b, the boundary between workgroups b - 1 and b (at
+// iteration lo_b); it lies inside spectrum k = lo_b / ips unless lo_b is that spectrum's first iteration.  The block of
+// the FIRST boundary inside k (b - 1 holds k's first iteration) writes row k; the others leave.  The segments are those
+// of the workgroups wa .. wb that hold k's first and last iteration (closed form: series_wg_of), wa's in slot 2 wa + 1,
+// every later one's in slot 2w.  K3's thread layout (reduce_kernel): thread (g, b) adds the segments g, g + GROUPS, ... of
+// one bin pair with 16-byte loads, then the group sums are added in group order -- for up to GROUPS segments that IS
+// workgroup order, and for any number the order is fixed by (grid, L, K) alone.
+template <int PAIRS, int GROUPS>
+__global__ __launch_bounds__(PAIRS* GROUPS) void series_fixup_kernel(const double* __restrict__ partial,
+                                                                     const SeriesArgs a, int N)
+{
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    __shared__ d2 red[GROUPS][PAIRS + 1];
+    const int bnd = static_cast<int>(blockIdx.y) + 1;
+    int lo, hi;
+    hop_range(bnd, a.q, a.r, &lo, &hi);
+    const int k = series_div(lo, a.magic, a.shift);
+    if (k * a.ips == lo) return;                                  // the boundary separates two spectra
+    int wa, wb;
+    series_spectrum_wgs(k, a, &wa, &wb);
+    if (wa != bnd - 1) return;                                    // an earlier boundary's block writes this row
+    const int nseg = wb - wa + 1;
+    const int b = threadIdx.x % PAIRS, g = threadIdx.x / PAIRS;
+    const int bin = blockIdx.x * (2 * PAIRS) + 2 * b;             // N is even: a pair never straddles the end
+    d2 s = {0.0, 0.0};
+    if (bin < N) {
+        for (int j = g; j < nseg; j += GROUPS) {
+            const size_t slot = static_cast<size_t>(2 * (wa + j) + (j == 0 ? 1 : 0));
+            const d2 v = *reinterpret_cast<const d2*>(partial + slot * N + bin);
+            s.x += v.x;
+            s.y += v.y;
+        }
+    }
+    red[g][b] = s;
+    __syncthreads();
+    if (g == 0 && bin < N) {
+        d2 tot = {0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < GROUPS; ++j) {
+            tot.x += red[j][b].x;
+            tot.y += red[j][b].y;
+        }
+        *reinterpret_cast<d2*>(a.out + static_cast<size_t>(k) * N + bin) = tot;
+    }
+}
+
+}  // namespace
+
+bool series_supported(int N, int fmt) { return find_series(N, fmt) != nullptr; }
+
+hipError_t plan_series(int N, bool window, int device, LaunchInfo* li, int fmt)
+{
+    const SeriesVariant* v = find_series(N, fmt);
+    if (!v) return hipErrorInvalidValue;
+    int per_cu = 1 << 30;
+    for (int d = 0; d < 2; ++d) {             // the two staging forms share one grid
+        const void* fn = reinterpret_cast<const void*>(v->fn[window ? 1 : 0][d]);
+        hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, v->lds_bytes);
+        if (err != hipSuccess) return err;
+        int n = 0;
+        err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, v->WG, v->lds_bytes);
+        if (err != hipSuccess) return err;
+        per_cu = std::min(per_cu, n);
+    }
+    hipDeviceProp_t prop;
+    hipError_t err = hipGetDeviceProperties(&prop, device);
+    if (err != hipSuccess) return err;
+    li->grid = std::max(per_cu, 1) * prop.multiProcessorCount;
+    li->block = v->WG;
+    li->fpw = v->fpw;
+    li->lds_bytes = v->lds_bytes;
+    li->partial_f32 = false;
+    return hipSuccess;
+}
+
+hipError_t launch_fft_accum_series(int N, bool window, bool use_dma, const SeriesArgs& args, const cf* d_twiddles,
+                                   const float* d_window, double* d_partial, int grid, hipStream_t stream,
+                                   LaunchInfo* li, int fmt)
+{
+    const SeriesVariant* v = find_series(N, fmt);
+    if (!v || grid < 1 || grid > args.total || args.K < 1 || !args.stream || !args.out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(v->fn[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->WG), v->lds_bytes, stream, d_twiddles,
+                       d_window, d_partial, args);
+    if (li) {
+        li->grid = grid;
+        li->block = v->WG;
+        li->fpw = v->fpw;
+        li->lds_bytes = v->lds_bytes;
+        li->partial_f32 = false;
+    }
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess || grid < 2) return err;       // one workgroup: every spectrum is complete
+    constexpr int PAIRS = 8, GROUPS = 16;
+    const dim3 blocks((N + 2 * PAIRS - 1) / (2 * PAIRS), grid - 1);
+    hipLaunchKernelGGL((series_fixup_kernel<PAIRS, GROUPS>), blocks, dim3(PAIRS * GROUPS), 0, stream, d_partial, args, N);
+    return hipGetLastError();
+}
+
+}  // namespace rpf

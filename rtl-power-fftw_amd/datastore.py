@@ -222,6 +222,33 @@ class Datastore:
             ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(hip_stream), ctypes.byref(done)))
         return done.value
 
+    def accumulate_device_series(self, d_stream_ptr, nbytes, frames_per_spectrum, max_spectra, d_out_ptr, hip_stream=0):
+        """rpf_accumulate_device_series: consecutive spectra of `frames_per_spectrum` frames of a stream resident in
+        HBM, row k of d_out (K x N device doubles) = frames [k L, (k + 1) L); asynchronous.  Returns K."""
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_accumulate_device_series(
+            self._handle, ctypes.c_void_p(d_stream_ptr), nbytes, frames_per_spectrum, max_spectra,
+            ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(hip_stream), ctypes.byref(done)))
+        return done.value
+
+    def accumulate_series(self, stream, frames_per_spectrum, max_spectra=None):
+        """rpf_accumulate_series: the same on a host byte stream (not through the buffer queues).  Returns
+        (K x N array, K); max_spectra None = every whole spectrum the stream holds."""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        if max_spectra is None:
+            max_spectra = max(self.frames_in(stream.size) // frames_per_spectrum, 0) if frames_per_spectrum >= 1 else 0
+        rows = max(min(max_spectra, self.frames_in(stream.size) // max(frames_per_spectrum, 1)), 0)
+        out = np.zeros((max(rows, 1), self.params.N), dtype=np.float64)
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_accumulate_series(
+            self._handle, ctypes.c_void_p(stream.ctypes.data), stream.size, frames_per_spectrum, max_spectra,
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(done)))
+        return out[:done.value], done.value
+
+    def series_launches(self):
+        """rpf_series_launches: transform launches of the last series call (1 = the one-launch path)."""
+        return self._lib.rpf_series_launches(self._handle)
+
     def device_fused(self, d_stream_ptr, nbytes, repeats, hip_stream=0):
         """K1 only (measurement hook, rpf_device_fused)."""
         done = ctypes.c_int64()

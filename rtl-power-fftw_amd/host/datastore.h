@@ -9,6 +9,7 @@
 #ifndef RPF_HOST_DATASTORE_H
 #define RPF_HOST_DATASTORE_H
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <iostream>
@@ -161,6 +162,29 @@ public:
       fused_gave_up_ = gave_up;
     }
   }
+  // Spectrogram (rpf_accumulate_series): consecutive spectra of frames_per_spectrum frames of a host stream, row k of
+  // `rows` (resized to K x N) = frames [k L, (k + 1) L).  Not through the buffer queues: pwr and repeats_done stay.
+  // Returns K = min(max_spectra, frames / L).
+  int64_t accumulate_series(const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra,
+                            std::vector<double>& rows) {
+    const int64_t frames = rpf_frames_in(engine_, nbytes);
+    const int64_t fit = frames_per_spectrum >= 1 ? frames / frames_per_spectrum : 0;
+    rows.assign(static_cast<size_t>(std::max<int64_t>(1, std::min(fit, std::max<int64_t>(max_spectra, 0)))) * params.N, 0.0);
+    int64_t done = 0;
+    check(rpf_accumulate_series(engine_, stream, nbytes, frames_per_spectrum, max_spectra, rows.data(), &done));
+    rows.resize(static_cast<size_t>(done) * params.N);
+    return done;
+  }
+  // The same on a stream resident in HBM (rpf_accumulate_device_series): d_out = K x N device doubles, asynchronous
+  // on hip_stream.
+  int64_t accumulate_device_series(const void* d_stream, size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra,
+                                   double* d_out, void* hip_stream = nullptr) {
+    int64_t done = 0;
+    check(rpf_accumulate_device_series(engine_, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out, hip_stream, &done));
+    return done;
+  }
+  // transform launches of the last series call: 1 = the one-launch path
+  int series_launches() const { return rpf_series_launches(engine_); }
   // the engine behind this Datastore (multi-device scans hand it to the scan reducer)
   const rpf_engine* engine() const { return engine_; }
   // datastore.cxx:98-103

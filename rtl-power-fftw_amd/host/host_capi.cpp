@@ -2,6 +2,7 @@
 // host (option parsing, unit parsing, Plan, aux-file parsing, spectrum writer)
 // so that tests/ can drive them through ctypes and compare with the oracle's
 // restatements and the man page.  Not needed by the CLI itself.
+#include <algorithm>
 #include <cstring>
 #include <sstream>
 #include <string>
@@ -181,6 +182,37 @@ void rpf_host_format_matrix(double* pwr, int N, long long repeats_done, int samp
     spectrum_matrix_row(p, N, repeats_done, samplerate, linear != 0, baseline ? &b : nullptr, row);
     std::memcpy(row_out, row.data(), sizeof(float) * N);
     std::memcpy(pwr, p.data(), sizeof(double) * N);
+}
+
+// rpf_host::Datastore's two series calls (needs a device, unlike the rest of this shim): spectra of L frames of a
+// host stream through accumulate_series into out[cap_rows x N]; device != 0: the stream is first copied to the GPU by
+// the caller (d_stream, d_out device pointers) and accumulate_device_series runs on the null stream.  Returns K, or
+// -(the reference's exit code) with the message in `msg`.
+long long rpf_host_accumulate_series(int N, int sample_format, int frame_step, const unsigned char* stream, size_t nbytes,
+                                     long long L, long long max_spectra, double* out, long long cap_rows, int device_resident,
+                                     int* launches, char* msg, size_t cap)
+{
+    try {
+        Params params;
+        params.N = N;
+        params.sample_format = sample_format;
+        params.frame_step = frame_step;
+        std::vector<float> no_window;
+        Datastore data(params, no_window);
+        long long done = 0;
+        if (device_resident) {
+            done = data.accumulate_device_series(stream, nbytes, L, std::min(max_spectra, cap_rows), out);
+        } else {
+            std::vector<double> rows;
+            done = data.accumulate_series(stream, nbytes, L, std::min(max_spectra, cap_rows), rows);
+            std::memcpy(out, rows.data(), sizeof(double) * rows.size());
+        }
+        if (launches) *launches = data.series_launches();
+        return done;
+    } catch (RPFexception& e) {
+        copy_out(e.what(), msg, cap);
+        return -static_cast<long long>(e.returnValue());
+    }
 }
 
 void rpf_host_synthetic(unsigned long long seed, unsigned long long first, unsigned long long n, unsigned char* out)

@@ -53,6 +53,7 @@ struct Options : Params {
     uint64_t synthetic_seed = 2;
     std::vector<int> devices;        // --gpus a,b,... (else the single --gpu ordinal)
     std::string reduce;              // --reduce rccl|host ("" = rccl if it loads, else host)
+    int64_t series_frames = 0;       // --series <frames>: spectrogram of the replay, one spectrum per <frames> frames (0 = off)
     bool show_help = false, show_version = false;
 };
 

@@ -15,6 +15,8 @@
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
+#include <cstdio>
+#include <cstring>
 #include <ctime>
 #include <fstream>
 #include <iostream>
@@ -344,6 +346,65 @@ private:
     int64_t hops_written_ = 0;
 };
 
+// --series <frames>: the replay cut into consecutive integrations of <frames> frames (rpf_accumulate_series), one text
+// block per integration -- what `-c -n <frames> --input` writes, block for block, without an acquisition per block.
+// The file is read in pieces of whole spectra (64 MB, or one spectrum if that is larger); with overlapped frames the
+// bytes a piece's last frames share with the next piece's first are carried over.
+int run_series(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
+{
+    Datastore data(options, aux.window_values);
+    std::FILE* file = options.input_file == "-" ? stdin : std::fopen(options.input_file.c_str(), "rb");
+    if (!file) throw RPFexception("Could not open " + options.input_file + ".", ReturnValue::InvalidInput);
+    struct CloseOnExit {
+        std::FILE* f;
+        ~CloseOnExit() { if (f != stdin) std::fclose(f); }
+    } close_file{file};
+    const int64_t L = options.series_frames;
+    const int64_t b = options.sample_bytes();
+    const int64_t frame = b * options.N, pitch = b * options.step();
+    const int64_t piece_budget = static_cast<int64_t>(64) << 20;
+    const int64_t fit = piece_budget < frame ? 0 : ((piece_budget - frame) / pitch + 1) / L;
+    const int64_t per_piece = std::max<int64_t>(1, fit);
+    std::vector<uint8_t> bytes(static_cast<size_t>(options.frame_span(per_piece * L)));
+    const std::vector<double>* baseline = options.baseline ? &aux.baseline_values : nullptr;
+    std::vector<double> rows, pwr(options.N);
+    size_t have = 0;
+    int64_t written = 0;
+    bool ended = false;
+    set_CtrlC_handler(true);
+    while (!checkInterrupt(InterruptState::FinishNow)) {
+        const std::string start_stamp = Acquisition::utc_now();
+        while (!ended && have < bytes.size()) {
+            const size_t got = std::fread(bytes.data() + have, 1, bytes.size() - have, file);
+            if (got == 0) ended = true;
+            have += got;
+        }
+        const int64_t done = data.accumulate_series(bytes.data(), have, L, per_piece, rows);
+        if (done == 0) break;
+        const std::string end_stamp = Acquisition::utc_now();
+        for (int64_t k = 0; k < done; ++k) {
+            std::copy(rows.begin() + static_cast<size_t>(k) * options.N, rows.begin() + static_cast<size_t>(k + 1) * options.N,
+                      pwr.begin());
+            write_text_header(std::cout, start_stamp, end_stamp);
+            write_spectrum_text(std::cout, pwr, options.N, L, tuned_freq, actual_samplerate, options.linear, baseline);
+            std::cout << std::endl;          // (the blank line that closes a pass of -c)
+        }
+        written += done;
+        const size_t used = static_cast<size_t>(done * L * pitch);      // the next spectrum starts here
+        std::memmove(bytes.data(), bytes.data() + used, have - used);
+        have -= used;
+        if (ended && static_cast<int64_t>(have) < options.frame_span(L)) break;
+    }
+    if (chatty(options)) {
+        std::cerr << "Spectra written: " << written << ", " << L << " frames each ("
+                  << (data.series_launches() == 1 ? "one launch per piece" : "one launch per spectrum") << ")" << std::endl;
+        print_acquisition_summary(options.N, written * L, 0, 0, actual_samplerate);
+    }
+    if (written == 0)
+        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+    return 0;
+}
+
 int run(int argc, char** argv)
 {
     Options options = parse_command_line(argc, argv);
@@ -392,6 +453,8 @@ int run(int argc, char** argv)
 
     Plan plan(options, actual_samplerate);
     plan.print();
+
+    if (options.series_frames > 0) return run_series(options, aux, actual_samplerate, source->frequency());
 
     const bool multi = options.devices.size() > 1;
     std::unique_ptr<Datastore> data;                 // after Plan fixed N / repeats / buf_length
