@@ -1,10 +1,14 @@
-// k1_kernels.h -- the K1 kernel templates (fused unpack -> FFT -> |X|^2, rpf_kernels.hip's header comment) and their
-// dispatch table entry, shared by the translation units that instantiate them: rpf_kernels.hip (unsigned 8-bit
-// samples, the default) and rpf_kernels_formats.hip (signed 8- and 16-bit samples).  Device code only.
+// k1_kernels.h -- the K1 kernel templates (fused unpack -> FFT -> |X|^2, rpf_kernels.hip's header comment), their
+// dispatch table entry and its builder over the size table (k1_sizes.h), shared by the translation units that
+// instantiate them (the list is at Variant, below).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
+#include <utility>
+
+#include "k1_sizes.h"
 #include "rpf_device_common.h"
 #include "rpf_kernels.h"
 #include "series_partition.h"
@@ -212,50 +216,115 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_series_kernel(const cf* __r
 using SingleFn = void (*)(const uint8_t*, long, const cf*, const float*, double*);
 using ScanFn = void (*)(const cf*, const float*, double*, const HopArgs);
 using StridedFn = void (*)(const uint8_t*, long, long, const cf*, const float*, double*);
+using SeriesFn = void (*)(const cf*, const float*, double*, const SeriesArgs);
 
+// One geometry of one size and the kernels instantiated for it, each as [window][dma]; a unit leaves the kernels it
+// does not instantiate null (K1Kernels).
 struct Variant {
-    int N, vid, P, WG, fpw, lds_bytes;
+    int N, vid, P;
+    K1Geometry geo;
     bool partial_f32;
-    SingleFn single[2][2];   // [window][dma]: one acquisition per launch
+    SingleFn single[2][2];   // one acquisition per launch
     ScanFn scan[2][2];       // several hops per launch
     StridedFn strided[2][2]; // one acquisition of overlapped frames (frame pitch a kernel argument)
+    SeriesFn series[2][2];   // a uniform series of spectra per launch
 };
 
-// The instantiations for the signed sample formats (rpf_kernels_formats.hip): variant 0 of every K1 size, or null.
-const Variant* find_format_variant(int N, int fmt);
-// The instantiations with per-bin statistics (rpf_kernels_stats.hip: cu8; rpf_kernels_stats_formats.hip: cs8, cs16):
-// variant 0 of every K1 size, the single-acquisition and strided kernels only (scan entries null), or null.
-const Variant* find_stats_variant(int N, int fmt);
-const Variant* find_stats_format_variant(int N, int fmt);
+// Variant 0 of every K1 size, one finder per translation unit so that the units compile side by side; each answers
+// for its own sample formats and returns null for the others.  find_variant (rpf_kernels.hip) is the one entry the
+// launch code uses and picks among the first four; the series kernels are looked up where they are launched.
+//   k1_variant              rpf_kernels.hip                cu8        single, scan, strided
+//   k1_format_variant       rpf_kernels_formats.hip        cs8, cs16  single, scan, strided
+//   k1_stats_variant        rpf_kernels_stats.hip          cu8        single, strided with per-bin statistics
+//   k1_stats_format_variant rpf_kernels_stats_formats.hip  cs8, cs16  single, strided with per-bin statistics
+//   k1_series_variant       rpf_kernels_series.hip         all three  series
+const Variant* k1_variant(int N, int fmt);
+const Variant* k1_format_variant(int N, int fmt);
+const Variant* k1_stats_variant(int N, int fmt);
+const Variant* k1_stats_format_variant(int N, int fmt);
+const Variant* k1_series_variant(int N, int fmt);
+
+// The resident grid of kernels that share one launch geometry on `device`: for each kernel (null entries skipped) the
+// dynamic-LDS attribute is set and its occupancy asked; *grid = max(the smallest, 1) x CUs.  rpf_kernels.hip.
+hipError_t plan_resident_grid(std::initializer_list<const void*> kernels, const K1Geometry& geo, int device, int* grid);
+
+// What a plan or a launch reports (li may be null).  `slots` is not K1's to set; the Bluestein record has no
+// partial_f32 and leaves it alone.
+inline void fill_info(LaunchInfo* li, const K1Geometry& geo, int grid)
+{
+    if (!li) return;
+    li->grid = grid;
+    li->block = geo.WG;
+    li->fpw = geo.fpw;
+    li->lds_bytes = geo.lds_bytes;
+}
+inline void fill_info(LaunchInfo* li, const Variant& v, int grid)
+{
+    fill_info(li, v.geo, grid);
+    if (li) li->partial_f32 = v.partial_f32;
+}
 
 namespace {
 
+// The kernels a Variant names: kK1Plain single, scan and strided; kK1Stats single and strided with STATS (a scan of
+// a stats engine runs hop by hop); kK1Series the series kernel alone, with the geometry of the size's scan kernel.
+enum K1Kernels { kK1Plain, kK1Stats, kK1Series };
 
-// OCC (OCCW for the windowed kernels) = waves per SIMD the register budget
-// must admit (= resident workgroups per CU x WG/256).  vid = tuning variant
-// (0 = the default for this N).
+// the [window][dma] instantiations of one kernel template; the arguments are its template arguments after TWLDS
+#define RPF_K1_FORMS(KERNEL, ...)                                                             \
+    {{KERNEL<G, WG, OCC, false, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, __VA_ARGS__>,       \
+      KERNEL<G, WG, OCC, false, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, __VA_ARGS__>},       \
+     {KERNEL<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, __VA_ARGS__>,      \
+      KERNEL<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, __VA_ARGS__>}}
+
+// The template arguments are K1Size's (k1_sizes.h) and the kernels' (above).  vid = tuning variant (0 = the default
+// for this N).
 template <int N, int P, int OCC, int OCCW = OCC, bool DBUF = false, int ACCB = 0, bool PF32 = false,
-          int RAWD = 2, int ABL = 0, bool TWLDS = false, int WGO = 0, int FMT = kFmtCu8>
+          int RAWD = 2, int ABL = 0, bool TWLDS = false, int WGO = 0, int FMT = kFmtCu8, bool TWLDSW = TWLDS,
+          K1Kernels KERNELS = kK1Plain>
 Variant make_variant(int vid)
 {
     using G = Geom<N, P>;
-    constexpr int WG = WGO ? WGO : (G::T >= 256 ? G::T : 256);   // WGO: several frames per workgroup
-    constexpr int FPW = WG / G::T;
-    constexpr int LDS = FPW * ((DBUF ? 2 : 1) * G::LDS_CPX * (int)sizeof(cf) + RAWD * sample_bytes_of(FMT) * N) +
-                        (TWLDS ? twlds_entries<G>() * (int)sizeof(cf) : 0);
-    return Variant{N, vid, P, WG, FPW, LDS, PF32,
-                   {{fft_accum_kernel<G, WG, OCC, false, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>,
-                     fft_accum_kernel<G, WG, OCC, false, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>},
-                    {fft_accum_kernel<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>,
-                     fft_accum_kernel<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>}},
-                   {{fft_accum_scan_kernel<G, WG, OCC, false, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>,
-                     fft_accum_scan_kernel<G, WG, OCC, false, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>},
-                    {fft_accum_scan_kernel<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>,
-                     fft_accum_scan_kernel<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>}},
-                   {{fft_accum_strided_kernel<G, WG, OCC, false, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>,
-                     fft_accum_strided_kernel<G, WG, OCC, false, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>},
-                    {fft_accum_strided_kernel<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>,
-                     fft_accum_strided_kernel<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT>}}};
+    constexpr K1Geometry geo = k1_geometry<G>(WGO, DBUF ? 2 : 1, RAWD, FMT, TWLDS || TWLDSW);
+    constexpr int WG = geo.WG;
+    if constexpr (KERNELS == kK1Series)
+        return Variant{N, vid, P, geo, PF32, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_kernel, FMT)};
+    else if constexpr (KERNELS == kK1Stats)
+        return Variant{N, vid, P, geo, PF32, RPF_K1_FORMS(fft_accum_kernel, FMT, true), {},
+                       RPF_K1_FORMS(fft_accum_strided_kernel, FMT, true), {}};
+    else
+        return Variant{N, vid, P, geo, PF32, RPF_K1_FORMS(fft_accum_kernel, FMT, false),
+                       RPF_K1_FORMS(fft_accum_scan_kernel, FMT), RPF_K1_FORMS(fft_accum_strided_kernel, FMT, false), {}};
+}
+#undef RPF_K1_FORMS
+
+// Variant 0 of every row of the size table for one sample format and one set of kernels, and its look-up by N.
+template <K1Kernels KERNELS, int FMT, int I>
+Variant default_variant()
+{
+    constexpr K1Size s = k1_size(I, FMT, KERNELS == kK1Stats);
+    return make_variant<s.N, s.P, s.OCC, s.OCCW, false, 0, false, s.RAWD, 0, s.TWLDS, s.WGO, FMT, s.TWLDSW, KERNELS>(0);
+}
+template <K1Kernels KERNELS, int FMT, int... I>
+const Variant* find_default_variant(int N, std::integer_sequence<int, I...>)
+{
+    static const Variant table[] = {default_variant<KERNELS, FMT, I>()...};
+    for (const Variant& v : table)
+        if (v.N == N) return &v;
+    return nullptr;
+}
+template <K1Kernels KERNELS, int FMT>
+const Variant* find_default_variant(int N)
+{
+    return find_default_variant<KERNELS, FMT>(N, std::make_integer_sequence<int, kK1SizeCount>{});
+}
+// ... for the two signed formats, which share a unit wherever they are instantiated
+template <K1Kernels KERNELS>
+const Variant* find_signed_variant(int N, int fmt)
+{
+    return fmt == kFmtCs8    ? find_default_variant<KERNELS, kFmtCs8>(N)
+           : fmt == kFmtCs16 ? find_default_variant<KERNELS, kFmtCs16>(N)
+                             : nullptr;
 }
 
 }  // namespace

@@ -1,0 +1,88 @@
+// k1_sizes.h -- K1's per-size geometry, stated once.  Every translation unit that instantiates K1 kernels
+// (rpf_kernels.hip, rpf_kernels_formats.hip, rpf_kernels_stats*.hip, rpf_kernels_series.hip) builds its table of
+// variant 0 from this list (k1_kernels.h, find_default_variant); only the tuning build's experiments (k1_tuning.inc)
+// name geometries of their own.
+#pragma once
+
+#include "fft_core.h"
+#include "rpf_device_common.h"
+
+namespace rpf {
+
+// P      points per lane: a frame is owned by T = N / P threads
+// OCC    waves per SIMD the register budget must admit (= resident workgroups per CU x WG / 256); OCCW: windowed kernels
+// RAWD   depth of the raw-byte ring = iterations staged ahead (k1_kernels.h); kRingSmall: by sample format, below
+// TWLDS  the twiddles of the passes after the first in an LDS table instead of registers; TWLDSW: windowed kernels
+//        (k1_size sets it: TWLDS, but for one statistics kernel)
+// WGO    workgroup size; 0 = max(T, 256).  A larger one runs more frames side by side.
+struct K1Size {
+    int N, P, OCC, OCCW, RAWD;
+    bool TWLDS;
+    int WGO;
+    bool TWLDSW = false;
+};
+
+constexpr int kRingSmall = 0;
+
+constexpr K1Size kK1Sizes[] = {
+    //  N   P  OCC OCCW  RAWD      TWLDS  WGO
+    {64, 8, 4, 4, kRingSmall, false, 0},
+    // 128 = 16 x 8 and 256 = 16 x 16: two passes and ONE exchange at 16 points per lane (measured
+    // 12-14 % faster than 8 x 8 x 2 / 8 x 8 x 4 -- the LDS stores are what costs)
+    {128, 16, 3, 3, kRingSmall, false, 0},
+    {256, 16, 3, 3, kRingSmall, false, 0},
+    {512, 8, 4, 4, 2, false, 0},
+    {1024, 16, 3, 2, 2, true, 0},
+    // 2048/4096: one 512-thread workgroup per CU (4 / 2 frames side by side): as fast as three
+    // 256-thread workgroups (the kernel is VALU-bound at 8 waves) and a third of the partials.
+    {2048, 16, 2, 2, 2, true, 512},
+    {4096, 16, 2, 2, 2, true, 512},
+    {8192, 16, 2, 2, 2, false, 0},
+};
+constexpr int kK1SizeCount = sizeof(kK1Sizes) / sizeof(kK1Sizes[0]);
+
+// kRingSmall, the tiny frames of N <= 256: four frames in flight with 2-byte samples, two with cs16's 4-byte samples
+// -- the same bytes in flight and the same LDS, so the same occupancy.  Everywhere else every format keeps two, and
+// cs16's LDS grows by 4N per frame slot (N = 8192: 68 KB slab + 64 KB ring of the CU's 160 KB, one workgroup per CU
+// as with cu8).
+constexpr int ring_depth(int rawd, int fmt) { return rawd != kRingSmall ? rawd : fmt == kFmtCs16 ? 2 : 4; }
+
+// Row i as the kernels of sample format `fmt` take it; stats: the kernels with per-bin statistics
+// (RPF_FLAG_BIN_STATS), which depart from the table where the registers run out.  Three double accumulators per bin
+// are 6 P registers (96 at P = 16) beside the frame, the twiddles and the window: the sizes whose plain twins run at
+// three waves per SIMD (168 registers) take two here (256), and no instantiation spills
+// (profiles/spectral_stats_resources.txt): windowed 512 takes three waves instead of four, and windowed 8192, whose
+// 512-thread workgroup cannot have more than 256 registers per lane, reads the twiddles of passes 2 and 3 from an LDS
+// table (4 KB more LDS for both window forms of that size).  Slab, ring and workgroup are the plain kernels'.
+constexpr K1Size k1_size(int i, int fmt, bool stats)
+{
+    K1Size s = kK1Sizes[i];
+    s.RAWD = ring_depth(s.RAWD, fmt);
+    s.TWLDSW = s.TWLDS;
+    if (stats) {
+        if (s.N == 128 || s.N == 256 || s.N == 1024) s.OCC = s.OCCW = 2;
+        if (s.N == 512) s.OCCW = 3;
+        if (s.N == 8192) s.TWLDSW = true;
+    }
+    return s;
+}
+
+// What the host needs to launch a K1-shaped kernel: workgroup size, frames side by side in it, dynamic LDS.
+struct K1Geometry {
+    int WG, fpw, lds_bytes;
+};
+
+// G: the frame's Geom; wgo: K1Size::WGO; per frame slot `slabs` exchange slabs (2: double-buffered) and a raw ring
+// of `rawd` frames of format `fmt` (0: no ring, the Bluestein kernel); twtable: the LDS twiddle table, one per
+// workgroup.  The kernels index LDS by the same compile-time quantities (k1_body.inc).
+template <class G>
+constexpr K1Geometry k1_geometry(int wgo, int slabs, int rawd, int fmt, bool twtable)
+{
+    const int wg = wgo ? wgo : (G::T >= 256 ? G::T : 256);
+    const int fpw = wg / G::T;
+    return K1Geometry{wg, fpw,
+                      fpw * (slabs * G::LDS_CPX * static_cast<int>(sizeof(cf)) + rawd * sample_bytes_of(fmt) * G::N) +
+                          (twtable ? twlds_entries<G>() * static_cast<int>(sizeof(cf)) : 0)};
+}
+
+}  // namespace rpf

@@ -3,59 +3,11 @@
 // {cu8, cs8, cs16}, with the geometry of the size's scan-kernel entry, and the fix-up kernel that adds the segments of
 // the spectra a workgroup boundary cuts.  A translation unit of its own: it compiles beside the others and none of
 // their kernels moves.
-#include <algorithm>
-
 #include "k1_kernels.h"
 
 namespace rpf {
 
 namespace {
-
-using SeriesFn = void (*)(const cf*, const float*, double*, const SeriesArgs);
-
-struct SeriesVariant {
-    int N, WG, fpw, lds_bytes;
-    SeriesFn fn[2][2];       // [window][dma]
-};
-
-template <int N, int P, int OCC, int OCCW, int RAWD, bool TWLDS, int WGO, int FMT>
-SeriesVariant make_series()
-{
-    using G = Geom<N, P>;
-    constexpr int WG = WGO ? WGO : (G::T >= 256 ? G::T : 256);
-    constexpr int FPW = WG / G::T;
-    constexpr int LDS = FPW * (G::LDS_CPX * (int)sizeof(cf) + RAWD * sample_bytes_of(FMT) * N) +
-                        (TWLDS ? twlds_entries<G>() * (int)sizeof(cf) : 0);
-    return SeriesVariant{N, WG, FPW, LDS,
-                         {{fft_accum_series_kernel<G, WG, OCC, false, false, false, 0, false, RAWD, 0, TWLDS, FMT>,
-                           fft_accum_series_kernel<G, WG, OCC, false, true, false, 0, false, RAWD, 0, TWLDS, FMT>},
-                          {fft_accum_series_kernel<G, WG, OCCW, true, false, false, 0, false, RAWD, 0, TWLDS, FMT>,
-                           fft_accum_series_kernel<G, WG, OCCW, true, true, false, 0, false, RAWD, 0, TWLDS, FMT>}}};
-}
-
-template <int FMT>
-const SeriesVariant* find_in_table(int N)
-{
-    constexpr int R = FMT == kFmtCs16 ? 2 : 4;     // ring depth of the three smallest sizes (rpf_kernels_formats.hip)
-    // Template arguments after <N, P>: OCC, OCCW, RAWD, TWLDS, WGO, FMT -- the defaults of rpf_kernels.hip's kVariants
-    static const SeriesVariant table[] = {
-        make_series<64, 8, 4, 4, R, false, 0, FMT>(),       make_series<128, 16, 3, 3, R, false, 0, FMT>(),
-        make_series<256, 16, 3, 3, R, false, 0, FMT>(),     make_series<512, 8, 4, 4, 2, false, 0, FMT>(),
-        make_series<1024, 16, 3, 2, 2, true, 0, FMT>(),     make_series<2048, 16, 2, 2, 2, true, 512, FMT>(),
-        make_series<4096, 16, 2, 2, 2, true, 512, FMT>(),   make_series<8192, 16, 2, 2, 2, false, 0, FMT>(),
-    };
-    for (const SeriesVariant& v : table)
-        if (v.N == N) return &v;
-    return nullptr;
-}
-
-const SeriesVariant* find_series(int N, int fmt)
-{
-    return fmt == kFmtCu8    ? find_in_table<kFmtCu8>(N)
-           : fmt == kFmtCs8  ? find_in_table<kFmtCs8>(N)
-           : fmt == kFmtCs16 ? find_in_table<kFmtCs16>(N)
-                             : nullptr;
-}
 
 // The spectra that a workgroup boundary cuts.  blockIdx.y + 1 = b, the boundary between workgroups b - 1 and b (at
 // iteration lo_b); it lies inside spectrum k = lo_b / ips unless lo_b is that spectrum's first iteration.  The block of
@@ -105,30 +57,24 @@ __global__ __launch_bounds__(PAIRS* GROUPS) void series_fixup_kernel(const doubl
 
 }  // namespace
 
-bool series_supported(int N, int fmt) { return find_series(N, fmt) != nullptr; }
+const Variant* k1_series_variant(int N, int fmt)
+{
+    return fmt == kFmtCu8 ? find_default_variant<kK1Series, kFmtCu8>(N) : find_signed_variant<kK1Series>(N, fmt);
+}
+
+bool series_supported(int N, int fmt) { return k1_series_variant(N, fmt) != nullptr; }
 
 hipError_t plan_series(int N, bool window, int device, LaunchInfo* li, int fmt)
 {
-    const SeriesVariant* v = find_series(N, fmt);
+    const Variant* v = k1_series_variant(N, fmt);
     if (!v) return hipErrorInvalidValue;
-    int per_cu = 1 << 30;
-    for (int d = 0; d < 2; ++d) {             // the two staging forms share one grid
-        const void* fn = reinterpret_cast<const void*>(v->fn[window ? 1 : 0][d]);
-        hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, v->lds_bytes);
-        if (err != hipSuccess) return err;
-        int n = 0;
-        err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, v->WG, v->lds_bytes);
-        if (err != hipSuccess) return err;
-        per_cu = std::min(per_cu, n);
-    }
-    hipDeviceProp_t prop;
-    hipError_t err = hipGetDeviceProperties(&prop, device);
+    const int w = window ? 1 : 0;
+    int grid = 0;
+    // the two staging forms share one grid
+    hipError_t err = plan_resident_grid({reinterpret_cast<const void*>(v->series[w][0]),
+                                         reinterpret_cast<const void*>(v->series[w][1])}, v->geo, device, &grid);
     if (err != hipSuccess) return err;
-    li->grid = std::max(per_cu, 1) * prop.multiProcessorCount;
-    li->block = v->WG;
-    li->fpw = v->fpw;
-    li->lds_bytes = v->lds_bytes;
-    li->partial_f32 = false;
+    fill_info(li, *v, grid);
     return hipSuccess;
 }
 
@@ -136,17 +82,11 @@ hipError_t launch_fft_accum_series(int N, bool window, bool use_dma, const Serie
                                    const float* d_window, double* d_partial, int grid, hipStream_t stream,
                                    LaunchInfo* li, int fmt)
 {
-    const SeriesVariant* v = find_series(N, fmt);
+    const Variant* v = k1_series_variant(N, fmt);
     if (!v || grid < 1 || grid > args.total || args.K < 1 || !args.stream || !args.out) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(v->fn[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->WG), v->lds_bytes, stream, d_twiddles,
-                       d_window, d_partial, args);
-    if (li) {
-        li->grid = grid;
-        li->block = v->WG;
-        li->fpw = v->fpw;
-        li->lds_bytes = v->lds_bytes;
-        li->partial_f32 = false;
-    }
+    hipLaunchKernelGGL(v->series[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->geo.WG), v->geo.lds_bytes, stream,
+                       d_twiddles, d_window, d_partial, args);
+    fill_info(li, *v, grid);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess || grid < 2) return err;       // one workgroup: every spectrum is complete
     constexpr int PAIRS = 8, GROUPS = 16;

@@ -1,7 +1,7 @@
-// rpf_kernels_stats.hip -- K1 with per-bin statistics (k1_stats_table.h) for unsigned 8-bit samples, and the
-// look-up of all three formats.  A translation unit of its own, as rpf_kernels_formats.hip: the plain kernels of
-// rpf_kernels.hip are not compiled here and do not change.
-#include "k1_stats_table.h"
+// rpf_kernels_stats.hip -- K1 with per-bin statistics (k1_kernels.h, kK1Stats) for unsigned 8-bit samples, and K3 for
+// the statistics.  A translation unit of its own, as rpf_kernels_formats.hip: the plain kernels of rpf_kernels.hip are
+// not compiled here and do not change.
+#include "k1_kernels.h"
 
 namespace rpf {
 
@@ -70,9 +70,9 @@ hipError_t launch_reduce_stats(const double* d_partial, int nslots, int N, doubl
     return hipGetLastError();
 }
 
-const Variant* find_stats_variant(int N, int fmt)
+const Variant* k1_stats_variant(int N, int fmt)
 {
-    return fmt == kFmtCu8 ? find_in_stats_table<kFmtCu8>(N) : find_stats_format_variant(N, fmt);
+    return fmt == kFmtCu8 ? find_default_variant<kK1Stats, kFmtCu8>(N) : nullptr;
 }
 
 }  // namespace rpf
