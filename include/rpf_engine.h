@@ -270,7 +270,7 @@ int rpf_max_hops_per_launch(void);
  * writes for that slice of the stream (a fused four-step launch that gives up NaN-fills its own row), correct at every
  * size and fast at none.  rpf_series_launches tells the two apart.
  * RPF_ERR_INVALID_ARGUMENT: frames_per_spectrum < 1, max_spectra < 0, a misaligned stream or output, an engine created
- * with RPF_FLAG_BIN_STATS (time-resolved statistics are not built). */
+ * with RPF_FLAG_BIN_STATS (its series entry is rpf_accumulate_device_series_stats, below). */
 int rpf_accumulate_device_series(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
                                  int64_t max_spectra, double* d_out /* K x N */, void* hip_stream, int64_t* spectra_done);
 /* The same calculation on a host stream, the counterpart of rpf_accumulate -- but not through the buffer queues: the
@@ -281,7 +281,28 @@ int rpf_accumulate_device_series(rpf_engine* e, const void* d_stream, size_t nby
  * returns.  Not while an acquisition is running. */
 int rpf_accumulate_series(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
                           int64_t max_spectra, double* out /* K x N, host */, int64_t* spectra_done);
-/* Transform-kernel launches the engine's last series call enqueued: 1 on the one-launch path (whatever K is), K on the
+/* Time-resolved statistics: the series of an engine created with RPF_FLAG_BIN_STATS.  L, max_spectra, K, the frame
+ * count and the dropped tail are those of rpf_accumulate_device_series; for every spectrum k the three planes
+ * RPF_FLAG_BIN_STATS defines, over its L frames: row k = d_out[k 3N .. k 3N + 3N) = S1[N], S2[N], PK[N] (device doubles,
+ * 16-byte aligned), bin N/2 = DC -- what rpf_accumulate_device_stats writes for that slice of the stream.  PK starts
+ * from 0 in every row.  Rows < K are overwritten, rows >= K are not touched; K = 0 is RPF_OK and launches nothing.
+ * SK of row k is the estimator above with M = L.
+ * Powers of two 64 .. 8192, frame step N, all three formats, windowed or not, either staging: ONE persistent launch,
+ * the series kernel with two more register accumulators per bin; a spectrum cut by a workgroup boundary leaves three
+ * planes per segment and the fix-up launch adds S1 and S2 in workgroup order and takes the maximum of PK.  S1 is
+ * computed by the operations of rpf_accumulate_device_series, in the same order for the same grid.  Every other engine
+ * -- another size, frame step S != N, RPF_FLAG_CATCH_ALL -- runs spectrum by spectrum through
+ * rpf_accumulate_device_stats' path, bit for bit.  rpf_series_launches tells the two apart.
+ * RPF_ERR_INVALID_ARGUMENT: an engine created without RPF_FLAG_BIN_STATS, and what rpf_accumulate_device_series refuses. */
+int rpf_accumulate_device_series_stats(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
+                                       int64_t max_spectra, double* d_out /* K x 3 x N */, void* hip_stream,
+                                       int64_t* spectra_done);
+/* The same on a host stream, as rpf_accumulate_series: bounded pieces of whole spectra through engine-owned device
+ * memory, not through the buffer queues; pwr, S2, PK and repeats_done of the engine are not touched.  Synchronises
+ * before it returns.  Not while an acquisition is running. */
+int rpf_accumulate_series_stats(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
+                                int64_t max_spectra, double* out /* K x 3 x N, host */, int64_t* spectra_done);
+/* Transform-kernel launches the engine's last series call (either kind) enqueued: 1 on the one-launch path (whatever K is), K on the
  * spectrum-by-spectrum path, summed over the pieces of rpf_accumulate_series; 0 before any series call and for K = 0.
  * rpf_last_launch_info reports the geometry of the last of them. */
 int rpf_series_launches(const rpf_engine* e);

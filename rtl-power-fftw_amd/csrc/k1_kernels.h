@@ -189,7 +189,7 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_scan_kernel(const cf* __res
                                                             double* __restrict__ partial,
                                                             const HopArgs hops)
 {
-    constexpr bool SERIES = false;
+    constexpr bool SERIES = false, STATS = false;
     using TABLE = HopLanes;
 #include "k1_scan_body.inc"
 }
@@ -206,7 +206,23 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_series_kernel(const cf* __r
                                                               double* __restrict__ partial,
                                                               const SeriesArgs hops)
 {
-    constexpr bool SERIES = true;
+    constexpr bool SERIES = true, STATS = false;
+    using TABLE = SeriesTable;
+#include "k1_scan_body.inc"
+}
+
+// The series kernel with per-bin statistics (rpf_accumulate_device_series_stats): S2 and PK accumulated beside the
+// power as in fft_accum_kernel's STATS form, zeroed at every spectrum; row k of hops.out and every partial slot are
+// three planes of N, S1, S2, PK, handed over one after the other.  A kernel of its own name, so that the plain series
+// kernels keep theirs.  Instantiated in rpf_kernels_series_stats.hip only.
+template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
+          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8>
+__global__ __launch_bounds__(WG, OCC) void fft_accum_series_stats_kernel(const cf* __restrict__ twN,
+                                                                    const float* __restrict__ window,
+                                                                    double* __restrict__ partial,
+                                                                    const SeriesArgs hops)
+{
+    constexpr bool SERIES = true, STATS = true;
     using TABLE = SeriesTable;
 #include "k1_scan_body.inc"
 }
@@ -227,7 +243,7 @@ struct Variant {
     SingleFn single[2][2];   // one acquisition per launch
     ScanFn scan[2][2];       // several hops per launch
     StridedFn strided[2][2]; // one acquisition of overlapped frames (frame pitch a kernel argument)
-    SeriesFn series[2][2];   // a uniform series of spectra per launch
+    SeriesFn series[2][2];   // a uniform series of spectra per launch (kK1SeriesStats: of three-plane statistics)
 };
 
 // Variant 0 of every K1 size, one finder per translation unit so that the units compile side by side; each answers
@@ -238,11 +254,13 @@ struct Variant {
 //   k1_stats_variant        rpf_kernels_stats.hip          cu8        single, strided with per-bin statistics
 //   k1_stats_format_variant rpf_kernels_stats_formats.hip  cs8, cs16  single, strided with per-bin statistics
 //   k1_series_variant       rpf_kernels_series.hip         all three  series
+//   k1_series_stats_variant rpf_kernels_series_stats.hip   all three  series with per-bin statistics
 const Variant* k1_variant(int N, int fmt);
 const Variant* k1_format_variant(int N, int fmt);
 const Variant* k1_stats_variant(int N, int fmt);
 const Variant* k1_stats_format_variant(int N, int fmt);
 const Variant* k1_series_variant(int N, int fmt);
+const Variant* k1_series_stats_variant(int N, int fmt);
 
 // The resident grid of kernels that share one launch geometry on `device`: for each kernel (null entries skipped) the
 // dynamic-LDS attribute is set and its occupancy asked; *grid = max(the smallest, 1) x CUs.  rpf_kernels.hip.
@@ -267,8 +285,9 @@ inline void fill_info(LaunchInfo* li, const Variant& v, int grid)
 namespace {
 
 // The kernels a Variant names: kK1Plain single, scan and strided; kK1Stats single and strided with STATS (a scan of
-// a stats engine runs hop by hop); kK1Series the series kernel alone, with the geometry of the size's scan kernel.
-enum K1Kernels { kK1Plain, kK1Stats, kK1Series };
+// a stats engine runs hop by hop); kK1Series the series kernel alone, with the geometry of the size's scan kernel;
+// kK1SeriesStats the series kernel with statistics alone, with the geometry of the size's statistics kernels.
+enum K1Kernels { kK1Plain, kK1Stats, kK1Series, kK1SeriesStats };
 
 // the [window][dma] instantiations of one kernel template; the arguments are its template arguments after TWLDS
 #define RPF_K1_FORMS(KERNEL, ...)                                                             \
@@ -289,6 +308,8 @@ Variant make_variant(int vid)
     constexpr int WG = geo.WG;
     if constexpr (KERNELS == kK1Series)
         return Variant{N, vid, P, geo, PF32, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_kernel, FMT)};
+    else if constexpr (KERNELS == kK1SeriesStats)
+        return Variant{N, vid, P, geo, PF32, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_stats_kernel, FMT)};
     else if constexpr (KERNELS == kK1Stats)
         return Variant{N, vid, P, geo, PF32, RPF_K1_FORMS(fft_accum_kernel, FMT, true), {},
                        RPF_K1_FORMS(fft_accum_strided_kernel, FMT, true), {}};
@@ -302,7 +323,7 @@ Variant make_variant(int vid)
 template <K1Kernels KERNELS, int FMT, int I>
 Variant default_variant()
 {
-    constexpr K1Size s = k1_size(I, FMT, KERNELS == kK1Stats);
+    constexpr K1Size s = k1_size(I, FMT, KERNELS == kK1Stats || KERNELS == kK1SeriesStats);
     return make_variant<s.N, s.P, s.OCC, s.OCCW, false, 0, false, s.RAWD, 0, s.TWLDS, s.WGO, FMT, s.TWLDSW, KERNELS>(0);
 }
 template <K1Kernels KERNELS, int FMT, int... I>

@@ -5,7 +5,9 @@
 // TABLE::load takes and carries q, r and step.  An include rather than a force-inlined device function, as k1_body.inc:
 // the scan kernel compiles to the instruction stream it had before the series form existed (tools/kernel_streams.py).
 // What SERIES changes is where a segment goes (the hand-over below): a complete spectrum straight to its output row,
-// a cut one to partial slot 2w or 2w + 1.
+// a cut one to partial slot 2w or 2w + 1.  The includer also declares `constexpr bool STATS` (true in
+// fft_accum_series_stats_kernel alone): the per-bin statistics of k1_body.inc beside the power, and rows and slots of
+// three planes each.  With it false nothing below changes what the two other kernels compile to.
     constexpr int P = G::P, T = G::T, N = G::N, NPASS = G::NPASS;
     constexpr int FPW = WG / T;
     constexpr int NSLAB = DBUF ? 2 : 1;
@@ -93,6 +95,10 @@
     }
     double acc[P];
     float acc32[ACCB > 0 ? P : 1];
+    // STATS: the sum of the squared powers and the peak power of every bin beside acc (fft_core.h,
+    // phase_accumulate_stats), zeroed with it at every spectrum; the peak starts from 0, which no power is below.
+    static_assert(!STATS || (SERIES && ACCB == 0 && !PF32 && ABL == 0), "the statistics: series kernels only, no tuning paths");
+    double acc_s2[STATS ? P : 1], acc_pk[STATS ? P : 1];
 
     PhaseClock clk;
     clk.start();
@@ -107,6 +113,10 @@
         if constexpr (ACCB > 0) {
 #pragma unroll
             for (int a = 0; a < P; ++a) acc32[a] = 0.0f;
+        }
+        if constexpr (STATS) {
+#pragma unroll
+            for (int a = 0; a < P; ++a) acc_s2[a] = acc_pk[a] = 0.0;
         }
         int fb = (cur.j - cur.begin) * FPW;        // slot-0 frame of the iteration, within the hop
         for (int n = seg; n > 0; --n, ++it, fb += fstep) {
@@ -157,6 +167,8 @@
             } else if constexpr (ABL & 1) {
 #pragma unroll
                 for (int a = 0; a < P; ++a) asm volatile("" ::"v"(x[a]));
+            } else if constexpr (STATS) {
+                if (active) phase_accumulate_stats(x, acc, acc_s2, acc_pk, P);   // (an inactive slot leaves the peak alone)
             } else {
                 if (active) phase_accumulate(x, acc, P);
             }
@@ -180,46 +192,75 @@
         // stage addresses must not be hoisted into registers that live across the frame loop)
         int ft = t, ftid = tid, ffs = fs;
         asm volatile("" : "+v"(ft), "+v"(ftid), "+v"(ffs));
-#pragma unroll
-        for (int a = 0; a < P; ++a) {
-            const int bin = bin_of<G>(ft, a);
-            stage[ffs * SN + bin + (bin >> 4)] = acc[a];
-        }
-        exchange_sync<true>();
-        size_t slot = 0;
-        double* row = nullptr;           // SERIES: where this segment goes
-        if constexpr (SERIES) {
-            // (cur.j is still the segment's first iteration; first + it the one after its last)
-            static_assert(!PF32, "a series row is double");
+        if constexpr (STATS) {
+            // Three planes per row or slot, S1, S2, PK at p N: one after the other through the same staging area, the
+            // frame slots combined by +, +, max (stats_combine), plane 0 exactly as the plain hand-over below.
             const int w = static_cast<int>(blockIdx.x);
-            row = series_segment_complete(cur.j, first + it, cur.begin, cur.end)
-                      ? series_rows(hops) + static_cast<size_t>(cur.h) * N
-                      : partial + static_cast<size_t>(series_segment_slot(w, cur.j, cur.begin)) * N;
-        } else {
-            slot = static_cast<size_t>(tbl.slot_bias(cur.h) + static_cast<int>(blockIdx.x));
-        }
-        if constexpr (PF32) {
-            for (int bin = ftid; bin < N; bin += WG) {
-                double v = 0.0;
+            double* const row3 = series_segment_complete(cur.j, first + it, cur.begin, cur.end)
+                                     ? series_rows(hops) + static_cast<size_t>(cur.h) * (kStatsPlanes * N)
+                                     : partial + static_cast<size_t>(series_segment_slot(w, cur.j, cur.begin)) * (kStatsPlanes * N);
 #pragma unroll
-                for (int k = 0; k < FPW; ++k) v += stage[k * SN + bin + (bin >> 4)];
-                reinterpret_cast<float*>(partial)[slot * N + bin] = static_cast<float>(v);
+            for (int plane = 0; plane < kStatsPlanes; ++plane) {
+                if (plane > 0) exchange_sync<true>();     // every wave has read the previous plane
+                const double* const src = plane == 0 ? acc : plane == 1 ? acc_s2 : acc_pk;
+#pragma unroll
+                for (int a = 0; a < P; ++a) {
+                    const int bin = bin_of<G>(ft, a);
+                    stage[ffs * SN + bin + (bin >> 4)] = src[a];
+                }
+                exchange_sync<true>();
+                for (int bin = 2 * ftid; bin < N; bin += 2 * WG) {
+                    partial2_t v = {0.0, 0.0};
+#pragma unroll
+                    for (int k = 0; k < FPW; ++k) {
+                        v.x = stats_combine(plane, v.x, stage[k * SN + bin + (bin >> 4)]);
+                        v.y = stats_combine(plane, v.y, stage[k * SN + bin + 1 + (bin >> 4)]);
+                    }
+                    store_partial2(row3 + plane * N + bin, v);
+                }
             }
         } else {
-            // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
-            // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
-            // Written through (store_partial2), as K1's flush.
-            for (int bin = 2 * ftid; bin < N; bin += 2 * WG) {
-                partial2_t v = {0.0, 0.0};
 #pragma unroll
-                for (int k = 0; k < FPW; ++k) {
-                    v.x += stage[k * SN + bin + (bin >> 4)];
-                    v.y += stage[k * SN + bin + 1 + (bin >> 4)];
+            for (int a = 0; a < P; ++a) {
+                const int bin = bin_of<G>(ft, a);
+                stage[ffs * SN + bin + (bin >> 4)] = acc[a];
+            }
+            exchange_sync<true>();
+            size_t slot = 0;
+            double* row = nullptr;           // SERIES: where this segment goes
+            if constexpr (SERIES) {
+                // (cur.j is still the segment's first iteration; first + it the one after its last)
+                static_assert(!PF32, "a series row is double");
+                const int w = static_cast<int>(blockIdx.x);
+                row = series_segment_complete(cur.j, first + it, cur.begin, cur.end)
+                          ? series_rows(hops) + static_cast<size_t>(cur.h) * N
+                          : partial + static_cast<size_t>(series_segment_slot(w, cur.j, cur.begin)) * N;
+            } else {
+                slot = static_cast<size_t>(tbl.slot_bias(cur.h) + static_cast<int>(blockIdx.x));
+            }
+            if constexpr (PF32) {
+                for (int bin = ftid; bin < N; bin += WG) {
+                    double v = 0.0;
+#pragma unroll
+                    for (int k = 0; k < FPW; ++k) v += stage[k * SN + bin + (bin >> 4)];
+                    reinterpret_cast<float*>(partial)[slot * N + bin] = static_cast<float>(v);
                 }
-                if constexpr (SERIES)
-                    store_partial2(row + bin, v);
-                else
-                    store_partial2(partial + slot * N + bin, v);
+            } else {
+                // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
+                // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
+                // Written through (store_partial2), as K1's flush.
+                for (int bin = 2 * ftid; bin < N; bin += 2 * WG) {
+                    partial2_t v = {0.0, 0.0};
+#pragma unroll
+                    for (int k = 0; k < FPW; ++k) {
+                        v.x += stage[k * SN + bin + (bin >> 4)];
+                        v.y += stage[k * SN + bin + 1 + (bin >> 4)];
+                    }
+                    if constexpr (SERIES)
+                        store_partial2(row + bin, v);
+                    else
+                        store_partial2(partial + slot * N + bin, v);
+                }
             }
         }
         if (it >= count) break;

@@ -1,5 +1,5 @@
 // k1_sizes.h -- K1's per-size geometry, stated once.  Every translation unit that instantiates K1 kernels
-// (rpf_kernels.hip, rpf_kernels_formats.hip, rpf_kernels_stats*.hip, rpf_kernels_series.hip) builds its table of
+// (rpf_kernels.hip, rpf_kernels_formats.hip, rpf_kernels_stats*.hip, rpf_kernels_series*.hip) builds its table of
 // variant 0 from this list (k1_kernels.h, find_default_variant); only the tuning build's experiments (k1_tuning.inc)
 // name geometries of their own.
 #pragma once
@@ -54,6 +54,8 @@ constexpr int ring_depth(int rawd, int fmt) { return rawd != kRingSmall ? rawd :
 // (profiles/spectral_stats_resources.txt): windowed 512 takes three waves instead of four, and windowed 8192, whose
 // 512-thread workgroup cannot have more than 256 registers per lane, reads the twiddles of passes 2 and 3 from an LDS
 // table (4 KB more LDS for both window forms of that size).  Slab, ring and workgroup are the plain kernels'.
+// The series kernels with statistics (rpf_kernels_series_stats.hip) take the same departures and need no further one:
+// 102 .. 134 registers at P = 8, 208 .. 252 of 256 at P = 16, no scratch (profiles/series_stats_resources.txt).
 constexpr K1Size k1_size(int i, int fmt, bool stats)
 {
     K1Size s = kK1Sizes[i];

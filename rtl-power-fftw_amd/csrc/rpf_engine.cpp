@@ -152,14 +152,15 @@ struct rpf_engine {
     int last_slots = 0;                   // partial spectra left by the last transform
     rpf::SlotRanges last_ranges;          // ... and which of them belong to which hop (K1 hop launches)
     int last_hops = 0;                    // hops of the last rpf_device_fused_hops (0: a single-acquisition transform)
-    // series entries (rpf_accumulate_device_series, rpf_accumulate_series); all allocated at the first call that needs them
+    // series entries (rpf_accumulate_device_series[_stats], rpf_accumulate_series[_stats]; a stats engine's rows and
+    // slots are three planes); all allocated at the first call that needs them
     bool series_planned = false;
     rpf::LaunchInfo series_plan;          // the series kernel's resident grid
-    double* d_series_partial = nullptr;   // its scratch: 2 x grid x N doubles, whatever K is
+    double* d_series_partial = nullptr;   // its scratch: 2 x grid x N doubles (a stats engine's: x 3), whatever K is
     int series_launches = 0;              // transform-kernel launches of the last series call
     uint8_t* d_series_in = nullptr;       // rpf_accumulate_series: one piece of the host stream ...
     size_t series_in_bytes = 0;
-    double* d_series_out = nullptr;       // ... and its rows
+    double* d_series_out = nullptr;       // ... and its rows (N doubles each; a stats engine's 3 N)
     size_t series_out_rows = 0;
 
     mutable std::string last_error;
@@ -1612,17 +1613,21 @@ int rpf_device_fused_hops(rpf_engine* e, const void* const* d_streams, const siz
 // ---- spectrogram: consecutive L-frame spectra of one stream ----------------------------------------------------
 
 // The series kernel serves this engine: K1 (variant 0), frames side by side, and L small enough for its int frame index.
+// (A stats engine asks for the kernels with statistics; only the _series_stats entries get here on one.)
 static bool series_native(const rpf_engine* e, int64_t L)
 {
-    return is_k1(e) && !overlapped(e) && e->variant == 0 && !e->stats && L <= INT32_MAX - 64 &&
-           rpf::series_supported(e->N, e->format);
+    return is_k1(e) && !overlapped(e) && e->variant == 0 && L <= INT32_MAX - 64 &&
+           (e->stats ? rpf::series_stats_supported(e->N, e->format) : rpf::series_supported(e->N, e->format));
 }
 
+// want_stats: the _series_stats entries, which need the flag as the plain ones need its absence.
 static int series_check(rpf_engine* e, const char* who, const void* stream, size_t nbytes, int64_t L, int64_t max_spectra,
-                        const void* out)
+                        const void* out, bool want_stats = false)
 {
     if (!e || !out || (!stream && nbytes)) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
-    if (e->stats)
+    if (want_stats && !e->stats)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": the engine was created without RPF_FLAG_BIN_STATS");
+    if (!want_stats && e->stats)
         return fail(e, RPF_ERR_INVALID_ARGUMENT,
                     std::string(who) + ": not on an engine with RPF_FLAG_BIN_STATS (time-resolved statistics are not built)");
     if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": acquisition running");
@@ -1632,24 +1637,26 @@ static int series_check(rpf_engine* e, const char* who, const void* stream, size
 }
 
 // K spectra of L frames from d_stream into d_out on `s`; counts the transform launches into e->series_launches.
+// On a stats engine a row is three planes, S1, S2, PK (rpf_accumulate_device_series_stats).
 static int series_enqueue(rpf_engine* e, const uint8_t* d_stream, int64_t L, int64_t K, double* d_out, hipStream_t s)
 {
-    const size_t N = static_cast<size_t>(e->N);
+    const size_t row = static_cast<size_t>(e->N) * (e->stats ? rpf::kStatsPlanes : 1);       // doubles per row
     if (!series_native(e, L)) {
         // spectrum by spectrum through the engine's own single-acquisition path (any size, any frame step): spectrum k
         // starts at frame k L = byte k L bS
         const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
         for (int64_t k = 0; k < K; ++k) {
-            const int rc = launch_frames(e, d_stream + static_cast<size_t>(k) * hop, L, d_out + static_cast<size_t>(k) * N,
-                                         /*accumulate=*/false, s);
+            const int rc = launch_frames(e, d_stream + static_cast<size_t>(k) * hop, L, d_out + static_cast<size_t>(k) * row,
+                                         /*accumulate=*/false, s, nullptr, /*want_stats=*/e->stats);
             if (rc != RPF_OK) return rc;
             ++e->series_launches;
         }
         return RPF_OK;
     }
     if (!e->series_planned) {
-        HIP_TRY(e, rpf::plan_series(e->N, e->has_window, e->device, &e->series_plan, e->format));
-        HIP_TRY(e, hipMalloc(&e->d_series_partial, sizeof(double) * 2 * N * static_cast<size_t>(e->series_plan.grid)));
+        HIP_TRY(e, e->stats ? rpf::plan_series_stats(e->N, e->has_window, e->device, &e->series_plan, e->format)
+                            : rpf::plan_series(e->N, e->has_window, e->device, &e->series_plan, e->format));
+        HIP_TRY(e, hipMalloc(&e->d_series_partial, sizeof(double) * 2 * row * static_cast<size_t>(e->series_plan.grid)));
         e->series_planned = true;
     }
     const long frame_bytes = static_cast<long>(e->sample_bytes) * e->N;
@@ -1661,21 +1668,22 @@ static int series_enqueue(rpf_engine* e, const uint8_t* d_stream, int64_t L, int
         const int64_t kc = std::min(share, K - k0);
         rpf::SeriesArgs args;
         const int grid = rpf::partition_series(kc, L, e->series_plan.fpw, e->series_plan.grid, frame_bytes, &args);
-        if (grid < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_series: too many frames for one launch");
+        if (grid < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, "series: too many frames for one launch");
         args.stream = d_stream + static_cast<size_t>(k0) * static_cast<size_t>(args.spectrum_bytes);
-        args.out = d_out + static_cast<size_t>(k0) * N;
-        HIP_TRY(e, rpf::launch_fft_accum_series(e->N, e->has_window, dma, args, e->d_twiddles, e->d_window,
-                                                e->d_series_partial, grid, s, &e->last, e->format));
+        args.out = d_out + static_cast<size_t>(k0) * row;
+        HIP_TRY(e, (e->stats ? rpf::launch_fft_accum_series_stats : rpf::launch_fft_accum_series)(
+                       e->N, e->has_window, dma, args, e->d_twiddles, e->d_window, e->d_series_partial, grid, s, &e->last,
+                       e->format));
         ++e->series_launches;
     }
     return RPF_OK;
 }
 
-int rpf_accumulate_device_series(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
-                                 int64_t max_spectra, double* d_out, void* hip_stream, int64_t* spectra_done)
+static int series_device(rpf_engine* e, const char* who, bool want_stats, const void* d_stream, size_t nbytes,
+                         int64_t frames_per_spectrum, int64_t max_spectra, double* d_out, void* hip_stream,
+                         int64_t* spectra_done)
 {
-    const char* const who = "rpf_accumulate_device_series";
-    int rc = series_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out);
+    int rc = series_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out, want_stats);
     if (rc != RPF_OK) return rc;
     if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
         return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
@@ -1691,10 +1699,24 @@ int rpf_accumulate_device_series(rpf_engine* e, const void* d_stream, size_t nby
                           static_cast<hipStream_t>(hip_stream));
 }
 
-int rpf_accumulate_series(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
-                          int64_t max_spectra, double* out, int64_t* spectra_done)
+int rpf_accumulate_device_series(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
+                                 int64_t max_spectra, double* d_out, void* hip_stream, int64_t* spectra_done)
 {
-    int rc = series_check(e, "rpf_accumulate_series", stream, nbytes, frames_per_spectrum, max_spectra, out);
+    return series_device(e, "rpf_accumulate_device_series", false, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out,
+                         hip_stream, spectra_done);
+}
+
+int rpf_accumulate_device_series_stats(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
+                                       int64_t max_spectra, double* d_out, void* hip_stream, int64_t* spectra_done)
+{
+    return series_device(e, "rpf_accumulate_device_series_stats", true, d_stream, nbytes, frames_per_spectrum, max_spectra,
+                         d_out, hip_stream, spectra_done);
+}
+
+static int series_host(rpf_engine* e, const char* who, bool want_stats, const uint8_t* stream, size_t nbytes,
+                       int64_t frames_per_spectrum, int64_t max_spectra, double* out, int64_t* spectra_done)
+{
+    int rc = series_check(e, who, stream, nbytes, frames_per_spectrum, max_spectra, out, want_stats);
     if (rc != RPF_OK) return rc;
     e->series_launches = 0;
     const int64_t L = frames_per_spectrum;
@@ -1706,7 +1728,7 @@ int rpf_accumulate_series(rpf_engine* e, const uint8_t* stream, size_t nbytes, i
     // A piece = the whole number of spectra whose frames span at most kSeriesPiece bytes, at least one spectrum;
     // spectrum k starts at byte k L bS and p spectra span frame_span(p L) bytes.
     constexpr size_t kSeriesPiece = static_cast<size_t>(64) << 20;
-    const size_t N = static_cast<size_t>(e->N);
+    const size_t row = static_cast<size_t>(e->N) * (e->stats ? rpf::kStatsPlanes : 1);       // doubles per row
     const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
     const int64_t fit = frames_in(e, kSeriesPiece) / L;
     const int64_t per_piece = std::min(K, std::max<int64_t>(1, fit));
@@ -1724,7 +1746,7 @@ int rpf_accumulate_series(rpf_engine* e, const uint8_t* stream, size_t nbytes, i
         if (e->d_series_out) (void)hipFree(e->d_series_out);
         e->d_series_out = nullptr;
         e->series_out_rows = 0;
-        HIP_TRY(e, hipMalloc(&e->d_series_out, sizeof(double) * N * static_cast<size_t>(per_piece)));
+        HIP_TRY(e, hipMalloc(&e->d_series_out, sizeof(double) * row * static_cast<size_t>(per_piece)));
         e->series_out_rows = static_cast<size_t>(per_piece);
     }
     // (a stream pinned with rpf_stream_register is copied from where it lies, asynchronously; a pageable one through
@@ -1739,11 +1761,24 @@ int rpf_accumulate_series(rpf_engine* e, const uint8_t* stream, size_t nbytes, i
             (void)hipStreamSynchronize(s);
             return rc;
         }
-        HIP_TRY(e, hipMemcpyAsync(out + static_cast<size_t>(k0) * N, e->d_series_out, sizeof(double) * N * static_cast<size_t>(kc),
+        HIP_TRY(e, hipMemcpyAsync(out + static_cast<size_t>(k0) * row, e->d_series_out, sizeof(double) * row * static_cast<size_t>(kc),
                                   hipMemcpyDeviceToHost, s));
         HIP_TRY(e, hipStreamSynchronize(s));       // the piece's buffers are reused by the next one
     }
     return RPF_OK;
+}
+
+int rpf_accumulate_series(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
+                          int64_t max_spectra, double* out, int64_t* spectra_done)
+{
+    return series_host(e, "rpf_accumulate_series", false, stream, nbytes, frames_per_spectrum, max_spectra, out, spectra_done);
+}
+
+int rpf_accumulate_series_stats(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
+                                int64_t max_spectra, double* out, int64_t* spectra_done)
+{
+    return series_host(e, "rpf_accumulate_series_stats", true, stream, nbytes, frames_per_spectrum, max_spectra, out,
+                       spectra_done);
 }
 
 int rpf_series_launches(const rpf_engine* e) { return e ? e->series_launches : 0; }

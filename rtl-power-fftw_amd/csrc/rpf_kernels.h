@@ -71,6 +71,16 @@ hipError_t launch_fft_accum_series(int N, bool window, bool use_dma, const Serie
                                    const float* d_window, double* d_partial, int grid, hipStream_t stream,
                                    LaunchInfo* li, int fmt = kFmtCu8);
 
+// The same with per-bin statistics (rpf_kernels_series_stats.hip; the kernels of RPF_FLAG_BIN_STATS engines): row k =
+// args.out[3 k N ..) = S1[N], S2[N], PK[N] of spectrum k, what launch_fft_accum(stats) + launch_reduce_stats give for
+// the slice; d_partial: 2 x grid x 3 x N doubles, slot s = three planes from d_partial[3 s N ..); the fix-up adds
+// planes 0 and 1 in the plain fix-up's order and takes the maximum of plane 2.
+bool series_stats_supported(int N, int fmt = kFmtCu8);
+hipError_t plan_series_stats(int N, bool window, int device, LaunchInfo* li, int fmt = kFmtCu8);
+hipError_t launch_fft_accum_series_stats(int N, bool window, bool use_dma, const SeriesArgs& args, const cf* d_twiddles,
+                                         const float* d_window, double* d_partial, int grid, hipStream_t stream,
+                                         LaunchInfo* li, int fmt = kFmtCu8);
+
 // d_out[bin] = (accumulate ? d_out[bin] : 0) + sum_{s < nslots} d_partial[s*stride + bin],
 // summed in a fixed order (deterministic).
 // slot_stride = distance between partial spectra in elements (0: N).  N even.

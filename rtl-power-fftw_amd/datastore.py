@@ -245,6 +245,30 @@ class Datastore:
             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(done)))
         return out[:done.value], done.value
 
+    def accumulate_device_series_stats(self, d_stream_ptr, nbytes, frames_per_spectrum, max_spectra, d_out_ptr, hip_stream=0):
+        """rpf_accumulate_device_series_stats (stats engines): as accumulate_device_series, row k of d_out (K x 3 x N
+        device doubles) = S1, S2, PK of frames [k L, (k + 1) L); asynchronous.  Returns K."""
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_accumulate_device_series_stats(
+            self._handle, ctypes.c_void_p(d_stream_ptr), nbytes, frames_per_spectrum, max_spectra,
+            ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(hip_stream), ctypes.byref(done)))
+        return done.value
+
+    def accumulate_series_stats(self, stream, frames_per_spectrum, max_spectra=None):
+        """rpf_accumulate_series_stats: the same on a host byte stream (not through the buffer queues).  Returns
+        (K x 3 x N array, K), [k, 0] = S1, [k, 1] = S2, [k, 2] = PK; stats.spectral_kurtosis(out[:, 0], out[:, 1],
+        frames_per_spectrum) is the spectral kurtosis of every row.  max_spectra None = every whole spectrum."""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        if max_spectra is None:
+            max_spectra = max(self.frames_in(stream.size) // frames_per_spectrum, 0) if frames_per_spectrum >= 1 else 0
+        rows = max(min(max_spectra, self.frames_in(stream.size) // max(frames_per_spectrum, 1)), 0)
+        out = np.zeros((max(rows, 1), 3, self.params.N), dtype=np.float64)
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_accumulate_series_stats(
+            self._handle, ctypes.c_void_p(stream.ctypes.data), stream.size, frames_per_spectrum, max_spectra,
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(done)))
+        return out[:done.value], done.value
+
     def series_launches(self):
         """rpf_series_launches: transform launches of the last series call (1 = the one-launch path)."""
         return self._lib.rpf_series_launches(self._handle)

@@ -183,6 +183,28 @@ public:
     check(rpf_accumulate_device_series(engine_, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out, hip_stream, &done));
     return done;
   }
+  // Time-resolved statistics (rpf_accumulate_series_stats, params.bin_stats): as accumulate_series, row k of `rows`
+  // (resized to K x 3 x N) = S1[N], S2[N], PK[N] of frames [k L, (k + 1) L); spectral_kurtosis with M = L per row.
+  int64_t accumulate_series_stats(const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra,
+                                  std::vector<double>& rows) {
+    const int64_t frames = rpf_frames_in(engine_, nbytes);
+    const int64_t fit = frames_per_spectrum >= 1 ? frames / frames_per_spectrum : 0;
+    const size_t row = static_cast<size_t>(3) * params.N;
+    rows.assign(static_cast<size_t>(std::max<int64_t>(1, std::min(fit, std::max<int64_t>(max_spectra, 0)))) * row, 0.0);
+    int64_t done = 0;
+    check(rpf_accumulate_series_stats(engine_, stream, nbytes, frames_per_spectrum, max_spectra, rows.data(), &done));
+    rows.resize(static_cast<size_t>(done) * row);
+    return done;
+  }
+  // The same on a stream resident in HBM (rpf_accumulate_device_series_stats): d_out = K x 3 x N device doubles,
+  // asynchronous on hip_stream.
+  int64_t accumulate_device_series_stats(const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
+                                         int64_t max_spectra, double* d_out, void* hip_stream = nullptr) {
+    int64_t done = 0;
+    check(rpf_accumulate_device_series_stats(engine_, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out, hip_stream,
+                                             &done));
+    return done;
+  }
   // transform launches of the last series call: 1 = the one-launch path
   int series_launches() const { return rpf_series_launches(engine_); }
   // the engine behind this Datastore (multi-device scans hand it to the scan reducer)

@@ -215,6 +215,35 @@ long long rpf_host_accumulate_series(int N, int sample_format, int frame_step, c
     }
 }
 
+// The same for the two series calls with statistics, on a Datastore with params.bin_stats: out[cap_rows x 3 x N].
+long long rpf_host_accumulate_series_stats(int N, int sample_format, int frame_step, const unsigned char* stream,
+                                           size_t nbytes, long long L, long long max_spectra, double* out, long long cap_rows,
+                                           int device_resident, int* launches, char* msg, size_t cap)
+{
+    try {
+        Params params;
+        params.N = N;
+        params.sample_format = sample_format;
+        params.frame_step = frame_step;
+        params.bin_stats = true;
+        std::vector<float> no_window;
+        Datastore data(params, no_window);
+        long long done = 0;
+        if (device_resident) {
+            done = data.accumulate_device_series_stats(stream, nbytes, L, std::min(max_spectra, cap_rows), out);
+        } else {
+            std::vector<double> rows;
+            done = data.accumulate_series_stats(stream, nbytes, L, std::min(max_spectra, cap_rows), rows);
+            std::memcpy(out, rows.data(), sizeof(double) * rows.size());
+        }
+        if (launches) *launches = data.series_launches();
+        return done;
+    } catch (RPFexception& e) {
+        copy_out(e.what(), msg, cap);
+        return -static_cast<long long>(e.returnValue());
+    }
+}
+
 void rpf_host_synthetic(unsigned long long seed, unsigned long long first, unsigned long long n, unsigned char* out)
 {
     SyntheticSource::generate(seed, first, n, out);

@@ -66,6 +66,9 @@ const Spec kSpecs[] = {
     {0, "series", Kind::Int64, "frames",
      "Spectrogram of --input: one spectrum per <frames> consecutive FFT frames, written one after the other "
      "(not with a frequency range, -n, -t, -c, -e, -m, --stats or several --gpus)."},
+    {0, "series-stats", Kind::Int64, "frames",
+     "Time-resolved statistics of --input: one block with the --stats columns (peak hold, spectral kurtosis) per "
+     "<frames> consecutive FFT frames (implies --stats; not with --series, a frequency range, -n, -t, -c, -e, -m or several --gpus)."},
     {0, "reduce", Kind::Text, "rccl|host", "With --gpus: where a scan's per-device spectra are added (default: rccl if it loads, else host)."},
     {'h', "help", Kind::Flag, "", "Displays usage information and exits."},
     {0, "version", Kind::Flag, "", "Displays version information and exits."},
@@ -325,12 +328,18 @@ Options parse_command_line(int argc, const char* const* argv)
     if (o.bin_stats && o.devices.size() > 1)
         throw RPFexception("Option --stats does not combine with several devices in --gpus. Exiting.",
                            ReturnValue::InvalidArgument);
-    if (p.has("series")) {
-        o.series_frames = to_number<int64_t>(*find_spec("--series"), p.get("series"));
-        auto conflict = [](const std::string& what) {
-            throw RPFexception("Option --series " + what + " Exiting.", ReturnValue::InvalidArgument);
+    // --series <frames>, or --series-stats <frames>: the same series with a stats engine (--stats beside it changes nothing)
+    if (p.has("series") && p.has("series-stats"))
+        throw RPFexception("Option --series-stats does not combine with --series: it is the series with the statistics "
+                           "columns. Exiting.", ReturnValue::InvalidArgument);
+    if (p.has("series") || p.has("series-stats")) {
+        o.series_stats = p.has("series-stats");
+        const std::string opt = o.series_stats ? "series-stats" : "series";
+        o.series_frames = to_number<int64_t>(*find_spec("--" + opt), p.get(opt.c_str()));
+        auto conflict = [&opt](const std::string& what) {
+            throw RPFexception("Option --" + opt + " " + what + " Exiting.", ReturnValue::InvalidArgument);
         };
-        if (o.series_frames < 1) conflict("needs a number of frames of at least 1, got " + p.get("series") + ".");
+        if (o.series_frames < 1) conflict("needs a number of frames of at least 1, got " + p.get(opt.c_str()) + ".");
         if (!p.has("input")) conflict("needs --input: it cuts a replayed stream into consecutive integrations.");
         if (o.freq_hopping_isSet) conflict("does not combine with a frequency range in -f: a replay is one stream.");
         for (const char* name : {"repeats", "time", "continue", "elapsed"})
@@ -338,8 +347,9 @@ Options parse_command_line(int argc, const char* const* argv)
                 conflict(std::string("does not combine with --") + name + " (-" + find_spec(std::string("--") + name)->short_name +
                          "): the integration length is its own argument and the replay is read once.");
         if (o.matrixMode) conflict("does not combine with -m (matrix mode): the spectra are text blocks.");
-        if (o.bin_stats) conflict("does not combine with --stats: time-resolved statistics are not built.");
+        if (o.bin_stats && !o.series_stats) conflict("does not combine with --stats: time-resolved statistics are not built.");
         if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
+        if (o.series_stats) o.bin_stats = true;
     }
     if (p.has("input")) o.input_file = p.get("input");
     o.synthetic = p.has("synthetic");

@@ -54,6 +54,7 @@ struct Options : Params {
     std::vector<int> devices;        // --gpus a,b,... (else the single --gpu ordinal)
     std::string reduce;              // --reduce rccl|host ("" = rccl if it loads, else host)
     int64_t series_frames = 0;       // --series <frames>: spectrogram of the replay, one spectrum per <frames> frames (0 = off)
+    bool series_stats = false;       // --series-stats <frames>: the same with the --stats columns per block (sets both above)
     bool show_help = false, show_version = false;
 };
 

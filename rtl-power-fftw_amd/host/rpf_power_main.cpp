@@ -350,6 +350,8 @@ private:
 // block per integration -- what `-c -n <frames> --input` writes, block for block, without an acquisition per block.
 // The file is read in pieces of whole spectra (64 MB, or one spectrum if that is larger); with overlapped frames the
 // bytes a piece's last frames share with the next piece's first are carried over.
+// --series-stats <frames> (options.series_stats): the same through rpf_accumulate_series_stats, every block with the
+// --stats columns for M = <frames> -- what `--stats -c -n <frames> --input` writes.
 int run_series(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
 {
     Datastore data(options, aux.window_values);
@@ -367,7 +369,13 @@ int run_series(const Options& options, AuxData& aux, int actual_samplerate, int6
     const int64_t per_piece = std::max<int64_t>(1, fit);
     std::vector<uint8_t> bytes(static_cast<size_t>(options.frame_span(per_piece * L)));
     const std::vector<double>* baseline = options.baseline ? &aux.baseline_values : nullptr;
-    std::vector<double> rows, pwr(options.N);
+    std::vector<double> rows, pwr(options.N), sum_sq, peak;
+    const bool stats = options.series_stats;
+    const size_t row = static_cast<size_t>(stats ? 3 : 1) * options.N;
+    if (stats) {
+        sum_sq.resize(options.N);
+        peak.resize(options.N);
+    }
     size_t have = 0;
     int64_t written = 0;
     bool ended = false;
@@ -379,14 +387,22 @@ int run_series(const Options& options, AuxData& aux, int actual_samplerate, int6
             if (got == 0) ended = true;
             have += got;
         }
-        const int64_t done = data.accumulate_series(bytes.data(), have, L, per_piece, rows);
+        const int64_t done = stats ? data.accumulate_series_stats(bytes.data(), have, L, per_piece, rows)
+                                   : data.accumulate_series(bytes.data(), have, L, per_piece, rows);
         if (done == 0) break;
         const std::string end_stamp = Acquisition::utc_now();
         for (int64_t k = 0; k < done; ++k) {
-            std::copy(rows.begin() + static_cast<size_t>(k) * options.N, rows.begin() + static_cast<size_t>(k + 1) * options.N,
-                      pwr.begin());
-            write_text_header(std::cout, start_stamp, end_stamp);
-            write_spectrum_text(std::cout, pwr, options.N, L, tuned_freq, actual_samplerate, options.linear, baseline);
+            const auto at = rows.begin() + static_cast<size_t>(k) * row;
+            std::copy(at, at + options.N, pwr.begin());
+            write_text_header(std::cout, start_stamp, end_stamp, stats);
+            if (stats) {
+                std::copy(at + options.N, at + 2 * options.N, sum_sq.begin());
+                std::copy(at + 2 * options.N, at + 3 * options.N, peak.begin());
+                write_spectrum_text_stats(std::cout, pwr, sum_sq, peak, options.N, L, tuned_freq, actual_samplerate,
+                                          options.linear, baseline);
+            } else {
+                write_spectrum_text(std::cout, pwr, options.N, L, tuned_freq, actual_samplerate, options.linear, baseline);
+            }
             std::cout << std::endl;          // (the blank line that closes a pass of -c)
         }
         written += done;
