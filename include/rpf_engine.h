@@ -34,7 +34,9 @@ extern "C" {
                                additive within 2: rpf_config::frame_step, rpf_frames_in, rpf_frame_span;
                                RPF_FLAG_SAMPLE_FORMAT, RPF_FLAG_CATCH_ALL, rpf_sample_bytes, rpf_sample_format;
                                RPF_FLAG_BIN_STATS, rpf_has_bin_stats, rpf_get_bin_stats, rpf_accumulate_device_stats;
-                               rpf_accumulate_device_series, rpf_accumulate_series, rpf_series_launches */
+                               rpf_accumulate_device_series, rpf_accumulate_series, rpf_series_launches;
+                               rpf_accumulate_device_series_stats, rpf_accumulate_series_stats;
+                               rpf_accumulate_device_excised, rpf_accumulate_excised */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -302,6 +304,48 @@ int rpf_accumulate_device_series_stats(rpf_engine* e, const void* d_stream, size
  * before it returns.  Not while an acquisition is running. */
 int rpf_accumulate_series_stats(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
                                 int64_t max_spectra, double* out /* K x 3 x N, host */, int64_t* spectra_done);
+/* The excised average: the power summed over the stream with the integrations that carried interference left out, bin
+ * by bin (RPF_FLAG_BIN_STATS engines).  Everything that computes or checks it refers to this definition.
+ *   Rows.  L = frames_per_spectrum >= 2, K = min(max_spectra, rpf_frames_in(e, nbytes) / L) as above; row k has the planes
+ *     S1_k, S2_k, PK_k over the frames [k L, (k + 1) L), bit for bit the rows rpf_accumulate_device_series_stats writes
+ *     for the same stream on the same engine (the same kernels run, one-launch route or spectrum by spectrum).
+ *   Spectral kurtosis.  SK_k[b] = ((m + 1) / (m - 1)) * (m * S2 / (S1 * S1) - 1), m = (double)L, in IEEE double in exactly
+ *     this order of operations -- the order of stats.spectral_kurtosis -- each operation rounded on its own: no
+ *     contraction, no fast-math, a correctly rounded division (csrc/excise_core.h).  NaN where S1 = 0.
+ *   Kept.  Integration k is kept in bin b iff sk_lo <= SK_k[b] && SK_k[b] <= sk_hi; a NaN compares false and is flagged.
+ *     sk_lo and sk_hi are the caller's; -inf and +inf are allowed.
+ *   Outputs.  d_out[3 x N] (device doubles, 16-byte aligned, overwritten; zeros for K = 0, and nothing else is launched):
+ *       clean[b] = d_out[b]       sum of S1_k[b] over the kept k
+ *       kept[b]  = d_out[N + b]   the number of kept k, as a double (an exact integer)
+ *       total[b] = d_out[2N + b]  sum of S1_k[b] over all k < K
+ *     d_mask (may be NULL): d_mask[k N + b] = 1 where (k, b) is flagged, else 0, for k < K; rows >= K are not touched.
+ *     Bin N/2 = DC, no interpolation.
+ *   Addition order.  Fixed for a given call -- no floating-point atomics, the same call twice gives the same bits -- and
+ *     the same for clean and total: with nothing flagged clean == total bit for bit.  (Row k adds into accumulator
+ *     k mod G of its bin in increasing k, and the G accumulators are added in a fixed order: csrc/excise_core.h.  The
+ *     order differs from a sequential sum, so clean and total agree with one to a few ulp.)
+ * The rows never leave HBM: the stream goes through the series kernels in pieces of whole rows -- as many as fit in
+ * 64 MB of rows, at least one -- into engine-owned row scratch, and one launch per piece reads S1 and S2 of the piece
+ * (16 N bytes per row; PK is not read) and updates the accumulators; one small launch at the end writes d_out.  So it
+ * works at every size, frame step and format the engine serves and is fast where the series is; rpf_series_launches
+ * reports the transform launches as for the series calls.  Same stream, alignment and no-synchronise rules as
+ * rpf_accumulate_device (one exception of the same kind: a call that needs more row scratch than any before it
+ * synchronises once to grow it).  One excised call at a time per engine: the scratch is the engine's.
+ * The thresholds are the caller's business (stats.sk_limits, host/datastore.h sk_limits: 1 +- sigma sd of SK for
+ * Gaussian noise and independent frames); nothing here is a calibrated false-alarm rate.
+ * RPF_ERR_INVALID_ARGUMENT: an engine without RPF_FLAG_BIN_STATS, frames_per_spectrum < 2, sk_lo > sk_hi or a NaN
+ * threshold, a misaligned d_out, and what rpf_accumulate_device_series_stats refuses. */
+int rpf_accumulate_device_excised(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
+                                  int64_t max_spectra, double sk_lo, double sk_hi,
+                                  double* d_out /* 3 x N: clean, kept, total */, uint8_t* d_mask /* K x N or NULL */,
+                                  void* hip_stream, int64_t* spectra_done);
+/* The same on a host stream: the input moves in pieces as in rpf_accumulate_series_stats (no piece larger than the row
+ * scratch holds), only 3 x N doubles and, if asked for, the mask come back.  Not through the buffer queues: the queues,
+ * pwr, S2, PK and repeats_done of the engine are not touched.  Synchronises before it returns.  Not while an
+ * acquisition is running. */
+int rpf_accumulate_excised(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
+                           int64_t max_spectra, double sk_lo, double sk_hi, double* out /* 3 x N, host */,
+                           uint8_t* mask /* K x N or NULL, host */, int64_t* spectra_done);
 /* Transform-kernel launches the engine's last series call (either kind) enqueued: 1 on the one-launch path (whatever K is), K on the
  * spectrum-by-spectrum path, summed over the pieces of rpf_accumulate_series; 0 before any series call and for K = 0.
  * rpf_last_launch_info reports the geometry of the last of them. */

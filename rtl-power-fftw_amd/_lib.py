@@ -100,6 +100,12 @@ _SYMBOLS = [
                                                           ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_accumulate_series_stats", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64,
                                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_accumulate_device_excised", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64,
+                                                     ctypes.c_double, ctypes.c_double, _P, _P, _P,
+                                                     ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_accumulate_excised", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_series_launches", ctypes.c_int, [_P]),
     ("rpf_device_fused", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P,
                                         ctypes.POINTER(ctypes.c_int64)]),

@@ -162,6 +162,10 @@ struct rpf_engine {
     size_t series_in_bytes = 0;
     double* d_series_out = nullptr;       // ... and its rows (N doubles each; a stats engine's 3 N)
     size_t series_out_rows = 0;
+    // excised average (rpf_accumulate[_device]_excised): a piece's rows go to d_series_out, and
+    double* d_excise_state = nullptr;     // the (row group, bin) accumulators, then 3 N doubles: the host entry's result
+    uint8_t* d_excise_mask = nullptr;     // the host entry's mask bytes of one piece
+    size_t excise_mask_bytes = 0;
 
     mutable std::string last_error;
 };
@@ -798,6 +802,8 @@ void release_device(rpf_engine* e)
     if (e->d_series_partial) (void)hipFree(e->d_series_partial);
     if (e->d_series_in) (void)hipFree(e->d_series_in);
     if (e->d_series_out) (void)hipFree(e->d_series_out);
+    if (e->d_excise_state) (void)hipFree(e->d_excise_state);
+    if (e->d_excise_mask) (void)hipFree(e->d_excise_mask);
     if (e->d_pwr) (void)hipFree(e->d_pwr);
     for (auto& s : e->staging) {
         if (s.base) (void)hipFree(s.base);
@@ -1713,6 +1719,22 @@ int rpf_accumulate_device_series_stats(rpf_engine* e, const void* d_stream, size
                          d_out, hip_stream, spectra_done);
 }
 
+// The engine's row scratch holds `rows` rows (N doubles each; a stats engine's 3 N).  Grows, never shrinks: a call that
+// needs more than any before it synchronises `s` and the engine's stream once, frees and allocates.
+static int ensure_series_rows(rpf_engine* e, int64_t rows, hipStream_t s)
+{
+    if (static_cast<size_t>(rows) <= e->series_out_rows) return RPF_OK;
+    const size_t row = static_cast<size_t>(e->N) * (e->stats ? rpf::kStatsPlanes : 1);
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (s != e->compute_stream) HIP_TRY(e, hipStreamSynchronize(e->compute_stream));
+    if (e->d_series_out) (void)hipFree(e->d_series_out);
+    e->d_series_out = nullptr;
+    e->series_out_rows = 0;
+    HIP_TRY(e, hipMalloc(&e->d_series_out, sizeof(double) * row * static_cast<size_t>(rows)));
+    e->series_out_rows = static_cast<size_t>(rows);
+    return RPF_OK;
+}
+
 static int series_host(rpf_engine* e, const char* who, bool want_stats, const uint8_t* stream, size_t nbytes,
                        int64_t frames_per_spectrum, int64_t max_spectra, double* out, int64_t* spectra_done)
 {
@@ -1741,14 +1763,7 @@ static int series_host(rpf_engine* e, const char* who, bool want_stats, const ui
         HIP_TRY(e, hipMalloc(&e->d_series_in, piece_bytes));
         e->series_in_bytes = piece_bytes;
     }
-    if (static_cast<size_t>(per_piece) > e->series_out_rows) {
-        HIP_TRY(e, hipStreamSynchronize(e->compute_stream));
-        if (e->d_series_out) (void)hipFree(e->d_series_out);
-        e->d_series_out = nullptr;
-        e->series_out_rows = 0;
-        HIP_TRY(e, hipMalloc(&e->d_series_out, sizeof(double) * row * static_cast<size_t>(per_piece)));
-        e->series_out_rows = static_cast<size_t>(per_piece);
-    }
+    if ((rc = ensure_series_rows(e, per_piece, e->compute_stream)) != RPF_OK) return rc;
     // (a stream pinned with rpf_stream_register is copied from where it lies, asynchronously; a pageable one through
     // the runtime's own staging)
     hipStream_t s = e->compute_stream;
@@ -1779,6 +1794,152 @@ int rpf_accumulate_series_stats(rpf_engine* e, const uint8_t* stream, size_t nby
 {
     return series_host(e, "rpf_accumulate_series_stats", true, stream, nbytes, frames_per_spectrum, max_spectra, out,
                        spectra_done);
+}
+
+// ---- excised average: the series of statistics, judged by SK and summed where it passes ------------------------
+
+constexpr size_t kExciseRowBytes = static_cast<size_t>(64) << 20;      // a piece of rows: as many as fit, at least one
+
+// Everything series_check refuses for a stats entry, and what only the excised entries refuse.
+static int excise_check(rpf_engine* e, const char* who, const void* stream, size_t nbytes, int64_t L, int64_t max_spectra,
+                        double sk_lo, double sk_hi, const void* out)
+{
+    const int rc = series_check(e, who, stream, nbytes, L, max_spectra, out, /*want_stats=*/true);
+    if (rc != RPF_OK) return rc;
+    if (L < 2)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": frames_per_spectrum must be at least 2 (the spectral kurtosis of one frame is undefined)");
+    if (sk_lo != sk_lo || sk_hi != sk_hi)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": a threshold is NaN");
+    if (sk_lo > sk_hi)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": sk_lo is above sk_hi");
+    return RPF_OK;
+}
+
+static int64_t excise_rows_per_piece(const rpf_engine* e, int64_t K)
+{
+    const size_t row_bytes = sizeof(double) * rpf::kStatsPlanes * static_cast<size_t>(e->N);
+    return std::min(K, std::max<int64_t>(1, static_cast<int64_t>(kExciseRowBytes / row_bytes)));
+}
+
+static int ensure_excise_state(rpf_engine* e)
+{
+    if (e->d_excise_state) return RPF_OK;
+    HIP_TRY(e, hipMalloc(&e->d_excise_state,
+                         sizeof(double) * (rpf::excise_state_doubles(e->N) + rpf::kExcisePlanes * static_cast<size_t>(e->N))));
+    return RPF_OK;
+}
+
+// Rows [k0, k0 + kc) of the call from d_stream (its first byte is row k0's) into the row scratch, then into the
+// accumulators, on `s`; d_mask: this piece's bytes or null.
+static int excise_piece(rpf_engine* e, const uint8_t* d_stream, int64_t L, int64_t k0, int64_t kc, double sk_lo,
+                        double sk_hi, uint8_t* d_mask, hipStream_t s)
+{
+    const int rc = series_enqueue(e, d_stream, L, kc, e->d_series_out, s);
+    if (rc != RPF_OK) return rc;
+    HIP_TRY(e, rpf::launch_excise_rows(e->d_series_out, kc, k0, e->N, L, sk_lo, sk_hi, e->d_excise_state, d_mask, k0 == 0, s));
+    return RPF_OK;
+}
+
+int rpf_accumulate_device_excised(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
+                                  int64_t max_spectra, double sk_lo, double sk_hi, double* d_out, uint8_t* d_mask,
+                                  void* hip_stream, int64_t* spectra_done)
+{
+    const char* who = "rpf_accumulate_device_excised";
+    int rc = excise_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi, d_out);
+    if (rc != RPF_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
+    e->series_launches = 0;
+    const int64_t L = frames_per_spectrum;
+    const int64_t K = std::min(max_spectra, frames_in(e, nbytes) / L);
+    if (spectra_done) *spectra_done = K;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (K == 0) {
+        HIP_TRY(e, hipMemsetAsync(d_out, 0, sizeof(double) * rpf::kExcisePlanes * e->N, s));
+        return RPF_OK;
+    }
+    const int64_t per_piece = excise_rows_per_piece(e, K);
+    if ((rc = ensure_series_rows(e, per_piece, s)) != RPF_OK) return rc;
+    if ((rc = ensure_excise_state(e)) != RPF_OK) return rc;
+    const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
+    for (int64_t k0 = 0; k0 < K; k0 += per_piece) {
+        const int64_t kc = std::min(per_piece, K - k0);
+        rc = excise_piece(e, static_cast<const uint8_t*>(d_stream) + static_cast<size_t>(k0) * hop, L, k0, kc, sk_lo, sk_hi,
+                          d_mask ? d_mask + static_cast<size_t>(k0) * e->N : nullptr, s);
+        if (rc != RPF_OK) return rc;
+    }
+    HIP_TRY(e, rpf::launch_excise_combine(e->d_excise_state, e->N, d_out, s));
+    return RPF_OK;
+}
+
+int rpf_accumulate_excised(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
+                           int64_t max_spectra, double sk_lo, double sk_hi, double* out, uint8_t* mask,
+                           int64_t* spectra_done)
+{
+    int rc = excise_check(e, "rpf_accumulate_excised", stream, nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi, out);
+    if (rc != RPF_OK) return rc;
+    e->series_launches = 0;
+    const int64_t L = frames_per_spectrum;
+    const int64_t K = std::min(max_spectra, frames_in(e, nbytes) / L);
+    if (spectra_done) *spectra_done = K;
+    const size_t out_doubles = rpf::kExcisePlanes * static_cast<size_t>(e->N);
+    if (K == 0) {
+        std::fill(out, out + out_doubles, 0.0);
+        return RPF_OK;
+    }
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = e->compute_stream;
+    // a piece: whole spectra whose frames span at most 64 MB of input (series_host's pieces) and whose rows fit the
+    // row scratch, at least one
+    constexpr size_t kSeriesPiece = static_cast<size_t>(64) << 20;
+    const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
+    const int64_t fit = frames_in(e, kSeriesPiece) / L;
+    const int64_t per_piece = std::min(excise_rows_per_piece(e, K), std::max<int64_t>(1, fit));
+    const size_t piece_bytes = frame_span(e, per_piece * L);
+    if (piece_bytes > e->series_in_bytes) {
+        HIP_TRY(e, hipStreamSynchronize(s));
+        if (e->d_series_in) (void)hipFree(e->d_series_in);
+        e->d_series_in = nullptr;
+        e->series_in_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->d_series_in, piece_bytes));
+        e->series_in_bytes = piece_bytes;
+    }
+    const size_t mask_bytes = mask ? static_cast<size_t>(per_piece) * e->N : 0;
+    if (mask_bytes > e->excise_mask_bytes) {
+        HIP_TRY(e, hipStreamSynchronize(s));
+        if (e->d_excise_mask) (void)hipFree(e->d_excise_mask);
+        e->d_excise_mask = nullptr;
+        e->excise_mask_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->d_excise_mask, mask_bytes));
+        e->excise_mask_bytes = mask_bytes;
+    }
+    if ((rc = ensure_series_rows(e, per_piece, s)) != RPF_OK) return rc;
+    if ((rc = ensure_excise_state(e)) != RPF_OK) return rc;
+    for (int64_t k0 = 0; k0 < K; k0 += per_piece) {
+        const int64_t kc = std::min(per_piece, K - k0);
+        HIP_TRY(e, hipMemcpyAsync(e->d_series_in, stream + static_cast<size_t>(k0) * hop, frame_span(e, kc * L),
+                                  hipMemcpyHostToDevice, s));
+        rc = excise_piece(e, e->d_series_in, L, k0, kc, sk_lo, sk_hi, mask ? e->d_excise_mask : nullptr, s);
+        if (rc != RPF_OK) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        if (mask)
+            HIP_TRY(e, hipMemcpyAsync(mask + static_cast<size_t>(k0) * e->N, e->d_excise_mask, static_cast<size_t>(kc) * e->N,
+                                      hipMemcpyDeviceToHost, s));
+        HIP_TRY(e, hipStreamSynchronize(s));       // the piece's buffers are reused by the next one
+    }
+    double* d_result = e->d_excise_state + rpf::excise_state_doubles(e->N);
+    HIP_TRY(e, rpf::launch_excise_combine(e->d_excise_state, e->N, d_result, s));
+    HIP_TRY(e, hipMemcpyAsync(out, d_result, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return RPF_OK;
 }
 
 int rpf_series_launches(const rpf_engine* e) { return e ? e->series_launches : 0; }

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "excise_core.h"
 #include "fft_core.h"
 #include "hop_partition.h"
 #include "series_partition.h"
@@ -80,6 +81,17 @@ hipError_t plan_series_stats(int N, bool window, int device, LaunchInfo* li, int
 hipError_t launch_fft_accum_series_stats(int N, bool window, bool use_dma, const SeriesArgs& args, const cf* d_twiddles,
                                          const float* d_window, double* d_partial, int grid, hipStream_t stream,
                                          LaunchInfo* li, int fmt = kFmtCu8);
+
+// ---- the excised average over such rows (rpf_excise.hip, excise_core.h) ----
+// d_state: excise_state_doubles(N) doubles, one accumulator triple per (row group, bin), owned by one call at a time.
+size_t excise_state_doubles(int N);
+// One piece: rows [k0, k0 + kc) of the call, d_rows[kc x 3 x N] as the series with statistics writes them (L >= 2 frames
+// each), judged by sk_lo <= SK <= sk_hi and added into d_state; first: the call's first piece, d_state starts from zero.
+// d_mask: the piece's kc x N bytes, 1 = flagged, or null.
+hipError_t launch_excise_rows(const double* d_rows, int64_t kc, int64_t k0, int N, int64_t L, double sk_lo, double sk_hi,
+                              double* d_state, uint8_t* d_mask, bool first, hipStream_t stream);
+// After the last piece: d_out[3 x N] = clean, kept, total (16-byte aligned), the accumulators added in the fixed order.
+hipError_t launch_excise_combine(const double* d_state, int N, double* d_out, hipStream_t stream);
 
 // d_out[bin] = (accumulate ? d_out[bin] : 0) + sum_{s < nslots} d_partial[s*stride + bin],
 // summed in a fixed order (deterministic).

@@ -269,6 +269,34 @@ class Datastore:
             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(done)))
         return out[:done.value], done.value
 
+    def accumulate_device_excised(self, d_stream_ptr, nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi, d_out_ptr,
+                                  d_mask_ptr=0, hip_stream=0):
+        """rpf_accumulate_device_excised (stats engines): the excised average of a stream resident in HBM, d_out = 3 x N
+        device doubles (clean, kept, total), d_mask = K x N device bytes (1 = flagged) or 0; asynchronous.  Returns K."""
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_accumulate_device_excised(
+            self._handle, ctypes.c_void_p(d_stream_ptr), nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi,
+            ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(d_mask_ptr or None), ctypes.c_void_p(hip_stream),
+            ctypes.byref(done)))
+        return done.value
+
+    def accumulate_excised(self, stream, frames_per_spectrum, sk_lo, sk_hi, max_spectra=None, want_mask=False):
+        """rpf_accumulate_excised: the same on a host byte stream (not through the buffer queues).  Returns
+        (out (3, N): clean, kept, total; mask (K, N) uint8 with 1 = flagged, or None; K).  stats.sk_limits gives
+        thresholds; max_spectra None = every whole spectrum the stream holds."""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        if max_spectra is None:
+            max_spectra = max(self.frames_in(stream.size) // frames_per_spectrum, 0) if frames_per_spectrum >= 1 else 0
+        rows = max(min(max_spectra, self.frames_in(stream.size) // max(frames_per_spectrum, 1)), 0)
+        out = np.zeros((3, self.params.N), dtype=np.float64)
+        mask = np.zeros((max(rows, 1), self.params.N), dtype=np.uint8) if want_mask else None
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_accumulate_excised(
+            self._handle, ctypes.c_void_p(stream.ctypes.data), stream.size, frames_per_spectrum, max_spectra, sk_lo, sk_hi,
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+            mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if want_mask else None, ctypes.byref(done)))
+        return out, (mask[:done.value] if want_mask else None), done.value
+
     def series_launches(self):
         """rpf_series_launches: transform launches of the last series call (1 = the one-launch path)."""
         return self._lib.rpf_series_launches(self._handle)

@@ -130,6 +130,15 @@ void write_text_header(std::ostream& out, const std::string& start_stamp, const 
     write_text_header(out, start_stamp, end_stamp, false);
 }
 
+void write_text_header_excised(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp)
+{
+    out << "# rtl-power-fftw output" << std::endl;
+    out << "# Acquisition start: " << start_stamp << std::endl;
+    out << "# Acquisition end: " << end_stamp << std::endl;
+    out << "#" << std::endl;
+    out << "# frequency [Hz] power spectral density [dB/Hz] kept fraction" << std::endl;
+}
+
 void write_text_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, bool stats)
 {
     out << "# rtl-power-fftw output" << std::endl;
@@ -193,6 +202,28 @@ void write_spectrum_text_stats(std::ostream& out, std::vector<double>& pwr, cons
         out << std::setprecision(freq_digits) << freq << " " << std::setprecision(6)
             << bin_value(pwr, i, N, repeats_done, samplerate, linear, baseline) << " "
             << bin_value(peak, i, N, 1, samplerate, linear, baseline) << " " << sk[i] << std::endl;
+    }
+    out << std::endl;
+    out.flush();
+}
+
+void write_spectrum_text_excised(std::ostream& out, const std::vector<double>& clean, const std::vector<double>& kept,
+                                 const std::vector<double>& total, int N, int64_t K, int64_t L, int64_t tuned_freq,
+                                 int samplerate, bool linear, const std::vector<double>* baseline)
+{
+    // every bin's mean over ITS kept integrations (bins differ in how many that is), so the usual division by the
+    // number of frames happens here, bin by bin, and bin_value divides by 1
+    std::vector<double> mean(N);
+    const double l = static_cast<double>(L);
+    for (int i = 0; i < N; ++i)
+        mean[i] = kept[i] > 0 ? clean[i] / (kept[i] * l) : total[i] / (static_cast<double>(K) * l);
+    interpolate_dc(mean, N);
+    const int freq_digits = static_cast<int>(
+        std::ceil(std::floor(std::log10(static_cast<double>(tuned_freq))) - std::log10(samplerate / N) + 1 + 2));
+    for (int i = 0; i < N; ++i) {
+        const double freq = tuned_freq + (i - N / 2.0) * samplerate / N;
+        out << std::setprecision(freq_digits) << freq << " " << std::setprecision(6)
+            << bin_value(mean, i, N, 1, samplerate, linear, baseline) << " " << kept[i] / static_cast<double>(K) << std::endl;
     }
     out << std::endl;
     out.flush();

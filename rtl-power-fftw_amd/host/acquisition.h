@@ -107,6 +107,14 @@ void write_spectrum_text_stats(std::ostream& out, std::vector<double>& pwr, cons
                                int samplerate, bool linear, const std::vector<double>* baseline);
 // `stats`: the last '#' line names the two columns of --stats too
 void write_text_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, bool stats);
+// --excise: the header with "kept fraction" as the third column's name, and the block.  Power column: the mean over
+// the kept integrations, clean[b] / (kept[b] L) -- where none was kept, the unexcised mean total[b] / (K L) -- with its
+// DC bin the mean of its neighbours, then / N / samplerate, dB and baseline as always; third column: kept[b] / K as it
+// is (the DC bin too).
+void write_text_header_excised(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp);
+void write_spectrum_text_excised(std::ostream& out, const std::vector<double>& clean, const std::vector<double>& kept,
+                                 const std::vector<double>& total, int N, int64_t K, int64_t L, int64_t tuned_freq,
+                                 int samplerate, bool linear, const std::vector<double>* baseline);
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,
                          const std::vector<double>* baseline, std::vector<float>& row);
 // Matrix mode: append one float32 row to options.bin_file and keep the row/column

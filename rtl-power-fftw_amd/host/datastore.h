@@ -73,6 +73,20 @@ inline double spectral_kurtosis(double s1, double s2, int64_t M) {
   return ((m + 1.0) / (m - 1.0)) * (m * s2 / (s1 * s1) - 1.0);
 }
 
+// Thresholds for the excised average (rpf_accumulate_excised): 1 -+ sigma sd with sd^2 = 4 M^2 / ((M-1)(M+2)(M+3)), the
+// variance of SK for Gaussian noise and M independent frames; the lower limit not below 0.  The same operations as
+// stats.py's sk_limits.  SK is skewed to the right, so 3 sigma flags a fraction of a per cent of clean data: a starting
+// point, not a calibrated false-alarm rate.
+inline void sk_limits(int64_t M, double sigma, double& lo, double& hi) {
+  if (M < 2)
+    throw RPFexception("sk_limits: M must be at least 2, got " + std::to_string(M) + ".", ReturnValue::InvalidArgument);
+  const double m = static_cast<double>(M);
+  const double sd = std::sqrt(4.0 * m * m / ((m - 1.0) * (m + 2.0) * (m + 3.0)));
+  const double d = sigma * sd;
+  lo = std::max(1.0 - d, 0.0);
+  hi = 1.0 + d;
+}
+
 // A filled/empty hand-off buffer: what `Buffer&` is in acquisition.cxx:283,302-304
 // (data()/size()/resize()), backed by engine-owned pinned memory.
 class Buffer {
@@ -203,6 +217,31 @@ public:
     int64_t done = 0;
     check(rpf_accumulate_device_series_stats(engine_, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out, hip_stream,
                                              &done));
+    return done;
+  }
+  // The excised average (rpf_accumulate_excised, params.bin_stats; include/rpf_engine.h has the definition): `out`
+  // (resized to 3 x N) = clean, kept, total over the K integrations of frames_per_spectrum frames, an integration kept
+  // in a bin iff sk_lo <= SK <= sk_hi; mask: NULL, or resized to K x N bytes, 1 = flagged.  Returns K.
+  int64_t accumulate_excised(const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra,
+                             double sk_lo, double sk_hi, std::vector<double>& out, std::vector<uint8_t>* mask = nullptr) {
+    const int64_t frames = rpf_frames_in(engine_, nbytes);
+    const int64_t fit = frames_per_spectrum >= 1 ? frames / frames_per_spectrum : 0;
+    out.assign(static_cast<size_t>(3) * params.N, 0.0);
+    if (mask) mask->assign(static_cast<size_t>(std::max<int64_t>(1, std::min(fit, std::max<int64_t>(max_spectra, 0)))) * params.N, 0);
+    int64_t done = 0;
+    check(rpf_accumulate_excised(engine_, stream, nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi, out.data(),
+                                 mask ? mask->data() : nullptr, &done));
+    if (mask) mask->resize(static_cast<size_t>(done) * params.N);
+    return done;
+  }
+  // The same on a stream resident in HBM (rpf_accumulate_device_excised): d_out = 3 x N device doubles, d_mask = K x N
+  // device bytes or NULL, asynchronous on hip_stream.
+  int64_t accumulate_device_excised(const void* d_stream, size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra,
+                                    double sk_lo, double sk_hi, double* d_out, uint8_t* d_mask = nullptr,
+                                    void* hip_stream = nullptr) {
+    int64_t done = 0;
+    check(rpf_accumulate_device_excised(engine_, d_stream, nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi, d_out,
+                                        d_mask, hip_stream, &done));
     return done;
   }
   // transform launches of the last series call: 1 = the one-launch path

@@ -244,6 +244,65 @@ long long rpf_host_accumulate_series_stats(int N, int sample_format, int frame_s
     }
 }
 
+// datastore.h's sk_limits; 0, or -(exit code) with the message in `msg`.
+int rpf_host_sk_limits(long long M, double sigma, double* lo, double* hi, char* msg, size_t cap)
+{
+    try {
+        sk_limits(M, sigma, *lo, *hi);
+        return 0;
+    } catch (RPFexception& e) {
+        copy_out(e.what(), msg, cap);
+        return -static_cast<int>(e.returnValue());
+    }
+}
+
+// rpf_host::Datastore's two excised calls on a Datastore with params.bin_stats (needs a device): out[3 x N], mask
+// (cap_rows x N bytes, or NULL); device_resident != 0: stream, out and mask are device pointers and
+// accumulate_device_excised runs on the null stream.  Returns K, or -(exit code) with the message in `msg`.
+long long rpf_host_accumulate_excised(int N, int sample_format, int frame_step, const unsigned char* stream, size_t nbytes,
+                                      long long L, long long max_spectra, double sk_lo, double sk_hi, double* out,
+                                      unsigned char* mask, long long cap_rows, int device_resident, int* launches, char* msg,
+                                      size_t cap)
+{
+    try {
+        Params params;
+        params.N = N;
+        params.sample_format = sample_format;
+        params.frame_step = frame_step;
+        params.bin_stats = true;
+        std::vector<float> no_window;
+        Datastore data(params, no_window);
+        long long done = 0;
+        if (device_resident) {
+            done = data.accumulate_device_excised(stream, nbytes, L, std::min(max_spectra, cap_rows), sk_lo, sk_hi, out, mask);
+        } else {
+            std::vector<double> res;
+            std::vector<uint8_t> flags;
+            done = data.accumulate_excised(stream, nbytes, L, std::min(max_spectra, cap_rows), sk_lo, sk_hi, res,
+                                           mask ? &flags : nullptr);
+            std::memcpy(out, res.data(), sizeof(double) * res.size());
+            if (mask) std::memcpy(mask, flags.data(), flags.size());
+        }
+        if (launches) *launches = data.series_launches();
+        return done;
+    } catch (RPFexception& e) {
+        copy_out(e.what(), msg, cap);
+        return -static_cast<long long>(e.returnValue());
+    }
+}
+
+// The excised block's writer (write_spectrum_text_excised).
+long rpf_host_format_text_excised(const double* clean, const double* kept, const double* total, int N, long long K,
+                                  long long L, long long tuned_freq, int samplerate, int linear, const double* baseline,
+                                  char* out, size_t cap)
+{
+    std::vector<double> c(clean, clean + N), k(kept, kept + N), t(total, total + N), b;
+    if (baseline) b.assign(baseline, baseline + N);
+    std::ostringstream os;
+    write_spectrum_text_excised(os, c, k, t, N, K, L, tuned_freq, samplerate, linear != 0, baseline ? &b : nullptr);
+    return copy_out(os.str(), out, cap);
+}
+
 void rpf_host_synthetic(unsigned long long seed, unsigned long long first, unsigned long long n, unsigned char* out)
 {
     SyntheticSource::generate(seed, first, n, out);

@@ -69,6 +69,11 @@ const Spec kSpecs[] = {
     {0, "series-stats", Kind::Int64, "frames",
      "Time-resolved statistics of --input: one block with the --stats columns (peak hold, spectral kurtosis) per "
      "<frames> consecutive FFT frames (implies --stats; not with --series, a frequency range, -n, -t, -c, -e, -m or several --gpus)."},
+    {0, "excise", Kind::Int64, "frames",
+     "Average of --input without interference: integrations of <frames> consecutive FFT frames whose spectral kurtosis "
+     "leaves 1 +- sigma standard deviations are left out, bin by bin; one block with a kept-fraction column (implies "
+     "--stats' engine; not with --series, --series-stats, a frequency range, -n, -t, -c, -e, -m or several --gpus)."},
+    {0, "excise-sigma", Kind::Double, "sigma", "Width of the --excise thresholds in standard deviations of the estimator. Default 3."},
     {0, "reduce", Kind::Text, "rccl|host", "With --gpus: where a scan's per-device spectra are added (default: rccl if it loads, else host)."},
     {'h', "help", Kind::Flag, "", "Displays usage information and exits."},
     {0, "version", Kind::Flag, "", "Displays version information and exits."},
@@ -350,6 +355,36 @@ Options parse_command_line(int argc, const char* const* argv)
         if (o.bin_stats && !o.series_stats) conflict("does not combine with --stats: time-resolved statistics are not built.");
         if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
         if (o.series_stats) o.bin_stats = true;
+    }
+    if (p.has("excise-sigma") && !p.has("excise"))
+        throw RPFexception("Option --excise-sigma needs --excise: it sets the width of its thresholds. Exiting.",
+                           ReturnValue::InvalidArgument);
+    if (p.has("excise")) {
+        o.excise_frames = to_number<int64_t>(*find_spec("--excise"), p.get("excise"));
+        auto conflict = [](const std::string& what) {
+            throw RPFexception("Option --excise " + what + " Exiting.", ReturnValue::InvalidArgument);
+        };
+        if (o.excise_frames < 2)
+            conflict("needs a number of frames of at least 2 (the spectral kurtosis of one frame is undefined), got " +
+                     p.get("excise") + ".");
+        if (p.has("excise-sigma")) {
+            o.excise_sigma = to_number<double>(*find_spec("--excise-sigma"), p.get("excise-sigma"));
+            if (!(o.excise_sigma >= 0) || std::isinf(o.excise_sigma))
+                conflict("needs a finite, non-negative --excise-sigma, got " + p.get("excise-sigma") + ".");
+        }
+        if (!p.has("input")) conflict("needs --input: it averages a replayed stream.");
+        for (const char* name : {"series", "series-stats"})
+            if (p.has(name))
+                conflict(std::string("does not combine with --") + name + ": that writes every integration, this one their "
+                         "average.");
+        if (o.freq_hopping_isSet) conflict("does not combine with a frequency range in -f: a replay is one stream.");
+        for (const char* name : {"repeats", "time", "continue", "elapsed"})
+            if (p.has(name))
+                conflict(std::string("does not combine with --") + name + " (-" + find_spec(std::string("--") + name)->short_name +
+                         "): the integration length is its own argument and the replay is read once.");
+        if (o.matrixMode) conflict("does not combine with -m (matrix mode): the average is one text block.");
+        if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
+        o.bin_stats = true;
     }
     if (p.has("input")) o.input_file = p.get("input");
     o.synthetic = p.has("synthetic");

@@ -55,6 +55,8 @@ struct Options : Params {
     std::string reduce;              // --reduce rccl|host ("" = rccl if it loads, else host)
     int64_t series_frames = 0;       // --series <frames>: spectrogram of the replay, one spectrum per <frames> frames (0 = off)
     bool series_stats = false;       // --series-stats <frames>: the same with the --stats columns per block (sets both above)
+    int64_t excise_frames = 0;       // --excise <frames>: the replay's average without the SK-flagged integrations (0 = off)
+    double excise_sigma = 3.0;       // --excise-sigma <s>: its thresholds, sk_limits(frames, s)
     bool show_help = false, show_version = false;
 };
 

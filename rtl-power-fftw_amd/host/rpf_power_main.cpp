@@ -421,6 +421,71 @@ int run_series(const Options& options, AuxData& aux, int actual_samplerate, int6
     return 0;
 }
 
+// --excise <frames>: the replay's average with the integrations that carried interference left out, bin by bin
+// (rpf_accumulate_excised; thresholds sk_limits(<frames>, --excise-sigma)), ONE block for the file.  The file is read in
+// pieces of whole integrations as run_series reads it; every piece leaves clean, kept and total of its integrations,
+// and the pieces' results are added here in file order.
+int run_excise(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
+{
+    Datastore data(options, aux.window_values);
+    std::FILE* file = options.input_file == "-" ? stdin : std::fopen(options.input_file.c_str(), "rb");
+    if (!file) throw RPFexception("Could not open " + options.input_file + ".", ReturnValue::InvalidInput);
+    struct CloseOnExit {
+        std::FILE* f;
+        ~CloseOnExit() { if (f != stdin) std::fclose(f); }
+    } close_file{file};
+    const int64_t L = options.excise_frames;
+    double sk_lo = 0, sk_hi = 0;
+    sk_limits(L, options.excise_sigma, sk_lo, sk_hi);
+    const int64_t b = options.sample_bytes();
+    const int64_t frame = b * options.N, pitch = b * options.step();
+    const int64_t piece_budget = static_cast<int64_t>(64) << 20;
+    const int64_t fit = piece_budget < frame ? 0 : ((piece_budget - frame) / pitch + 1) / L;
+    const int64_t per_piece = std::max<int64_t>(1, fit);
+    std::vector<uint8_t> bytes(static_cast<size_t>(options.frame_span(per_piece * L)));
+    const size_t N = static_cast<size_t>(options.N);
+    std::vector<double> piece, clean(N, 0.0), kept(N, 0.0), total(N, 0.0);
+    size_t have = 0;
+    int64_t K = 0;
+    bool ended = false;
+    set_CtrlC_handler(true);
+    const std::string start_stamp = Acquisition::utc_now();
+    while (!checkInterrupt(InterruptState::FinishNow)) {
+        while (!ended && have < bytes.size()) {
+            const size_t got = std::fread(bytes.data() + have, 1, bytes.size() - have, file);
+            if (got == 0) ended = true;
+            have += got;
+        }
+        const int64_t done = data.accumulate_excised(bytes.data(), have, L, per_piece, sk_lo, sk_hi, piece);
+        if (done == 0) break;
+        for (size_t i = 0; i < N; ++i) {
+            clean[i] += piece[i];
+            kept[i] += piece[N + i];
+            total[i] += piece[2 * N + i];
+        }
+        K += done;
+        const size_t used = static_cast<size_t>(done * L * pitch);      // the next integration starts here
+        std::memmove(bytes.data(), bytes.data() + used, have - used);
+        have -= used;
+        if (ended && static_cast<int64_t>(have) < options.frame_span(L)) break;
+    }
+    if (K == 0)
+        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+    const std::string end_stamp = Acquisition::utc_now();
+    write_text_header_excised(std::cout, start_stamp, end_stamp);
+    write_spectrum_text_excised(std::cout, clean, kept, total, options.N, K, L, tuned_freq, actual_samplerate, options.linear,
+                                options.baseline ? &aux.baseline_values : nullptr);
+    std::cout << std::endl;          // (the blank line that closes a pass)
+    double flagged = 0;
+    for (size_t i = 0; i < N; ++i) flagged += static_cast<double>(K) - kept[i];
+    const double pairs = static_cast<double>(K) * static_cast<double>(N);
+    std::cerr << "Excised: " << static_cast<int64_t>(flagged) << " of " << static_cast<int64_t>(pairs)
+              << " (integration, bin) pairs flagged (" << 100.0 * flagged / pairs << " %), " << K << " integrations of " << L
+              << " frames, spectral kurtosis kept in [" << sk_lo << ", " << sk_hi << "]" << std::endl;
+    if (chatty(options)) print_acquisition_summary(options.N, K * L, 0, 0, actual_samplerate);
+    return 0;
+}
+
 int run(int argc, char** argv)
 {
     Options options = parse_command_line(argc, argv);
@@ -470,6 +535,7 @@ int run(int argc, char** argv)
     Plan plan(options, actual_samplerate);
     plan.print();
 
+    if (options.excise_frames > 0) return run_excise(options, aux, actual_samplerate, source->frequency());
     if (options.series_frames > 0) return run_series(options, aux, actual_samplerate, source->frequency());
 
     const bool multi = options.devices.size() > 1;

@@ -19,3 +19,38 @@ def spectral_kurtosis(S1, S2, M):
     s2 = np.broadcast_to(S2, out.shape)[ok]
     out[ok] = ((m + 1.0) / (m - 1.0)) * (m * s2 / (s1 * s1) - 1.0)
     return out
+
+
+def sk_limits(M, sigma=3.0):
+    """(lower, upper) = 1 -+ sigma * sqrt(4 M^2 / ((M-1)(M+2)(M+3))), the lower one not below 0: `sigma` standard
+    deviations of SK about its mean for Gaussian noise and M independent frames (Nita & Gary's variance).  SK is bounded
+    below by 0 and skewed to the right (skewness about 10/sqrt(M)), so at 3 sigma a fraction of a per cent of clean data
+    lies above the upper limit: thresholds to start from, not a calibrated false-alarm rate.  Overlapped frames
+    (frame step < N) are not independent.  The C++ host's sk_limits (host/datastore.h) does the same operations."""
+    M = int(M)
+    if M < 2:
+        raise ValueError("sk_limits: M must be at least 2, got %d" % M)
+    m = np.float64(M)
+    sd = np.sqrt(4.0 * m * m / ((m - 1.0) * (m + 2.0) * (m + 3.0)))
+    d = np.float64(sigma) * sd
+    return float(max(1.0 - d, 0.0)), float(1.0 + d)
+
+
+def excise(rows, L, sk_lo, sk_hi):
+    """The excised average of include/rpf_engine.h (rpf_accumulate_device_excised) stated in numpy, on the (K, 3, N)
+    rows of a series of statistics ([k, 0] = S1, [k, 1] = S2; PK is not used): integration k is kept in bin b iff
+    sk_lo <= SK_k[b] <= sk_hi with SK = spectral_kurtosis(S1, S2, L) (NaN: flagged).  Returns (out (3, N) = clean, kept,
+    total; mask (K, N) uint8, 1 = flagged).  The sums run over k in numpy's order, the engine's in its own: clean and
+    total agree to a few ulp, kept and mask exactly."""
+    rows = np.asarray(rows, dtype=np.float64)
+    K, planes, N = rows.shape
+    assert planes == 3
+    s1 = rows[:, 0]
+    sk = spectral_kurtosis(s1, rows[:, 1], L)
+    with np.errstate(invalid="ignore"):
+        keep = (sk >= sk_lo) & (sk <= sk_hi)
+    out = np.zeros((3, N))
+    out[0] = np.where(keep, s1, 0.0).sum(axis=0)
+    out[1] = keep.sum(axis=0)
+    out[2] = s1.sum(axis=0)
+    return out, (~keep).astype(np.uint8)
