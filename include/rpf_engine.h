@@ -104,16 +104,22 @@ typedef struct rpf_config {
  * exist only in the separate -DRPF_TUNING build used by tools/. */
 #define RPF_FLAG_VARIANT(k) (((uint32_t)(k) & 0xffu) << 8)
 /* Sample format of every stream the engine reads, in bits 16..19 of `flags` (zero = cu8, so a caller that never heard
- * of formats gets what it always got).  The sample is converted to float32 exactly (every value of all three formats
- * is a float32), (-1)^n is exact and the window multiplies once, with one rounding -- datastore.cxx:73-77 with
+ * of formats gets what it always got).  The sample is converted to float32 exactly (every value of the three integer
+ * formats is a float32), (-1)^n is exact and the window multiplies once, with one rounding -- datastore.cxx:73-77 with
  * `v - 127` replaced by `v` for the signed formats.  Any other value: RPF_ERR_INVALID_ARGUMENT from
  * rpf_engine_create, before any device is touched.
- * The LDS-resident kernel (powers of two 64 .. 8192) reads all three natively; at every other size a cs8 / cs16
- * engine runs on the catch-all Stockham path (rpf_supported_n(N) holds for all three formats), which is several
- * times slower than the tuned kernel a cu8 engine gets at that size (README.md, "Sample formats"). */
+ * cf32: the sample is the stored pair of IEEE float32 values, I then Q, little-endian, 8 bytes, x = v with no scaling,
+ * clamping or screening: a stream in +-1.0 gives powers 2^-14 of the same signal at 8-bit full scale, and a NaN or an
+ * Inf propagates into every bin of its frame and so into the sum.  A cf32 stream of int16 values gives the spectrum
+ * of the cs16 stream of those values.  (3 is not a format: 4 is cf32.)
+ * The LDS-resident kernel (powers of two 64 .. 8192) reads all four natively; at every other size a cs8 / cs16 / cf32
+ * engine runs on the catch-all Stockham path (rpf_supported_n(N) holds for all four formats), which is several
+ * times slower than the tuned kernel a cu8 engine gets at that size; so does a cf32 engine with RPF_FLAG_BIN_STATS
+ * at every size (README.md, "Sample formats"). */
 #define RPF_FORMAT_CU8  0   /* unsigned 8-bit I,Q; x = v - 127   (the reference; the default) */
 #define RPF_FORMAT_CS8  1   /* signed 8-bit I,Q;   x = v                                       */
 #define RPF_FORMAT_CS16 2   /* signed 16-bit little-endian I,Q; x = v                          */
+#define RPF_FORMAT_CF32 4   /* IEEE float32 little-endian I,Q;  x = v as stored                */
 #define RPF_FLAG_SAMPLE_FORMAT(f) (((uint32_t)(f) & 0xfu) << 16)
 /* Any N, any format on the catch-all Stockham path (A/B measurement, and the comparator of the format tests). */
 #define RPF_FLAG_CATCH_ALL 16u
@@ -129,8 +135,8 @@ typedef struct rpf_config {
  * An engine created with the flag keeps S2 and PK beside the power on the buffer-queue path (rpf_begin .. rpf_finish,
  * rpf_accumulate; rpf_get_bin_stats) and in rpf_accumulate_device_stats; rpf_get_power, rpf_accumulate and
  * rpf_accumulate_device keep their meaning and return S1.  Served natively by the LDS-resident kernel (powers of two
- * 64 .. 8192, all three sample formats, any frame step) with two more register accumulators per bin; at every other size
- * a stats engine runs on the catch-all Stockham path, as a cs8 / cs16 engine does (README.md, "Per-bin statistics").
+ * 64 .. 8192, the three integer sample formats, any frame step) with two more register accumulators per bin; at every other
+ * size, and with cf32 at every size, a stats engine runs on the catch-all Stockham path (README.md, "Per-bin statistics").
  * Without the flag nothing changes: same kernels, same scratch, same results.
  * RPF_ERR_INVALID_ARGUMENT from rpf_engine_create, before any device is touched: together with RPF_FLAG_FOURSTEP_FUSED
  * or with RPF_FLAG_VARIANT(k), k != 0.  On a stats engine rpf_device_fused, rpf_device_fused_hops and rpf_device_reduce
@@ -359,7 +365,7 @@ int rpf_series_launches(const rpf_engine* e);
  * the general entry point). */
 int64_t rpf_frames_in(const rpf_engine* e, size_t nbytes);
 size_t rpf_frame_span(const rpf_engine* e, int64_t frames);
-/* Bytes per complex sample, b: 2 (cu8, cs8) or 4 (cs16), and the engine's RPF_FORMAT_*.  EVERY byte count of this
+/* Bytes per complex sample, b: 2 (cu8, cs8), 4 (cs16) or 8 (cf32), and the engine's RPF_FORMAT_*.  EVERY byte count of this
  * interface that is written 2N / 2S above is bN / bS: frames(nbytes) = nbytes < bN ? 0 : (nbytes - bN) / (bS) + 1,
  * the span bN + bS (frames - 1), the frame quota and the trailing partial frame of rpf_finish, the hop lengths of
  * rpf_accumulate_device_hops.  rpf_buffer_submit wants nbytes % b == 0 (a sample never straddles two buffers; frames

@@ -59,8 +59,9 @@ FLAG_BIN_STATS = 32
 FORMAT_CU8 = 0
 FORMAT_CS8 = 1
 FORMAT_CS16 = 2
-FORMATS = {"cu8": FORMAT_CU8, "cs8": FORMAT_CS8, "cs16": FORMAT_CS16}
-SAMPLE_BYTES = {"cu8": 2, "cs8": 2, "cs16": 4}
+FORMAT_CF32 = 4     # (3 is not a format)
+FORMATS = {"cu8": FORMAT_CU8, "cs8": FORMAT_CS8, "cs16": FORMAT_CS16, "cf32": FORMAT_CF32}
+SAMPLE_BYTES = {"cu8": 2, "cs8": 2, "cs16": 4, "cf32": 8}
 
 
 def FLAG_SAMPLE_FORMAT(f):

@@ -297,7 +297,8 @@ constexpr float kTwo23 = 8388608.0f;
 constexpr int kFmtCu8 = 0;    // unsigned 8-bit I, Q; x = v - 127
 constexpr int kFmtCs8 = 1;    // signed 8-bit I, Q; x = v
 constexpr int kFmtCs16 = 2;   // signed 16-bit little-endian I, Q; x = v
-constexpr int sample_bytes_of(int fmt) { return fmt == kFmtCs16 ? 4 : 2; }
+constexpr int kFmtCf32 = 4;   // IEEE float32 little-endian I, Q; x = v as stored (3 stays unassigned: rpf_engine.h)
+constexpr int sample_bytes_of(int fmt) { return fmt == kFmtCf32 ? 8 : fmt == kFmtCs16 ? 4 : 2; }
 
 // One sample of a signed format as floats: every int8 / int16 value is a float32 exactly.  raw = the sample's
 // bytes, little-endian (cs8: I | Q << 8; cs16: I | Q << 16).  On the device a sign-extending field extract and
@@ -321,12 +322,18 @@ RPF_HD cf iq_signed(uint32_t raw)
 // workgroup's frame slots, and which byte of that frame.  16-byte pieces (j % 16
 // == 0) are contiguous and 16-byte aligned in the source because T % 8 == 0.
 // (cs16, 4 bytes per sample: rows of 256 bytes, lane l at 4 l + 256 a, a 256*P-byte area.)
+// (cf32, 8 bytes per sample: rows of 512 bytes, lane l at 8 l + 512 a, a 512*P-byte area; a piece is two samples.)
 constexpr int kRawChunk = 128;
 constexpr int raw_chunk_of(int fmt) { return 64 * sample_bytes_of(fmt); }
 template <class G, int FMT = kFmtCu8>
 RPF_HD void raw_source(int wave_in_wg, int j, int* slot, int* byte_in_frame)
 {
-    if constexpr (FMT == kFmtCs16) {
+    if constexpr (FMT == kFmtCf32) {
+        const int a = j / 512;
+        const int tid = wave_in_wg * 64 + ((j % 512) >> 3);
+        *slot = tid / G::T;
+        *byte_in_frame = 8 * (tid % G::T + G::T * a) + (j & 7);
+    } else if constexpr (FMT == kFmtCs16) {
         const int a = j / 256;
         const int tid = wave_in_wg * 64 + ((j % 256) >> 2);
         *slot = tid / G::T;
@@ -345,7 +352,16 @@ RPF_HD void raw_source(int wave_in_wg, int j, int* slot, int* byte_in_frame)
 template <class G, bool WINDOW, int FMT = kFmtCu8>
 RPF_HD void phase_unpack(const uint8_t* lane_raw, float sgn, const float* wsgn, cf* x)
 {
-    if constexpr (FMT != kFmtCu8) {
+    if constexpr (FMT == kFmtCf32) {
+        // the sample is the stored pair of floats: one 8-byte read per point; * sgn exact, * (+-w) rounds once
+#pragma unroll
+        for (int a = 0; a < G::P; ++a) {
+            const cf f = *reinterpret_cast<const cf*>(lane_raw + raw_chunk_of(FMT) * a);
+            if constexpr (WINDOW) x[a] = f * wsgn[a];
+            else x[a] = f * sgn;
+        }
+        return;
+    } else if constexpr (FMT != kFmtCu8) {
         // v is exact, * sgn exact, * (+-w) rounds once
 #pragma unroll
         for (int a = 0; a < G::P; ++a) {

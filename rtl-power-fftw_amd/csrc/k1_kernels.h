@@ -25,7 +25,8 @@ namespace {
 // s_waitcnt vmcnt(N) at the top of the frame loop stays exact.
 // IDX: the frame index type -- long in the single-acquisition kernel, int in the
 // scan kernel (a hop's frames; one 64-bit multiply less per DMA instruction).
-// FMT: the sample format (fft_core.h); 4-byte samples double the pieces and the frame.
+// FMT: the sample format (fft_core.h); 4-byte samples double the pieces and the frame, cf32's 8-byte samples double
+// them again (P / 2 pieces: 8 at P = 16, under the 6-bit vmcnt field at every ring depth in use).
 template <class G, bool DMA, typename IDX, int FMT = kFmtCu8>
 __device__ __forceinline__ void stage_raw(const uint8_t* __restrict__ stream, IDX fb, IDX nframes,
                                           uint8_t* wave_raw, int wave, int lane)
@@ -248,15 +249,19 @@ struct Variant {
 
 // Variant 0 of every K1 size, one finder per translation unit so that the units compile side by side; each answers
 // for its own sample formats and returns null for the others.  find_variant (rpf_kernels.hip) is the one entry the
-// launch code uses and picks among the first four; the series kernels are looked up where they are launched.
+// launch code uses and picks among the first five; the series kernels are looked up where they are launched.
+// cf32 has the plain kernels only: a cf32 engine with statistics runs on the catch-all path and its series run
+// spectrum by spectrum (rpf_engine.cpp).
 //   k1_variant              rpf_kernels.hip                cu8        single, scan, strided
 //   k1_format_variant       rpf_kernels_formats.hip        cs8, cs16  single, scan, strided
+//   k1_cf32_variant         rpf_kernels_cf32.hip           cf32       single, scan, strided
 //   k1_stats_variant        rpf_kernels_stats.hip          cu8        single, strided with per-bin statistics
 //   k1_stats_format_variant rpf_kernels_stats_formats.hip  cs8, cs16  single, strided with per-bin statistics
-//   k1_series_variant       rpf_kernels_series.hip         all three  series
-//   k1_series_stats_variant rpf_kernels_series_stats.hip   all three  series with per-bin statistics
+//   k1_series_variant       rpf_kernels_series.hip         cu8, cs8, cs16 (null for cf32)  series
+//   k1_series_stats_variant rpf_kernels_series_stats.hip   cu8, cs8, cs16 (null for cf32)  series with per-bin statistics
 const Variant* k1_variant(int N, int fmt);
 const Variant* k1_format_variant(int N, int fmt);
+const Variant* k1_cf32_variant(int N, int fmt);
 const Variant* k1_stats_variant(int N, int fmt);
 const Variant* k1_stats_format_variant(int N, int fmt);
 const Variant* k1_series_variant(int N, int fmt);
@@ -324,6 +329,8 @@ template <K1Kernels KERNELS, int FMT, int I>
 Variant default_variant()
 {
     constexpr K1Size s = k1_size(I, FMT, KERNELS == kK1Stats || KERNELS == kK1SeriesStats);
+    static_assert(k1_geometry<Geom<s.N, s.P>>(s.WGO, 1, s.RAWD, FMT, s.TWLDS || s.TWLDSW).lds_bytes <= kLdsPerCU,
+                  "a workgroup's LDS fits the CU");
     return make_variant<s.N, s.P, s.OCC, s.OCCW, false, 0, false, s.RAWD, 0, s.TWLDS, s.WGO, FMT, s.TWLDSW, KERNELS>(0);
 }
 template <K1Kernels KERNELS, int FMT, int... I>

@@ -16,7 +16,7 @@
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     cf* const slab_base = reinterpret_cast<cf*>(smem);                        // [NSLAB][FPW][LDS_CPX]
-    uint8_t* const raw_base = smem + NSLAB * FPW * G::LDS_CPX * sizeof(cf);  // [WG/64][RAWD][128 P]
+    uint8_t* const raw_base = smem + NSLAB * FPW * G::LDS_CPX * sizeof(cf);  // [WG/64][RAWD][RAW_SLOT] bytes
 
     const int tid = threadIdx.x;
     const int fs = tid / T, t = tid % T;
@@ -132,7 +132,7 @@
             exchange_sync<false>();
             RPF_STAMP(clk, 0);                   // waiting for the staged bytes
             phase_unpack<G, WINDOW, FMT>(ring_slot + sample_bytes_of(FMT) * lane, sgn, wsgn, x);
-            // The slot is refilled next: its ds_read_u16 must have RETURNED first (a DMA
+            // The slot is refilled next: its LDS reads must have RETURNED first (a DMA
             // that hits in L2/MALL can land before queued LDS reads execute -- seen as
             // sporadic 1e-3 errors), so wait for this wave's LDS reads, not just issue.
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -1,7 +1,7 @@
 // k1_sizes.h -- K1's per-size geometry, stated once.  Every translation unit that instantiates K1 kernels
-// (rpf_kernels.hip, rpf_kernels_formats.hip, rpf_kernels_stats*.hip, rpf_kernels_series*.hip) builds its table of
-// variant 0 from this list (k1_kernels.h, find_default_variant); only the tuning build's experiments (k1_tuning.inc)
-// name geometries of their own.
+// (rpf_kernels.hip, rpf_kernels_formats.hip, rpf_kernels_cf32.hip, rpf_kernels_stats*.hip, rpf_kernels_series*.hip)
+// builds its table of variant 0 from this list (k1_kernels.h, find_default_variant); only the tuning build's
+// experiments (k1_tuning.inc) name geometries of their own.
 #pragma once
 
 #include "fft_core.h"
@@ -41,11 +41,42 @@ constexpr K1Size kK1Sizes[] = {
 };
 constexpr int kK1SizeCount = sizeof(kK1Sizes) / sizeof(kK1Sizes[0]);
 
-// kRingSmall, the tiny frames of N <= 256: four frames in flight with 2-byte samples, two with cs16's 4-byte samples
-// -- the same bytes in flight and the same LDS, so the same occupancy.  Everywhere else every format keeps two, and
-// cs16's LDS grows by 4N per frame slot (N = 8192: 68 KB slab + 64 KB ring of the CU's 160 KB, one workgroup per CU
-// as with cu8).
-constexpr int ring_depth(int rawd, int fmt) { return rawd != kRingSmall ? rawd : fmt == kFmtCs16 ? 2 : 4; }
+// What the host needs to launch a K1-shaped kernel: workgroup size, frames side by side in it, dynamic LDS.
+struct K1Geometry {
+    int WG, fpw, lds_bytes;
+};
+
+// The workgroup size and the LDS of its frame slots (slabs and raw ring, all but the twiddle table) from plain values,
+// so that k1_size can ask at a run-time row index whether a ring fits.
+constexpr int k1_workgroup(int n, int p, int wgo) { return wgo ? wgo : (n / p >= 256 ? n / p : 256); }
+constexpr int k1_slots_lds(int n, int p, int wgo, int slabs, int rawd, int fmt)
+{
+    return k1_workgroup(n, p, wgo) / (n / p) *
+           (slabs * (n + n / p) * static_cast<int>(sizeof(cf)) + rawd * sample_bytes_of(fmt) * n);
+}
+// G: the frame's Geom; wgo: K1Size::WGO; per frame slot `slabs` exchange slabs (2: double-buffered) and a raw ring
+// of `rawd` frames of format `fmt` (0: no ring, the Bluestein kernel); twtable: the LDS twiddle table, one per
+// workgroup.  The kernels index LDS by the same compile-time quantities (k1_body.inc).
+template <class G>
+constexpr K1Geometry k1_geometry(int wgo, int slabs, int rawd, int fmt, bool twtable)
+{
+    static_assert(G::T == G::N / G::P && G::LDS_CPX == G::N + G::N / G::P, "k1_slots_lds states the slab of Geom");
+    const int wg = k1_workgroup(G::N, G::P, wgo);
+    return K1Geometry{wg, wg / G::T,
+                      k1_slots_lds(G::N, G::P, wgo, slabs, rawd, fmt) +
+                          (twtable ? twlds_entries<G>() * static_cast<int>(sizeof(cf)) : 0)};
+}
+
+// kRingSmall, the tiny frames of N <= 256: four frames in flight with 2-byte samples, two with cs16's 4-byte samples,
+// one with cf32's 8-byte samples -- the same bytes in flight and the same LDS, so the same occupancy.  Everywhere else
+// every format keeps two where they fit (cf32: below), and cs16's LDS grows by 4N per frame slot (N = 8192: 68 KB slab
+// + 64 KB ring of the CU's 160 KB, one workgroup per CU as with cu8).
+constexpr int ring_depth(int rawd, int fmt)
+{
+    return rawd != kRingSmall ? rawd : fmt == kFmtCf32 ? 1 : fmt == kFmtCs16 ? 2 : 4;
+}
+
+constexpr int kLdsPerCU = 160 * 1024;
 
 // Row i as the kernels of sample format `fmt` take it; stats: the kernels with per-bin statistics
 // (RPF_FLAG_BIN_STATS), which depart from the table where the registers run out.  Three double accumulators per bin
@@ -56,10 +87,23 @@ constexpr int ring_depth(int rawd, int fmt) { return rawd != kRingSmall ? rawd :
 // table (4 KB more LDS for both window forms of that size).  Slab, ring and workgroup are the plain kernels'.
 // The series kernels with statistics (rpf_kernels_series_stats.hip) take the same departures and need no further one:
 // 102 .. 134 registers at P = 8, 208 .. 252 of 256 at P = 16, no scratch (profiles/series_stats_resources.txt).
+// cf32 departs where a workgroup with a two-deep ring of 8-byte samples is more than the CU's 160 KB of LDS: 2048 and
+// 4096 (200 KB + the twiddle table) and 8192 (200 KB); 512 (50 KB) and 1024 (102 KB) keep two.  Those three sizes
+// take a ring of depth 1, refilled behind the unpack: the same kernel body with RAWD = 1 -- the counted wait at the
+// top of the frame loop is vmcnt(0), the refill of the one slot is issued as soon as the unpack's LDS reads have
+// returned and has the frame's transform to land in (132 KB + table at 2048 and 4096, 132 KB at 8192).
+// cf32 also gives up the third wave per SIMD where three did not compile without scratch: the windowed kernels of 128
+// and 256 and the plain ones of 1024 take two (256 registers).  None of them had a third workgroup's LDS on the CU
+// to begin with (66 KB, 66 KB and 102 KB per workgroup), so no resident workgroup is lost
+// (profiles/cf32_resources.txt).
 constexpr K1Size k1_size(int i, int fmt, bool stats)
 {
     K1Size s = kK1Sizes[i];
     s.RAWD = ring_depth(s.RAWD, fmt);
+    // (slabs and ring alone decide it: where two frames fit, the twiddle table does too -- default_variant checks)
+    if (fmt == kFmtCf32 && s.RAWD > 1 && k1_slots_lds(s.N, s.P, s.WGO, 1, s.RAWD, fmt) > kLdsPerCU) s.RAWD = 1;
+    if (fmt == kFmtCf32 && (s.N == 128 || s.N == 256)) s.OCCW = 2;
+    if (fmt == kFmtCf32 && s.N == 1024) s.OCC = 2;
     s.TWLDSW = s.TWLDS;
     if (stats) {
         if (s.N == 128 || s.N == 256 || s.N == 1024) s.OCC = s.OCCW = 2;
@@ -67,24 +111,6 @@ constexpr K1Size k1_size(int i, int fmt, bool stats)
         if (s.N == 8192) s.TWLDSW = true;
     }
     return s;
-}
-
-// What the host needs to launch a K1-shaped kernel: workgroup size, frames side by side in it, dynamic LDS.
-struct K1Geometry {
-    int WG, fpw, lds_bytes;
-};
-
-// G: the frame's Geom; wgo: K1Size::WGO; per frame slot `slabs` exchange slabs (2: double-buffered) and a raw ring
-// of `rawd` frames of format `fmt` (0: no ring, the Bluestein kernel); twtable: the LDS twiddle table, one per
-// workgroup.  The kernels index LDS by the same compile-time quantities (k1_body.inc).
-template <class G>
-constexpr K1Geometry k1_geometry(int wgo, int slabs, int rawd, int fmt, bool twtable)
-{
-    const int wg = wgo ? wgo : (G::T >= 256 ? G::T : 256);
-    const int fpw = wg / G::T;
-    return K1Geometry{wg, fpw,
-                      fpw * (slabs * G::LDS_CPX * static_cast<int>(sizeof(cf)) + rawd * sample_bytes_of(fmt) * G::N) +
-                          (twtable ? twlds_entries<G>() * static_cast<int>(sizeof(cf)) : 0)};
 }
 
 }  // namespace rpf

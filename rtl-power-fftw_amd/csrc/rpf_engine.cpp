@@ -853,10 +853,10 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
                         std::to_string(cfg->N) + "; got " + std::to_string(frame_step) + ".");
     const int step = frame_step == 0 ? cfg->N : frame_step;
     const int format = static_cast<int>((cfg->flags >> 16) & 0xfu);
-    if (format != RPF_FORMAT_CU8 && format != RPF_FORMAT_CS8 && format != RPF_FORMAT_CS16)
+    if (format != RPF_FORMAT_CU8 && format != RPF_FORMAT_CS8 && format != RPF_FORMAT_CS16 && format != RPF_FORMAT_CF32)
         return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                    "Sample format must be 0 (cu8), 1 (cs8) or 2 (cs16); got " + std::to_string(format) + ".");
-    const size_t sample_bytes = format == RPF_FORMAT_CS16 ? 4 : 2;
+                    "Sample format must be 0 (cu8), 1 (cs8), 2 (cs16) or 4 (cf32); got " + std::to_string(format) + ".");
+    const size_t sample_bytes = static_cast<size_t>(rpf::sample_bytes_of(format));
     const bool stats = (cfg->flags & RPF_FLAG_BIN_STATS) != 0;
     if (stats && (cfg->flags & RPF_FLAG_FOURSTEP_FUSED))
         return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
@@ -868,7 +868,9 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
     // The catch-all path is the one that reads every format at every N: it takes the engines that ask for it and the
     // signed formats on every size K1 does not serve, whatever family that size runs on with cu8.
     // ... and so do the statistics: a stats engine at any size K1 does not serve runs there.
-    const bool catch_all = (cfg->flags & RPF_FLAG_CATCH_ALL) != 0 || ((format != RPF_FORMAT_CU8 || stats) && !native_k1);
+    // ... and a cf32 engine with statistics at every size: K1 has no cf32 kernels with statistics.
+    const bool catch_all = (cfg->flags & RPF_FLAG_CATCH_ALL) != 0 || ((format != RPF_FORMAT_CU8 || stats) && !native_k1) ||
+                           (format == RPF_FORMAT_CF32 && stats);
     const int variant = static_cast<int>((cfg->flags >> 8) & 0xffu);
     // (asking for the fused four-step kernel is asking for the four-step path)
     // 32768 is served twice, by the split form 2 x 16384 and by the four-step kernels.  Plain runs are faster on the
@@ -1363,7 +1365,7 @@ int rpf_accumulate(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t 
     std::vector<HostBuffer> pieces;
     for (const auto& r : e->registered) {
         if (stream >= r.first && stream + nbytes <= r.first + r.second) {
-            const size_t whole = ~(e->sample_bytes - 1);       // (2 or 4: whole samples)
+            const size_t whole = ~(e->sample_bytes - 1);       // (2, 4 or 8: whole samples)
             const size_t piece = std::min<size_t>(e->coalesce * e->buffer_capacity, static_cast<size_t>(8) << 20) & whole;
             const size_t even = nbytes & whole;
             pieces.reserve(even / piece + 1);
@@ -1414,7 +1416,7 @@ int rpf_accumulate_device(rpf_engine* e, const void* d_stream, size_t nbytes, in
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: acquisition running");
     if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
     if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
     if (reinterpret_cast<uintptr_t>(d_pwr_out) & 15)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: d_pwr_out must be 16-byte aligned");
     DeviceScope on_device(e->device);
@@ -1442,7 +1444,7 @@ int rpf_accumulate_device_stats(rpf_engine* e, const void* d_stream, size_t nbyt
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: acquisition running");
     if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
     if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
     if (reinterpret_cast<uintptr_t>(d_out) & 15)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: d_out must be 16-byte aligned");
     DeviceScope on_device(e->device);
@@ -1467,7 +1469,7 @@ int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: not on an engine with RPF_FLAG_BIN_STATS (use rpf_accumulate_device_stats)");
     if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: acquisition running");
     if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
     if (overlapped(e) && !is_k1(e))
         return fail(e, RPF_ERR_INVALID_ARGUMENT,
                     "rpf_device_fused: overlapped frames (frame step < N) on this size need rpf_accumulate_device");
@@ -1524,7 +1526,7 @@ static int check_hops(rpf_engine* e, const char* who, const void* const* d_strea
         if (repeats[h] < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
         if (!d_streams[h] && nbytes[h]) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL stream");
         if (reinterpret_cast<uintptr_t>(d_streams[h]) & (e->sample_bytes - 1))
-            return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": streams must be at least 2-byte aligned (4-byte for 16-bit samples)");
+            return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": streams must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
         (*frames)[h] = std::min<int64_t>(frames_in(e, nbytes[h]), repeats[h]);
     }
     return RPF_OK;
@@ -1692,7 +1694,7 @@ static int series_device(rpf_engine* e, const char* who, bool want_stats, const 
     int rc = series_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out, want_stats);
     if (rc != RPF_OK) return rc;
     if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
     if (reinterpret_cast<uintptr_t>(d_out) & 15)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
     e->series_launches = 0;
@@ -1849,7 +1851,7 @@ int rpf_accumulate_device_excised(rpf_engine* e, const void* d_stream, size_t nb
     int rc = excise_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi, d_out);
     if (rc != RPF_OK) return rc;
     if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples)");
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
     if (reinterpret_cast<uintptr_t>(d_out) & 15)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
     e->series_launches = 0;

@@ -77,6 +77,30 @@ __global__ __launch_bounds__(kThreads) void gen_load_kernel(const uint8_t* __res
     out[i] = v;
 }
 
+// The same for cf32: the stored pair of floats is the sample.  A kernel of its own, so that the integer formats'
+// loaders stay the instruction streams they were.
+template <bool BLU>
+__global__ __launch_bounds__(kThreads) void gen_load_cf32_kernel(const uint8_t* __restrict__ stream, int N, int M,
+                                                                long total, const float* __restrict__ window,
+                                                                const cf* __restrict__ g, cf* __restrict__ out)
+{
+    const long i = static_cast<long>(blockIdx.x) * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const long f = i / M;
+    const int n = static_cast<int>(i - f * M);
+    cf v = cf{0.0f, 0.0f};
+    if (n < N) {
+        const cf x = *reinterpret_cast<const cf*>(stream + (f * N + n) * 8);
+        if constexpr (BLU) {
+            v = cmul(x, g[n]);
+        } else {
+            const float s = (n & 1) ? -1.0f : 1.0f;
+            v = window ? x * (window[n] * s) : x * s;
+        }
+    }
+    out[i] = v;
+}
+
 __global__ __launch_bounds__(kThreads) void gen_radix2_kernel(const cf* __restrict__ x, cf* __restrict__ y, int M,
                                                              int ls, long total, TwoLevel tw)
 {
@@ -247,7 +271,7 @@ hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const fl
                           const cf* d_bhat, const cf* d_t0, const cf* d_t1, int h, cf* d_scratch, double* d_pwr,
                           bool accumulate, hipStream_t stream, int fmt, bool stats)
 {
-    if (!generic_supported(N) || nframes < 1 || fmt < kFmtCu8 || fmt > kFmtCs16) return hipErrorInvalidValue;
+    if (!generic_supported(N) || nframes < 1 || (fmt != kFmtCf32 && (fmt < kFmtCu8 || fmt > kFmtCs16))) return hipErrorInvalidValue;
     const long M = generic_length(N);
     const bool blu = M != N;
     const int batch = generic_batch(N);
@@ -260,11 +284,15 @@ hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const fl
         const long total = static_cast<long>(nb) * M;
         const unsigned blocks = static_cast<unsigned>((total + kThreads - 1) / kThreads);
         using LoadFn = void (*)(const uint8_t*, int, int, long, const float*, const cf*, cf*);
-        static const LoadFn load[3][2] = {{gen_load_kernel<false, kFmtCu8>, gen_load_kernel<true, kFmtCu8>},
-                                          {gen_load_kernel<false, kFmtCs8>, gen_load_kernel<true, kFmtCs8>},
-                                          {gen_load_kernel<false, kFmtCs16>, gen_load_kernel<true, kFmtCs16>}};
-        hipLaunchKernelGGL(load[fmt][blu ? 1 : 0], dim3(blocks), dim3(kThreads), 0, stream, src, N, static_cast<int>(M), total,
-                           d_window, d_g, d_a);
+        // cf32 has a loader and a table of its own, named first: kernel templates are emitted in the order they are
+        // first named, and the integer formats' loaders keep the place in the code object that they had
+        static const LoadFn load_cf32[2] = {gen_load_cf32_kernel<false>, gen_load_cf32_kernel<true>};
+        static const LoadFn load_int[3][2] = {{gen_load_kernel<false, kFmtCu8>, gen_load_kernel<true, kFmtCu8>},
+                                              {gen_load_kernel<false, kFmtCs8>, gen_load_kernel<true, kFmtCs8>},
+                                              {gen_load_kernel<false, kFmtCs16>, gen_load_kernel<true, kFmtCs16>}};
+        const LoadFn loader = fmt == kFmtCf32 ? load_cf32[blu ? 1 : 0] : load_int[fmt][blu ? 1 : 0];
+        hipLaunchKernelGGL(loader, dim3(blocks), dim3(kThreads), 0, stream, src, N, static_cast<int>(M), total, d_window,
+                           d_g, d_a);
         cf* res = run_fft(d_a, d_b, M, nb, d_t0, d_t1, h, stream);
         if (blu) {
             hipLaunchKernelGGL(gen_mul_conj_kernel, dim3(blocks), dim3(kThreads), 0, stream, res, d_bhat, static_cast<int>(M),

@@ -23,9 +23,9 @@ class Params:
         self.N = N
         # per-bin statistics beside the power (RPF_FLAG_BIN_STATS): Datastore.sum_sq, Datastore.peak
         self.bin_stats = bool(bin_stats)
-        # what one complex sample of the stream is: "cu8" (the reference's), "cs8", "cs16" (RPF_FORMAT_*)
+        # what one complex sample of the stream is: "cu8" (the reference's), "cs8", "cs16", "cf32" (RPF_FORMAT_*)
         if sample_format not in _lib.FORMATS:
-            raise RPFError("Unknown sample format '%s' (one of: cu8, cs8, cs16)." % (sample_format,),
+            raise RPFError("Unknown sample format '%s' (one of: cu8, cs8, cs16, cf32)." % (sample_format,),
                            ReturnValue.InvalidArgument)
         self.sample_format = sample_format
         # frame step S in complex samples (rpf_config::frame_step): frame f = samples [f S, f S + N); None = N
@@ -49,6 +49,15 @@ def frames_for_budget(r0, N, step):
     if r0 < 1 or not step:
         return r0
     return (r0 - 1) * N // step + 1
+
+
+def _as_bytes(stream):
+    """The bytes of a host stream: a complex64 or float32 array (cf32 samples) is viewed as its bytes, anything else
+    is taken as raw bytes."""
+    a = np.asarray(stream)
+    if a.dtype in (np.complex64, np.float32):
+        return np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    return np.ascontiguousarray(a, dtype=np.uint8)
 
 
 def frames_in(nbytes, N, step, sample_bytes=2):
@@ -186,7 +195,7 @@ class Datastore:
     def accumulate(self, stream, repeats=None):
         """Run one acquisition over a contiguous host byte stream through the
         buffer queues.  Returns (pwr copy, repeats_done)."""
-        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        stream = _as_bytes(stream)
         done = ctypes.c_int64()
         self._check(self._lib.rpf_accumulate(
             self._handle, ctypes.c_void_p(stream.ctypes.data), stream.size,
@@ -234,7 +243,7 @@ class Datastore:
     def accumulate_series(self, stream, frames_per_spectrum, max_spectra=None):
         """rpf_accumulate_series: the same on a host byte stream (not through the buffer queues).  Returns
         (K x N array, K); max_spectra None = every whole spectrum the stream holds."""
-        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        stream = _as_bytes(stream)
         if max_spectra is None:
             max_spectra = max(self.frames_in(stream.size) // frames_per_spectrum, 0) if frames_per_spectrum >= 1 else 0
         rows = max(min(max_spectra, self.frames_in(stream.size) // max(frames_per_spectrum, 1)), 0)
@@ -258,7 +267,7 @@ class Datastore:
         """rpf_accumulate_series_stats: the same on a host byte stream (not through the buffer queues).  Returns
         (K x 3 x N array, K), [k, 0] = S1, [k, 1] = S2, [k, 2] = PK; stats.spectral_kurtosis(out[:, 0], out[:, 1],
         frames_per_spectrum) is the spectral kurtosis of every row.  max_spectra None = every whole spectrum."""
-        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        stream = _as_bytes(stream)
         if max_spectra is None:
             max_spectra = max(self.frames_in(stream.size) // frames_per_spectrum, 0) if frames_per_spectrum >= 1 else 0
         rows = max(min(max_spectra, self.frames_in(stream.size) // max(frames_per_spectrum, 1)), 0)
@@ -284,7 +293,7 @@ class Datastore:
         """rpf_accumulate_excised: the same on a host byte stream (not through the buffer queues).  Returns
         (out (3, N): clean, kept, total; mask (K, N) uint8 with 1 = flagged, or None; K).  stats.sk_limits gives
         thresholds; max_spectra None = every whole spectrum the stream holds."""
-        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        stream = _as_bytes(stream)
         if max_spectra is None:
             max_spectra = max(self.frames_in(stream.size) // frames_per_spectrum, 0) if frames_per_spectrum >= 1 else 0
         rows = max(min(max_spectra, self.frames_in(stream.size) // max(frames_per_spectrum, 1)), 0)
@@ -346,7 +355,7 @@ class Datastore:
 
     @property
     def sample_bytes(self):
-        """rpf_sample_bytes: bytes per complex sample of this engine's format (2, 2, 4)."""
+        """rpf_sample_bytes: bytes per complex sample of this engine's format (2, 2, 4, 8)."""
         return self._lib.rpf_sample_bytes(self._handle)
 
     @property

@@ -50,7 +50,7 @@ struct Params {
   int64_t step() const { return frame_step > 0 ? frame_step : N; }
   // What one complex sample of the stream is (RPF_FORMAT_*, --format): cu8, the reference's, unless told otherwise.
   int sample_format = RPF_FORMAT_CU8;
-  int64_t sample_bytes() const { return sample_format == RPF_FORMAT_CS16 ? 4 : 2; }
+  int64_t sample_bytes() const { return sample_format == RPF_FORMAT_CF32 ? 8 : sample_format == RPF_FORMAT_CS16 ? 4 : 2; }
   // bytes `frames` frames span (rpf_frame_span): bN + bS (frames - 1), b bytes per sample
   int64_t frame_span(int64_t frames) const { return frames < 1 ? 0 : sample_bytes() * (static_cast<int64_t>(N) + step() * (frames - 1)); }
   // a sample budget of r0 side-by-side frames as frames at step S: floor((r0 - 1) N / S) + 1 (r0 at S = N)

@@ -53,7 +53,8 @@ const Spec kSpecs[] = {
     // additive (not in the reference)
     {0, "input", Kind::Text, "file|-", "Replay interleaved IQ samples (see --format) from a file or stdin."},
     {0, "format", Kind::Text, "cu8|cs8|cs16",
-     "Sample format of --input: cu8 (unsigned 8-bit, the default), cs8 (signed 8-bit), cs16 (signed 16-bit little-endian)."},
+     "Sample format of --input: cu8 (unsigned 8-bit, the default), cs8 (signed 8-bit), cs16 (signed 16-bit little-endian); "
+     "also cf32 (float32 little-endian I/Q, taken as stored: no scaling)."},
     {0, "synthetic", Kind::Int64, "seed", "Use the built-in synthetic receiver instead of a dongle."},
     {0, "gpu", Kind::Int, "ordinal", "HIP device to run on."},
     {0, "gpus", Kind::Text, "a,b,...", "HIP devices to spread a scan over (one engine per listed device)."},
@@ -284,13 +285,14 @@ Options parse_command_line(int argc, const char* const* argv)
         if (text == "cu8") o.sample_format = RPF_FORMAT_CU8;
         else if (text == "cs8") o.sample_format = RPF_FORMAT_CS8;
         else if (text == "cs16") o.sample_format = RPF_FORMAT_CS16;
+        else if (text == "cf32") o.sample_format = RPF_FORMAT_CF32;
         else
             throw RPFexception("Unknown sample format given to --format: " + text + ".\n"
-                               "Expecting one of cu8, cs8, cs16. Exiting.", ReturnValue::InvalidArgument);
+                               "Expecting one of cu8, cs8, cs16, cf32. Exiting.", ReturnValue::InvalidArgument);
         // the format describes a replayed file; a dongle and the synthetic receiver deliver cu8
         if (o.sample_format != RPF_FORMAT_CU8 && !p.has("input"))
             throw RPFexception("Option --format " + text + " needs --input: a dongle and --synthetic deliver cu8 "
-                               "(one of cu8, cs8, cs16). Exiting.", ReturnValue::InvalidArgument);
+                               "(one of cu8, cs8, cs16, cf32). Exiting.", ReturnValue::InvalidArgument);
     }
     if (p.has("repeats")) o.repeats = to_number<int64_t>(*find_spec("--repeats"), p.get("repeats"));
     else o.repeats = o.frames_for_budget(o.buf_length / (o.sample_bytes() * o.N));  // params.cxx:214-217, as a sample budget

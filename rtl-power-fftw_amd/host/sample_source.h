@@ -45,7 +45,7 @@ protected:
     int64_t frequency_ = 0;
 };
 
-// Interleaved I/Q from a file or stdin ("-"), `sample_bytes` bytes per complex sample (2: cu8 / cs8, 4: cs16); a
+// Interleaved I/Q from a file or stdin ("-"), `sample_bytes` bytes per complex sample (2: cu8 / cs8, 4: cs16, 8: cf32); a
 // short read ends the data.
 class FileSource : public SampleSource {
 public:

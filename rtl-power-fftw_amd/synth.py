@@ -102,6 +102,26 @@ def noise_tones_cs16(seed, nsamples, chunk=1 << 21):
     return out.view(np.uint8)
 
 
+# ---- float32 samples (rpf_engine.h RPF_FORMAT_CF32) ----
+def to_cf32(cs16_stream, scale=1.0):
+    """The cf32 stream (complex64 array, I + jQ) holding the int16 values of `cs16_stream` times `scale`: with scale 1
+    the stream a cf32 engine must read as the cs16 engine reads the original; a power of two scales exactly."""
+    v = cs16_values(cs16_stream).astype(np.float32) * np.float32(scale)
+    return np.ascontiguousarray(v).view(np.complex64)
+
+
+def gaussian_cf32(seed, nsamples, sigma=1.0):
+    """Complex Gaussian noise with full float32 mantissas, sigma per component, plus a complex tone of period 8 and
+    amplitude sigma / 2: nsamples complex64 values (8 * nsamples bytes, I then Q, little-endian on every host this
+    runs on)."""
+    rng = np.random.default_rng(seed)
+    z = rng.standard_normal((nsamples, 2)) * sigma
+    k = np.arange(nsamples)
+    z[:, 0] += 0.5 * sigma * np.cos(2 * np.pi * k / 8)
+    z[:, 1] += 0.5 * sigma * np.sin(2 * np.pi * k / 8)
+    return np.ascontiguousarray(z.astype("<f4")).view(np.complex64).reshape(-1)
+
+
 def _wrap64(v):
     """A 64-bit pattern as the signed Python int torch's int64 holds."""
     v &= (1 << 64) - 1
