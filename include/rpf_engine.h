@@ -36,7 +36,8 @@ extern "C" {
                                RPF_FLAG_BIN_STATS, rpf_has_bin_stats, rpf_get_bin_stats, rpf_accumulate_device_stats;
                                rpf_accumulate_device_series, rpf_accumulate_series, rpf_series_launches;
                                rpf_accumulate_device_series_stats, rpf_accumulate_series_stats;
-                               rpf_accumulate_device_excised, rpf_accumulate_excised */
+                               rpf_accumulate_device_excised, rpf_accumulate_excised;
+                               rpf_engine_create_pfb, rpf_pfb_taps */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -157,6 +158,37 @@ const char* rpf_last_global_error(void);
  * the producer fills directly), FFT plan (= twiddle tables on the device),
  * zeroed pwr[N] and queue_histogram[n_buffers+1]. */
 int rpf_engine_create(const rpf_config* cfg, rpf_engine** out);
+/* Polyphase filter bank (PFB) front end: an engine whose every frame is T N samples weighted by a prototype filter and
+ * folded to N before the transform, which makes a channel flat-topped and isolates it from its neighbours.  Everything
+ * that computes or checks it refers to this definition.
+ *   Fold.  T = taps >= 1, h[0 .. T N) = coeffs (float32, copied).  The samples x are converted to float32 exactly, as the
+ *     engine's format defines it (cu8: v - 127; cs8, cs16, cf32: v).  Output frame f, n in [0, N), I and Q separately:
+ *         z = h[n] * x[f N + n]                                    (one float32 rounding)
+ *         z = fmaf(h[t N + n], x[(f + t) N + n], z)   for t = 1 .. T-1, in increasing t
+ *     with no contraction or reassociation beyond this (csrc/pfb_core.h).  The (-1)^n is not applied here.
+ *   Spectrum.  What a RECTANGULAR cf32 engine of the same N computes from the frames z_f laid side by side (N is even, so
+ *     (-1)^(tN+n) = (-1)^n and the cf32 kernels' own (-1)^n puts DC in the middle of the folded frame): bit for bit that,
+ *     wherever the two launch the same grid on the same staging route.  Powers of two 64 .. 8192 run the LDS-resident
+ *     kernel's cf32 form, every other even N the catch-all path, as a cf32 engine does; rpf_last_launch_info reports the
+ *     transform launch.  The fold is one memory-bound launch (csrc/rpf_pfb.hip) per at most 64 MB of folded frames, in
+ *     front of the unchanged transform; chunks after the first add into the output, so more than 64 MB of frames agree
+ *     with the one-launch sum up to the grouping of the double additions.
+ *   Frames.  Frame f spans the samples [f N, f N + T N): a stream of B bytes holds frames(B) = B < bTN ? 0 :
+ *     (B - bTN) / (bN) + 1 frames and `frames` frames span bN (T - 1 + frames) bytes, b bytes per input sample.
+ *     rpf_frames_in, rpf_frame_span, the frame quota of rpf_finish and every entry point count that way; the buffer queue
+ *     carries up to a whole span from one staging slot to the next.  T = 1: one multiplication per sample.
+ *   cfg is as for rpf_engine_create; its sample format is the INPUT format (all four), which rpf_sample_bytes and
+ *     rpf_sample_format report.
+ * RPF_ERR_INVALID_ARGUMENT before any device is touched: taps < 1, taps > 32 or taps x N > 2^26; coeffs NULL; cfg->window
+ * non-NULL (the coefficients are the window); frame_step neither 0 nor N; RPF_FLAG_BIN_STATS; RPF_FLAG_FOURSTEP_FUSED; a
+ * kernel variant other than 0.
+ * On a PFB engine rpf_accumulate_device, the buffer queue (rpf_begin .. rpf_finish) and rpf_accumulate work;
+ * rpf_accumulate_device_hops runs hop by hop, as on an engine with overlapped frames; rpf_device_fused,
+ * rpf_device_fused_hops, rpf_device_reduce and the series, series-stats and excised entries return
+ * RPF_ERR_INVALID_ARGUMENT.  An engine without PFB takes exactly the path it took. */
+int rpf_engine_create_pfb(const rpf_config* cfg, int taps, const float* coeffs /* taps x N, copied */, rpf_engine** out);
+/* T of a PFB engine, 0 for an engine without PFB, -1 for NULL. */
+int rpf_pfb_taps(const rpf_engine* e);
 /* Datastore::~Datastore (datastore.cxx:36-46). */
 void rpf_engine_destroy(rpf_engine* e);
 const char* rpf_last_error(const rpf_engine* e);

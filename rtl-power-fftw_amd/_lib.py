@@ -75,6 +75,9 @@ _SYMBOLS = [
     ("rpf_supported_n", ctypes.c_int, [ctypes.c_int]),
     ("rpf_last_global_error", ctypes.c_char_p, []),
     ("rpf_engine_create", ctypes.c_int, [ctypes.POINTER(rpf_config), ctypes.POINTER(_P)]),
+    ("rpf_engine_create_pfb", ctypes.c_int, [ctypes.POINTER(rpf_config), ctypes.c_int, ctypes.POINTER(ctypes.c_float),
+                                             ctypes.POINTER(_P)]),
+    ("rpf_pfb_taps", ctypes.c_int, [_P]),
     ("rpf_engine_destroy", None, [_P]),
     ("rpf_last_error", ctypes.c_char_p, [_P]),
     ("rpf_begin", ctypes.c_int, [_P, ctypes.c_int64]),

@@ -166,6 +166,12 @@ struct rpf_engine {
     double* d_excise_state = nullptr;     // the (row group, bin) accumulators, then 3 N doubles: the host entry's result
     uint8_t* d_excise_mask = nullptr;     // the host entry's mask bytes of one piece
     size_t excise_mask_bytes = 0;
+    // polyphase filter bank front end (rpf_engine_create_pfb): this engine owns the queues and the fold, `inner` the transform
+    int taps = 0;                         // T; 0 = an engine without PFB
+    float* d_pfb_coeffs = nullptr;        // h[T x N]
+    rpf_engine* inner = nullptr;          // a rectangular cf32 engine of the same N, device and staging flag
+    float* d_pfb_z = nullptr;             // one chunk of folded frames, float32 I/Q side by side; allocated at the first launch
+    int64_t pfb_chunk_frames = 0;         // ... frames it holds (kGatherBytes / 8N, at least one)
 
     mutable std::string last_error;
 };
@@ -198,17 +204,20 @@ int fail(rpf_engine* e, int rc, const std::string& msg)
     return rc;
 }
 
-// frames(B) of a stream of B bytes at frame step S: frame f is bytes [bfS, bfS + bN), b bytes per sample.
+// Samples one frame spans: N, or T N on a PFB engine (whose frames advance by N).
+size_t span_samples(const rpf_engine* e) { return static_cast<size_t>(e->N) * static_cast<size_t>(std::max(e->taps, 1)); }
+
+// frames(B) of a stream of B bytes at frame step S: frame f is bytes [bfS, bfS + b span), b bytes per sample.
 int64_t frames_in(const rpf_engine* e, size_t nbytes)
 {
-    const size_t frame = e->sample_bytes * static_cast<size_t>(e->N), step = e->sample_bytes * static_cast<size_t>(e->step);
+    const size_t frame = e->sample_bytes * span_samples(e), step = e->sample_bytes * static_cast<size_t>(e->step);
     return nbytes < frame ? 0 : static_cast<int64_t>((nbytes - frame) / step + 1);
 }
 
-// Bytes `frames` frames span: bN + bS (frames - 1).
+// Bytes `frames` frames span: b span + bS (frames - 1).
 size_t frame_span(const rpf_engine* e, int64_t frames)
 {
-    return frames < 1 ? 0 : e->sample_bytes * (static_cast<size_t>(e->N) + static_cast<size_t>(e->step) * static_cast<size_t>(frames - 1));
+    return frames < 1 ? 0 : e->sample_bytes * (span_samples(e) + static_cast<size_t>(e->step) * static_cast<size_t>(frames - 1));
 }
 
 bool overlapped(const rpf_engine* e) { return e->step != e->N; }
@@ -449,6 +458,31 @@ int launch_gathered(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, dou
     return RPF_OK;
 }
 
+// A PFB engine: chunks of at most kGatherBytes of folded frames are produced in e->d_pfb_z (rpf_pfb.hip: one fold launch
+// over the chunk's n + T - 1 input frames) and the inner cf32 engine's unchanged transform + reduce runs over each, the
+// chunks after the first adding into d_out -- what launch_gathered does for overlapped frames.  The scratch comes from
+// hipMalloc, so the inner launch sees a 16-byte aligned stream and stages it through LDS-DMA unless told not to.
+int launch_pfb(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out, bool accumulate, hipStream_t stream)
+{
+    const size_t zframe = sizeof(float) * 2 * static_cast<size_t>(e->N);
+    if (!e->d_pfb_z) {
+        e->pfb_chunk_frames = std::max<int64_t>(1, static_cast<int64_t>(rpf::kGatherBytes / zframe));
+        void* p = nullptr;
+        HIP_TRY(e, hipMalloc(&p, static_cast<size_t>(e->pfb_chunk_frames) * zframe));
+        e->d_pfb_z = static_cast<float*>(p);
+    }
+    const size_t row = e->sample_bytes * static_cast<size_t>(e->N);
+    for (int64_t f0 = 0; f0 < nframes; f0 += e->pfb_chunk_frames) {
+        const int64_t n = std::min(e->pfb_chunk_frames, nframes - f0);
+        HIP_TRY(e, rpf::launch_pfb_fold(d_frames + static_cast<size_t>(f0) * row, n, e->N, e->taps, e->format, e->d_pfb_coeffs,
+                                        e->d_pfb_z, stream));
+        const int rc = launch_side_by_side(e->inner, reinterpret_cast<const uint8_t*>(e->d_pfb_z), n, d_out, accumulate || f0 > 0,
+                                           stream, nullptr, false);
+        if (rc != RPF_OK) return fail(e, rc, e->inner->last_error);
+    }
+    return RPF_OK;
+}
+
 // Transform + reduce for `nframes` frames starting at d_frames.
 // slot_verdict: the queue path's pinned word for this launch -- if a fused launch gives up, K3 leaves d_out as it
 // is, the word becomes 1 and the worker re-runs the bytes on K2a/K2b (recover_fused); null (the device-resident
@@ -459,6 +493,7 @@ int launch_frames(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, doubl
                   bool accumulate, hipStream_t stream, unsigned* slot_verdict = nullptr, bool want_stats = false)
 {
     if (nframes <= 0) return RPF_OK;
+    if (e->taps) return launch_pfb(e, d_frames, nframes, d_out, accumulate, stream);
     if (overlapped(e) && !is_k1(e)) return launch_gathered(e, d_frames, nframes, d_out, accumulate, stream, want_stats);
     return launch_side_by_side(e, d_frames, nframes, d_out, accumulate, stream, slot_verdict, want_stats);
 }
@@ -665,7 +700,8 @@ void worker_main(rpf_engine* e)
         WORKER_TRY(hipEventRecord(cur->kernel_done, e->compute_stream), "hipEventRecord(kernel_done)");
         cur->in_flight = ok();
         // the unfinished frame (if any) stays in this slot until the next one is launched: what follows the last
-        // frame's start + 2S, < 2N bytes (everything, before the first frame is complete)
+        // frame's start + bS, less than a frame's span -- bN bytes, b T N on a PFB engine -- (everything, before the
+        // first frame is complete)
         const size_t consumed = static_cast<size_t>(std::max<int64_t>(nframes, 0)) * step_bytes;
         carry = (frames_issued < e->repeats) ? avail - consumed : 0;
         carry_src = dst + off - carry;
@@ -804,6 +840,13 @@ void release_device(rpf_engine* e)
     if (e->d_series_out) (void)hipFree(e->d_series_out);
     if (e->d_excise_state) (void)hipFree(e->d_excise_state);
     if (e->d_excise_mask) (void)hipFree(e->d_excise_mask);
+    if (e->d_pfb_coeffs) (void)hipFree(e->d_pfb_coeffs);
+    if (e->d_pfb_z) (void)hipFree(e->d_pfb_z);
+    if (e->inner) {
+        release_device(e->inner);
+        delete e->inner;
+        e->inner = nullptr;
+    }
     if (e->d_pwr) (void)hipFree(e->d_pwr);
     for (auto& s : e->staging) {
         if (s.base) (void)hipFree(s.base);
@@ -836,7 +879,18 @@ int rpf_supported_n(int N)
 
 const char* rpf_last_global_error(void) { return g_last_error.c_str(); }
 
-int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
+}  // extern "C"
+
+namespace {
+
+struct PfbSpec {
+    int taps;
+    const float* coeffs;      // taps x N
+};
+
+// rpf_engine_create (pfb null) and rpf_engine_create_pfb.  inner_of_pfb: the transform engine a PFB engine owns -- it is
+// never fed through its queues, so its staging slots hold one (minimal) buffer each.
+int create_engine(const rpf_config* cfg, const PfbSpec* pfb, bool inner_of_pfb, rpf_engine** out)
 {
     if (!out) return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "rpf_engine_create: out is NULL");
     *out = nullptr;
@@ -864,6 +918,32 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
     if (stats && ((cfg->flags >> 8) & 0xffu) != 0)
         return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
                     "RPF_FLAG_BIN_STATS does not combine with a kernel variant other than 0.");
+    if (pfb) {
+        // (include/rpf_engine.h, rpf_engine_create_pfb: all of it before any device is touched)
+        if (pfb->taps < 1 || pfb->taps > rpf::kPfbMaxTaps)
+            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
+                        "Number of PFB taps must be between 1 and " + std::to_string(rpf::kPfbMaxTaps) + "; got " +
+                            std::to_string(pfb->taps) + ".");
+        if (static_cast<int64_t>(pfb->taps) * cfg->N > (static_cast<int64_t>(1) << 26))
+            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
+                        "PFB taps x bins must not exceed 67108864; got " + std::to_string(pfb->taps) + " x " +
+                            std::to_string(cfg->N) + ".");
+        if (!pfb->coeffs) return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "rpf_engine_create_pfb: coeffs is NULL");
+        if (cfg->window)
+            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
+                        "A PFB engine takes no window: the PFB coefficients are the window.");
+        if (step != cfg->N)
+            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
+                        "PFB frames advance by the number of bins: frame_step must be 0 or " + std::to_string(cfg->N) + "; got " +
+                            std::to_string(frame_step) + ".");
+        if (stats)
+            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "PFB does not combine with RPF_FLAG_BIN_STATS.");
+        if (cfg->flags & RPF_FLAG_FOURSTEP_FUSED)
+            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
+                        "PFB does not combine with RPF_FLAG_FOURSTEP_FUSED: the folded frames run on K1 or on the catch-all path.");
+        if (((cfg->flags >> 8) & 0xffu) != 0)
+            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "PFB does not combine with a kernel variant other than 0.");
+    }
     const bool native_k1 = rpf::kernel_supported(cfg->N, 0);
     // The catch-all path is the one that reads every format at every N: it takes the engines that ask for it and the
     // signed formats on every size K1 does not serve, whatever family that size runs on with cu8.
@@ -886,7 +966,8 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
     const bool tuned = !catch_all && (fourstep || mixed || bluestein || bigblu ||
                                       (rpf::kernel_supported(cfg->N, variant) && (format == RPF_FORMAT_CU8 || variant == 0)));
     const bool generic = !tuned && variant == 0 && rpf::generic_supported(cfg->N);
-    if (!tuned && !generic)
+    // (a PFB engine transforms nothing itself: what counts is that its inner cf32 engine has a kernel)
+    if (pfb ? !(native_k1 || rpf::generic_supported(cfg->N)) : (!tuned && !generic))
         return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
                     "No gfx950 kernel for " + std::to_string(cfg->N) +
                         " bins in this build (supported: every even N up to 8388608 and the powers of two up to 67108864).");
@@ -925,11 +1006,12 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
         e->sum_sq.assign(e->N, 0.0);
         e->peak.assign(e->N, 0.0);
     }
-    e->fourstep = fourstep;
-    e->mixed = mixed;
-    e->bluestein = bluestein;
-    e->bigblu = bigblu;
-    e->generic = generic;
+    e->fourstep = !pfb && fourstep;
+    e->mixed = !pfb && mixed;
+    e->bluestein = !pfb && bluestein;
+    e->bigblu = !pfb && bigblu;
+    e->generic = !pfb && generic;
+    e->taps = pfb ? pfb->taps : 0;
     e->queue_histogram.assign(e->n_buffers + 1, 0);
     e->pwr.assign(e->N, 0.0);
 
@@ -953,129 +1035,131 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
     for (hipStream_t& cs : e->copy_streams) CREATE_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     CREATE_TRY(hipStreamCreateWithFlags(&e->compute_stream, hipStreamNonBlocking));
 
-    // "plan": twiddle table on the device (where fftwf_plan_dft_1d stands, datastore.cxx:32)
-    std::vector<rpf::cf> tw;
-    int blu_m1 = 0, blu_m2 = 0;
-    if (e->bigblu) rpf::bigblu_lengths(e->N, &e->blu_M, &blu_m1, &blu_m2);
-    if (!e->generic) {
-        rpf::make_twiddles(e->bluestein ? rpf::bluestein_length(e->N) : e->bigblu ? e->blu_M : e->N, tw);
-        CREATE_TRY(hipMalloc(&e->d_twiddles, sizeof(rpf::cf) * tw.size()));
-        CREATE_TRY(hipMemcpy(e->d_twiddles, tw.data(), sizeof(rpf::cf) * tw.size(), hipMemcpyHostToDevice));
-    }
-    if (e->has_window) {
-        CREATE_TRY(hipMalloc(&e->d_window, sizeof(float) * e->N));
-        CREATE_TRY(hipMemcpy(e->d_window, cfg->window, sizeof(float) * e->N, hipMemcpyHostToDevice));
-    }
-    size_t partial_slots = 0, partial_len = e->N;
-    std::vector<float> blu_g, blu_bhat;
-    const bool gen_blu = e->generic && rpf::generic_length(e->N) != e->N;
-    if (e->bluestein || e->bigblu || gen_blu) {
-        std::vector<float>&g = blu_g, &bhat = blu_bhat;
-        rpf::make_bluestein_tables(e->N, cfg->window, g, bhat);
-        CREATE_TRY(hipMalloc(&e->d_chirp, sizeof(float) * g.size()));
-        CREATE_TRY(hipMemcpy(e->d_chirp, g.data(), sizeof(float) * g.size(), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc(&e->d_bhat, sizeof(float) * bhat.size()));
-        CREATE_TRY(hipMemcpy(e->d_bhat, bhat.data(), sizeof(float) * bhat.size(), hipMemcpyHostToDevice));
-    }
-    if (e->generic) {
-        std::vector<rpf::cf> t0, t1;
-        rpf::generic_twiddle_tables(e->N, t0, t1, &e->gen_h);
-        CREATE_TRY(hipMalloc(&e->d_tw_sub, sizeof(rpf::cf) * t0.size()));
-        CREATE_TRY(hipMemcpy(e->d_tw_sub, t0.data(), sizeof(rpf::cf) * t0.size(), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc(&e->d_tw_sub2, sizeof(rpf::cf) * t1.size()));
-        CREATE_TRY(hipMemcpy(e->d_tw_sub2, t1.data(), sizeof(rpf::cf) * t1.size(), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc(&e->d_scratch, rpf::generic_scratch_bytes(e->N)));
-        hipDeviceProp_t prop;
-        CREATE_TRY(hipGetDeviceProperties(&prop, e->device));
-        e->plan.grid = prop.multiProcessorCount;
-        e->plan.block = 256;
-        e->plan.fpw = rpf::generic_batch(e->N);
-        e->plan.lds_bytes = 0;
-        partial_slots = e->stats ? rpf::kStatsPlanes : 1;
-    } else if (e->mixed) {
-        CREATE_TRY(rpf::plan_mixed(e->N, e->variant, e->has_window, e->device, &e->plan));
-        partial_slots = e->plan.grid;
-    } else if (e->bluestein) {
-        CREATE_TRY(rpf::plan_bluestein(e->N, e->device, &e->plan));
-        partial_slots = e->plan.grid;
-    } else if (e->bigblu) {
-        CREATE_TRY(rpf::bigblu_prepare(e->N, e->device, &e->plan));
-        std::vector<rpf::cf> tws;
-        rpf::make_twiddles(blu_m1, tws);
-        CREATE_TRY(hipMalloc(&e->d_tw_sub, sizeof(rpf::cf) * tws.size()));
-        CREATE_TRY(hipMemcpy(e->d_tw_sub, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
-        rpf::make_twiddles(blu_m2, tws);
-        CREATE_TRY(hipMalloc(&e->d_tw_sub2, sizeof(rpf::cf) * tws.size()));
-        CREATE_TRY(hipMemcpy(e->d_tw_sub2, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
-        // (the intermediate starts at 256 MB and grows with the launches: ensure_scratch)
-        e->scratch_per_frame = rpf::bigblu_scratch_bytes_per_frame(e->N);
-        e->scratch_max = rpf::bigblu_scratch_bytes(e->N);
-        e->scratch_bytes = std::min<size_t>(e->scratch_max, std::max<size_t>(e->scratch_per_frame, static_cast<size_t>(256) << 20));
-        CREATE_TRY(hipMalloc(&e->d_scratch, e->scratch_bytes));
-        partial_slots = rpf::bigblu_partial_slots(e->N);
-        partial_len = e->blu_M;
-        // the kernels read chirp, kernel spectrum and inter-step twiddles in their own lane order
-        std::vector<rpf::cf> g_t, bhat_t, step_tw, step_tw2;
-        rpf::bigblu_tables(e->N, reinterpret_cast<const rpf::cf*>(blu_g.data()),
-                           reinterpret_cast<const rpf::cf*>(blu_bhat.data()), g_t, bhat_t, step_tw, step_tw2);
-        (void)hipFree(e->d_chirp);
-        e->d_chirp = nullptr;
-        CREATE_TRY(hipMalloc(&e->d_chirp, sizeof(rpf::cf) * g_t.size()));
-        CREATE_TRY(hipMemcpy(e->d_chirp, g_t.data(), sizeof(rpf::cf) * g_t.size(), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMemcpy(e->d_bhat, bhat_t.data(), sizeof(rpf::cf) * bhat_t.size(), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMemcpy(e->d_twiddles, step_tw.data(), sizeof(rpf::cf) * step_tw.size(), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc(&e->d_step2, sizeof(rpf::cf) * step_tw2.size()));
-        CREATE_TRY(hipMemcpy(e->d_step2, step_tw2.data(), sizeof(rpf::cf) * step_tw2.size(), hipMemcpyHostToDevice));
-    } else if (e->fourstep) {
-        CREATE_TRY(rpf::fourstep_prepare(e->N, e->device, &e->plan));
-        int n1 = 0, n2 = 0;
-        rpf::fourstep_sub_lengths(e->N, &n1, &n2);
-        std::vector<rpf::cf> tws;
-        rpf::make_twiddles(n1, tws);
-        CREATE_TRY(hipMalloc(&e->d_tw_sub, sizeof(rpf::cf) * tws.size()));
-        CREATE_TRY(hipMemcpy(e->d_tw_sub, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
-        rpf::make_twiddles(n2, tws);
-        CREATE_TRY(hipMalloc(&e->d_tw_sub2, sizeof(rpf::cf) * tws.size()));
-        CREATE_TRY(hipMemcpy(e->d_tw_sub2, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
-        // The fused kernel (one persistent launch, the intermediate stays in each XCD's L2) where
-        // the device is the 8 x 32-CU part it is written for and its teams assemble; else K2a/K2b.
-        int fused_grid = 0;
-        // (overlapped frames: the two-kernel path -- the fused kernel's give-up verdict is one word per staging slot,
-        // which the gather path's several launches per slot would share)
-        if (!(cfg->flags & RPF_FLAG_NO_FOURSTEP_FUSED) && step == e->N &&
-            rpf::fourstep_fused_prepare(e->N, e->device, &fused_grid) == hipSuccess) {
-            CREATE_TRY(hipMalloc(&e->d_fused_scratch, rpf::fourstep_fused_scratch_bytes(e->N)));
-            CREATE_TRY(hipMalloc(&e->d_fused_ctl, rpf::fourstep_fused_ctl_bytes()));
-            CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->h_fused_words), 64, hipHostMallocMapped));
-            std::memset(e->h_fused_words, 0, 64);
-            CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->d_fused_words), e->h_fused_words, 0));
-            e->fused = true;
-            // (room for either path's partial spectra: a fused launch that gives up is re-run on K2a/K2b)
-            partial_slots = std::max<size_t>(rpf::fourstep_fused_slots(e->N), rpf::fourstep_partial_slots(e->N));
-        } else {
-            (void)hipGetLastError();
-            e->scratch_per_frame = rpf::fourstep_scratch_bytes_per_frame(e->N);
-            e->scratch_max = rpf::fourstep_scratch_bytes(e->N);
-            e->scratch_bytes = std::min<size_t>(e->scratch_max, static_cast<size_t>(256) << 20);
-            CREATE_TRY(hipMalloc(&e->d_scratch, e->scratch_bytes));
-            partial_slots = rpf::fourstep_partial_slots(e->N);
+    if (!pfb) {
+        // "plan": twiddle table on the device (where fftwf_plan_dft_1d stands, datastore.cxx:32)
+        std::vector<rpf::cf> tw;
+        int blu_m1 = 0, blu_m2 = 0;
+        if (e->bigblu) rpf::bigblu_lengths(e->N, &e->blu_M, &blu_m1, &blu_m2);
+        if (!e->generic) {
+            rpf::make_twiddles(e->bluestein ? rpf::bluestein_length(e->N) : e->bigblu ? e->blu_M : e->N, tw);
+            CREATE_TRY(hipMalloc(&e->d_twiddles, sizeof(rpf::cf) * tw.size()));
+            CREATE_TRY(hipMemcpy(e->d_twiddles, tw.data(), sizeof(rpf::cf) * tw.size(), hipMemcpyHostToDevice));
         }
-        // K2a reads the inter-step twiddles and the window in its own lane order
-        std::vector<rpf::cf> step_tw;
-        std::vector<float> window_t;
-        rpf::fourstep_tables(e->N, cfg->window, step_tw, window_t);
-        CREATE_TRY(hipMemcpy(e->d_twiddles, step_tw.data(), sizeof(rpf::cf) * step_tw.size(), hipMemcpyHostToDevice));
-        if (e->has_window)
-            CREATE_TRY(hipMemcpy(e->d_window, window_t.data(), sizeof(float) * window_t.size(), hipMemcpyHostToDevice));
-    } else {
-        CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, true, e->device, &e->plan, e->format, e->stats));
-        rpf::LaunchInfo tmp;
-        CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, false, e->device, &tmp, e->format, e->stats));
-        e->plan.grid = std::min(e->plan.grid, tmp.grid);
-        partial_slots = e->plan.grid + rpf::kMaxHops;    // a workgroup leaves one partial per hop it touches
-        if (e->stats) partial_slots = static_cast<size_t>(e->plan.grid) * rpf::kStatsPlanes;   // three planes per workgroup, no scans
+        if (e->has_window) {
+            CREATE_TRY(hipMalloc(&e->d_window, sizeof(float) * e->N));
+            CREATE_TRY(hipMemcpy(e->d_window, cfg->window, sizeof(float) * e->N, hipMemcpyHostToDevice));
+        }
+        size_t partial_slots = 0, partial_len = e->N;
+        std::vector<float> blu_g, blu_bhat;
+        const bool gen_blu = e->generic && rpf::generic_length(e->N) != e->N;
+        if (e->bluestein || e->bigblu || gen_blu) {
+            std::vector<float>&g = blu_g, &bhat = blu_bhat;
+            rpf::make_bluestein_tables(e->N, cfg->window, g, bhat);
+            CREATE_TRY(hipMalloc(&e->d_chirp, sizeof(float) * g.size()));
+            CREATE_TRY(hipMemcpy(e->d_chirp, g.data(), sizeof(float) * g.size(), hipMemcpyHostToDevice));
+            CREATE_TRY(hipMalloc(&e->d_bhat, sizeof(float) * bhat.size()));
+            CREATE_TRY(hipMemcpy(e->d_bhat, bhat.data(), sizeof(float) * bhat.size(), hipMemcpyHostToDevice));
+        }
+        if (e->generic) {
+            std::vector<rpf::cf> t0, t1;
+            rpf::generic_twiddle_tables(e->N, t0, t1, &e->gen_h);
+            CREATE_TRY(hipMalloc(&e->d_tw_sub, sizeof(rpf::cf) * t0.size()));
+            CREATE_TRY(hipMemcpy(e->d_tw_sub, t0.data(), sizeof(rpf::cf) * t0.size(), hipMemcpyHostToDevice));
+            CREATE_TRY(hipMalloc(&e->d_tw_sub2, sizeof(rpf::cf) * t1.size()));
+            CREATE_TRY(hipMemcpy(e->d_tw_sub2, t1.data(), sizeof(rpf::cf) * t1.size(), hipMemcpyHostToDevice));
+            CREATE_TRY(hipMalloc(&e->d_scratch, rpf::generic_scratch_bytes(e->N)));
+            hipDeviceProp_t prop;
+            CREATE_TRY(hipGetDeviceProperties(&prop, e->device));
+            e->plan.grid = prop.multiProcessorCount;
+            e->plan.block = 256;
+            e->plan.fpw = rpf::generic_batch(e->N);
+            e->plan.lds_bytes = 0;
+            partial_slots = e->stats ? rpf::kStatsPlanes : 1;
+        } else if (e->mixed) {
+            CREATE_TRY(rpf::plan_mixed(e->N, e->variant, e->has_window, e->device, &e->plan));
+            partial_slots = e->plan.grid;
+        } else if (e->bluestein) {
+            CREATE_TRY(rpf::plan_bluestein(e->N, e->device, &e->plan));
+            partial_slots = e->plan.grid;
+        } else if (e->bigblu) {
+            CREATE_TRY(rpf::bigblu_prepare(e->N, e->device, &e->plan));
+            std::vector<rpf::cf> tws;
+            rpf::make_twiddles(blu_m1, tws);
+            CREATE_TRY(hipMalloc(&e->d_tw_sub, sizeof(rpf::cf) * tws.size()));
+            CREATE_TRY(hipMemcpy(e->d_tw_sub, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
+            rpf::make_twiddles(blu_m2, tws);
+            CREATE_TRY(hipMalloc(&e->d_tw_sub2, sizeof(rpf::cf) * tws.size()));
+            CREATE_TRY(hipMemcpy(e->d_tw_sub2, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
+            // (the intermediate starts at 256 MB and grows with the launches: ensure_scratch)
+            e->scratch_per_frame = rpf::bigblu_scratch_bytes_per_frame(e->N);
+            e->scratch_max = rpf::bigblu_scratch_bytes(e->N);
+            e->scratch_bytes = std::min<size_t>(e->scratch_max, std::max<size_t>(e->scratch_per_frame, static_cast<size_t>(256) << 20));
+            CREATE_TRY(hipMalloc(&e->d_scratch, e->scratch_bytes));
+            partial_slots = rpf::bigblu_partial_slots(e->N);
+            partial_len = e->blu_M;
+            // the kernels read chirp, kernel spectrum and inter-step twiddles in their own lane order
+            std::vector<rpf::cf> g_t, bhat_t, step_tw, step_tw2;
+            rpf::bigblu_tables(e->N, reinterpret_cast<const rpf::cf*>(blu_g.data()),
+                               reinterpret_cast<const rpf::cf*>(blu_bhat.data()), g_t, bhat_t, step_tw, step_tw2);
+            (void)hipFree(e->d_chirp);
+            e->d_chirp = nullptr;
+            CREATE_TRY(hipMalloc(&e->d_chirp, sizeof(rpf::cf) * g_t.size()));
+            CREATE_TRY(hipMemcpy(e->d_chirp, g_t.data(), sizeof(rpf::cf) * g_t.size(), hipMemcpyHostToDevice));
+            CREATE_TRY(hipMemcpy(e->d_bhat, bhat_t.data(), sizeof(rpf::cf) * bhat_t.size(), hipMemcpyHostToDevice));
+            CREATE_TRY(hipMemcpy(e->d_twiddles, step_tw.data(), sizeof(rpf::cf) * step_tw.size(), hipMemcpyHostToDevice));
+            CREATE_TRY(hipMalloc(&e->d_step2, sizeof(rpf::cf) * step_tw2.size()));
+            CREATE_TRY(hipMemcpy(e->d_step2, step_tw2.data(), sizeof(rpf::cf) * step_tw2.size(), hipMemcpyHostToDevice));
+        } else if (e->fourstep) {
+            CREATE_TRY(rpf::fourstep_prepare(e->N, e->device, &e->plan));
+            int n1 = 0, n2 = 0;
+            rpf::fourstep_sub_lengths(e->N, &n1, &n2);
+            std::vector<rpf::cf> tws;
+            rpf::make_twiddles(n1, tws);
+            CREATE_TRY(hipMalloc(&e->d_tw_sub, sizeof(rpf::cf) * tws.size()));
+            CREATE_TRY(hipMemcpy(e->d_tw_sub, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
+            rpf::make_twiddles(n2, tws);
+            CREATE_TRY(hipMalloc(&e->d_tw_sub2, sizeof(rpf::cf) * tws.size()));
+            CREATE_TRY(hipMemcpy(e->d_tw_sub2, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
+            // The fused kernel (one persistent launch, the intermediate stays in each XCD's L2) where
+            // the device is the 8 x 32-CU part it is written for and its teams assemble; else K2a/K2b.
+            int fused_grid = 0;
+            // (overlapped frames: the two-kernel path -- the fused kernel's give-up verdict is one word per staging slot,
+            // which the gather path's several launches per slot would share)
+            if (!(cfg->flags & RPF_FLAG_NO_FOURSTEP_FUSED) && step == e->N &&
+                rpf::fourstep_fused_prepare(e->N, e->device, &fused_grid) == hipSuccess) {
+                CREATE_TRY(hipMalloc(&e->d_fused_scratch, rpf::fourstep_fused_scratch_bytes(e->N)));
+                CREATE_TRY(hipMalloc(&e->d_fused_ctl, rpf::fourstep_fused_ctl_bytes()));
+                CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->h_fused_words), 64, hipHostMallocMapped));
+                std::memset(e->h_fused_words, 0, 64);
+                CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->d_fused_words), e->h_fused_words, 0));
+                e->fused = true;
+                // (room for either path's partial spectra: a fused launch that gives up is re-run on K2a/K2b)
+                partial_slots = std::max<size_t>(rpf::fourstep_fused_slots(e->N), rpf::fourstep_partial_slots(e->N));
+            } else {
+                (void)hipGetLastError();
+                e->scratch_per_frame = rpf::fourstep_scratch_bytes_per_frame(e->N);
+                e->scratch_max = rpf::fourstep_scratch_bytes(e->N);
+                e->scratch_bytes = std::min<size_t>(e->scratch_max, static_cast<size_t>(256) << 20);
+                CREATE_TRY(hipMalloc(&e->d_scratch, e->scratch_bytes));
+                partial_slots = rpf::fourstep_partial_slots(e->N);
+            }
+            // K2a reads the inter-step twiddles and the window in its own lane order
+            std::vector<rpf::cf> step_tw;
+            std::vector<float> window_t;
+            rpf::fourstep_tables(e->N, cfg->window, step_tw, window_t);
+            CREATE_TRY(hipMemcpy(e->d_twiddles, step_tw.data(), sizeof(rpf::cf) * step_tw.size(), hipMemcpyHostToDevice));
+            if (e->has_window)
+                CREATE_TRY(hipMemcpy(e->d_window, window_t.data(), sizeof(float) * window_t.size(), hipMemcpyHostToDevice));
+        } else {
+            CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, true, e->device, &e->plan, e->format, e->stats));
+            rpf::LaunchInfo tmp;
+            CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, false, e->device, &tmp, e->format, e->stats));
+            e->plan.grid = std::min(e->plan.grid, tmp.grid);
+            partial_slots = e->plan.grid + rpf::kMaxHops;    // a workgroup leaves one partial per hop it touches
+            if (e->stats) partial_slots = static_cast<size_t>(e->plan.grid) * rpf::kStatsPlanes;   // three planes per workgroup, no scans
+        }
+        CREATE_TRY(hipMalloc(&e->d_partial, sizeof(double) * partial_len * partial_slots));
     }
-    CREATE_TRY(hipMalloc(&e->d_partial, sizeof(double) * partial_len * partial_slots));
     const size_t pwr_planes = e->stats ? rpf::kStatsPlanes : 1;
     CREATE_TRY(hipMalloc(&e->d_pwr, sizeof(double) * e->N * pwr_planes));
     CREATE_TRY(hipMemset(e->d_pwr, 0, sizeof(double) * e->N * pwr_planes));
@@ -1131,10 +1215,11 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
         e->empty_buffers.push_back(&b);
     }
     // device staging ring: head room for a carried partial frame + one buffer
-    e->head_room = ((e->sample_bytes * static_cast<size_t>(e->N)) + 255) / 256 * 256;
+    // (a PFB engine carries up to a whole span, b T N bytes, less one sample)
+    e->head_room = ((e->sample_bytes * span_samples(e)) + 255) / 256 * 256;
     // a slot (= one transform launch) holds as many buffers as fit 32 MB, at least one -- more than the pool has where the
     // buffers are small: they return to the producer when their copy lands, not when the slot is launched
-    e->coalesce = std::max<size_t>(1, (32u << 20) / e->buffer_capacity);
+    e->coalesce = inner_of_pfb ? 1 : std::max<size_t>(1, (32u << 20) / e->buffer_capacity);
     e->staging.resize(kStagingSlots);
     for (auto& s : e->staging) {
         void* p = nullptr;
@@ -1146,10 +1231,41 @@ int rpf_engine_create(const rpf_config* cfg, rpf_engine** out)
     static_assert(kStagingSlots <= 3, "h_fused_words[0 .. 2]: one verdict word per staging slot");
     if (e->h_fused_words)
         for (size_t k = 0; k < e->staging.size(); ++k) e->staging[k].verdict = e->h_fused_words + k;
+    if (pfb) {
+        const size_t nco = static_cast<size_t>(e->taps) * static_cast<size_t>(e->N);
+        CREATE_TRY(hipMalloc(&e->d_pfb_coeffs, sizeof(float) * nco));
+        CREATE_TRY(hipMemcpy(e->d_pfb_coeffs, pfb->coeffs, sizeof(float) * nco, hipMemcpyHostToDevice));
+        // the transform: a rectangular cf32 engine of the same N, device and staging flag, with one minimal buffer
+        rpf_config icfg;
+        icfg.struct_size = sizeof(icfg);
+        icfg.N = e->N;
+        icfg.window = nullptr;
+        icfg.n_buffers = 1;
+        icfg.buffer_capacity = 8;
+        icfg.device = e->device;
+        icfg.flags = (cfg->flags & (RPF_FLAG_NO_LDS_DMA | RPF_FLAG_CATCH_ALL)) | RPF_FLAG_SAMPLE_FORMAT(RPF_FORMAT_CF32);
+        icfg.frame_step = 0;
+        const int rc = create_engine(&icfg, nullptr, /*inner_of_pfb=*/true, &e->inner);
+        if (rc != RPF_OK) return cleanup(rc);
+    }
 #undef CREATE_TRY
     *out = e;
     return RPF_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int rpf_engine_create(const rpf_config* cfg, rpf_engine** out) { return create_engine(cfg, nullptr, false, out); }
+
+int rpf_engine_create_pfb(const rpf_config* cfg, int taps, const float* coeffs, rpf_engine** out)
+{
+    const PfbSpec pfb{taps, coeffs};
+    return create_engine(cfg, &pfb, false, out);
+}
+
+int rpf_pfb_taps(const rpf_engine* e) { return e ? e->taps : -1; }
 
 void rpf_engine_destroy(rpf_engine* e)
 {
@@ -1465,6 +1581,8 @@ int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t
                      void* hip_stream, int64_t* repeats_done)
 {
     if (!e || !d_stream) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: NULL argument");
+    if (e->taps)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: not on a PFB engine (the fold and the transform are several launches: use rpf_accumulate_device)");
     if (e->stats)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: not on an engine with RPF_FLAG_BIN_STATS (use rpf_accumulate_device_stats)");
     if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: acquisition running");
@@ -1497,6 +1615,8 @@ int rpf_device_reduce(rpf_engine* e, double* d_pwr_out, void* hip_stream)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: d_pwr_out must be 16-byte aligned");
     if (e->stats)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: not on an engine with RPF_FLAG_BIN_STATS (use rpf_accumulate_device_stats)");
+    if (e->taps)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: not on a PFB engine (use rpf_accumulate_device)");
     if (e->last_slots < 1 && e->last_hops < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: nothing to reduce");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
@@ -1558,10 +1678,10 @@ int rpf_accumulate_device_hops(rpf_engine* e, const void* const* d_streams, cons
     if (repeats_done)
         for (int h = 0; h < n_hops; ++h) repeats_done[h] = frames[h];
     const size_t N = static_cast<size_t>(e->N);
-    if (!is_k1(e) || overlapped(e) || e->stats) {
-        // the other kernel families -- and overlapped frames (the scan kernel reads frames side by side), and stats
-        // engines (the scan kernel keeps no statistics; what comes back here is the power alone) -- run one
-        // acquisition per launch set
+    if (!is_k1(e) || overlapped(e) || e->stats || e->taps) {
+        // the other kernel families -- and overlapped frames (the scan kernel reads frames side by side), stats
+        // engines (the scan kernel keeps no statistics; what comes back here is the power alone) and PFB engines (a
+        // fold in front of every transform) -- run one acquisition per launch set
         for (int h = 0; h < n_hops; ++h) {
             if (frames[h] == 0) {
                 HIP_TRY(e, hipMemsetAsync(d_pwr_out + h * N, 0, sizeof(double) * N, s));
@@ -1600,6 +1720,8 @@ int rpf_device_fused_hops(rpf_engine* e, const void* const* d_streams, const siz
     if (rc != RPF_OK) return rc;
     if (e->stats)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused_hops: not on an engine with RPF_FLAG_BIN_STATS");
+    if (e->taps)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused_hops: not on a PFB engine (use rpf_accumulate_device_hops)");
     if (!is_k1(e) || n_hops > rpf::kMaxHops || overlapped(e))
         return fail(e, RPF_ERR_INVALID_ARGUMENT,
                     "rpf_device_fused_hops: needs a size the LDS-resident kernel serves, frames side by side (frame step N) "
@@ -1633,6 +1755,8 @@ static int series_check(rpf_engine* e, const char* who, const void* stream, size
                         const void* out, bool want_stats = false)
 {
     if (!e || !out || (!stream && nbytes)) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+    if (e->taps)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": not on a PFB engine (PFB with series, statistics or excision is not built)");
     if (want_stats && !e->stats)
         return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": the engine was created without RPF_FLAG_BIN_STATS");
     if (!want_stats && e->stats)
@@ -2000,6 +2124,7 @@ int rpf_last_launch_info(const rpf_engine* e, int* grid, int* block, int* frames
                          int* lds_bytes)
 {
     if (!e) return RPF_ERR_INVALID_ARGUMENT;
+    if (e->inner) e = e->inner;           // a PFB engine reports its transform launch
     if (grid) *grid = e->last.grid ? e->last.grid : e->plan.grid;
     if (block) *block = e->plan.block;
     if (frames_per_wg) *frames_per_wg = e->plan.fpw;

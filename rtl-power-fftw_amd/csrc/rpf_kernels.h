@@ -10,6 +10,7 @@
 #include "excise_core.h"
 #include "fft_core.h"
 #include "hop_partition.h"
+#include "pfb_core.h"
 #include "series_partition.h"
 
 namespace rpf {
@@ -198,6 +199,17 @@ hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const fl
 constexpr size_t kGatherBytes = static_cast<size_t>(64) << 20;   // gathered frames per chunk (the engine's scratch)
 hipError_t launch_gather_frames(const uint8_t* d_src, long nframes, long pitch, long frame_bytes, uint8_t* d_dst,
                                 hipStream_t stream);
+
+// ---- polyphase filter bank front end (rpf_pfb.hip, pfb_core.h) ----------------------------------------
+// d_z[f][n] (float32 I/Q, frames side by side, 16-byte aligned) = the fold of include/rpf_engine.h over the input
+// frames f .. f + taps - 1 of d_src (frames of N samples of format `fmt` side by side; d_src a multiple of the sample's
+// bytes) for f < nframes: nframes + taps - 1 input frames are read.  d_coeffs: taps x N floats, 8-byte aligned.
+// taps 1, 2, 3, 4, 8: the sliding-window kernel; any other taps <= 32: the re-reading kernel.  In both a lane walks
+// pfb_segment_frames(taps, fmt) output frames.
+bool pfb_sliding(int taps);
+int pfb_segment_frames(int taps, int fmt);
+hipError_t launch_pfb_fold(const uint8_t* d_src, long nframes, int N, int taps, int fmt, const float* d_coeffs, float* d_z,
+                           hipStream_t stream);
 
 // Master twiddle table W_N^k = exp(-2 pi i k / N), k in [0,N), evaluated in
 // long double and rounded once to float.

@@ -19,8 +19,13 @@ class Params:
 
     def __init__(self, N=512, buffers=5, buf_length=BASE_BUF * DEFAULT_BUF_MULTIPLIER,
                  repeats=None, window=False, sample_rate=2000000, cfreq=1420405752,
-                 linear=False, baseline=False, frame_step=None, sample_format="cu8", bin_stats=False):
+                 linear=False, baseline=False, frame_step=None, sample_format="cu8", bin_stats=False,
+                 pfb_taps=0, pfb_coeffs=None):
         self.N = N
+        # polyphase filter bank front end (rpf_engine_create_pfb): T taps, 0 = none; pfb_coeffs: T x N float32 values,
+        # None = pfb.coefficients(N, T), the default prototype
+        self.pfb_taps = int(pfb_taps)
+        self.pfb_coeffs = pfb_coeffs
         # per-bin statistics beside the power (RPF_FLAG_BIN_STATS): Datastore.sum_sq, Datastore.peak
         self.bin_stats = bool(bin_stats)
         # what one complex sample of the stream is: "cu8" (the reference's), "cs8", "cs16", "cf32" (RPF_FORMAT_*)
@@ -34,7 +39,8 @@ class Params:
         self.buf_length = buf_length
         # params.h:56: repeats = buf_length/(2*N) unless -n/-t say otherwise -- a sample budget, which overlapped
         # frames turn into more frames from the same samples
-        self.repeats = (frames_for_budget(buf_length // (_lib.SAMPLE_BYTES[sample_format] * N), N, self.frame_step)
+        self.repeats = (frames_for_budget(buf_length // (_lib.SAMPLE_BYTES[sample_format] * N), N, self.frame_step,
+                                          max(self.pfb_taps, 1))
                         if repeats is None
                         else repeats)
         self.window = window
@@ -44,10 +50,13 @@ class Params:
         self.baseline = baseline
 
 
-def frames_for_budget(r0, N, step):
-    """R = floor((R0 - 1) N / S) + 1: the frames at step S the samples of R0 side-by-side frames hold (R0 for S = N)."""
+def frames_for_budget(r0, N, step, taps=1):
+    """R = floor((R0 - 1) N / S) + 1: the frames at step S the samples of R0 side-by-side frames hold (R0 for S = N).
+    With a PFB of `taps` taps a frame spans taps x N samples: R0 - (taps - 1) frames, at least one."""
     if r0 < 1 or not step:
         return r0
+    if taps > 1:
+        return max(r0 - (taps - 1), 1)
     return (r0 - 1) * N // step + 1
 
 
@@ -60,15 +69,16 @@ def _as_bytes(stream):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
-def frames_in(nbytes, N, step, sample_bytes=2):
-    """frames(B) = B < bN ? 0 : (B - bN) / (bS) + 1 (rpf_frames_in); b = sample_bytes."""
+def frames_in(nbytes, N, step, sample_bytes=2, taps=1):
+    """frames(B) = B < bTN ? 0 : (B - bTN) / (bS) + 1 (rpf_frames_in); b = sample_bytes, T = taps (a PFB engine's
+    frame spans T N samples and its step is N; 1 without PFB)."""
     b = sample_bytes
-    return 0 if nbytes < b * N else (nbytes - b * N) // (b * step) + 1
+    return 0 if nbytes < b * taps * N else (nbytes - b * taps * N) // (b * step) + 1
 
 
-def frame_span(frames, N, step, sample_bytes=2):
-    """Bytes `frames` frames span: bN + bS (frames - 1) (rpf_frame_span); b = sample_bytes."""
-    return 0 if frames < 1 else sample_bytes * (N + step * (frames - 1))
+def frame_span(frames, N, step, sample_bytes=2, taps=1):
+    """Bytes `frames` frames span: bTN + bS (frames - 1) (rpf_frame_span); b = sample_bytes, T = taps."""
+    return 0 if frames < 1 else sample_bytes * (taps * N + step * (frames - 1))
 
 
 class Datastore:
@@ -98,7 +108,24 @@ class Datastore:
         if getattr(params, "bin_stats", False):
             cfg.flags |= _lib.FLAG_BIN_STATS
         cfg.frame_step = getattr(params, "frame_step", params.N)
-        rc = self._lib.rpf_engine_create(ctypes.byref(cfg), ctypes.byref(self._handle))
+        taps = getattr(params, "pfb_taps", 0)
+        if taps:
+            from . import pfb
+            coeffs = getattr(params, "pfb_coeffs", None)
+            if coeffs is None and 1 <= taps <= pfb.MAX_TAPS:
+                coeffs = pfb.coefficients(params.N, taps)
+            if coeffs is not None:
+                coeffs = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(-1)
+                if coeffs.size != taps * params.N and taps >= 1:
+                    raise RPFError("Error reading PFB coefficients. Expected %d values, found %d."
+                                   % (taps * params.N, coeffs.size), ReturnValue.InvalidInput)
+            self._pfb_coeffs = coeffs
+            rc = self._lib.rpf_engine_create_pfb(
+                ctypes.byref(cfg), taps,
+                None if coeffs is None else coeffs.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                ctypes.byref(self._handle))
+        else:
+            rc = self._lib.rpf_engine_create(ctypes.byref(cfg), ctypes.byref(self._handle))
         if rc != 0:
             self._handle = ctypes.c_void_p()
             raise RPFError(self._lib.rpf_last_global_error().decode(), rc)
@@ -352,6 +379,11 @@ class Datastore:
     def frame_span(self, frames):
         """rpf_frame_span: bytes `frames` frames span at this engine's frame step."""
         return self._lib.rpf_frame_span(self._handle, frames)
+
+    @property
+    def pfb_taps(self):
+        """rpf_pfb_taps: T of a PFB engine, 0 for an engine without PFB."""
+        return self._lib.rpf_pfb_taps(self._handle)
 
     @property
     def sample_bytes(self):

@@ -51,10 +51,25 @@ struct Params {
   // What one complex sample of the stream is (RPF_FORMAT_*, --format): cu8, the reference's, unless told otherwise.
   int sample_format = RPF_FORMAT_CU8;
   int64_t sample_bytes() const { return sample_format == RPF_FORMAT_CF32 ? 8 : sample_format == RPF_FORMAT_CS16 ? 4 : 2; }
-  // bytes `frames` frames span (rpf_frame_span): bN + bS (frames - 1), b bytes per sample
-  int64_t frame_span(int64_t frames) const { return frames < 1 ? 0 : sample_bytes() * (static_cast<int64_t>(N) + step() * (frames - 1)); }
-  // a sample budget of r0 side-by-side frames as frames at step S: floor((r0 - 1) N / S) + 1 (r0 at S = N)
-  int64_t frames_for_budget(int64_t r0) const { return r0 < 1 ? r0 : (r0 - 1) * N / step() + 1; }
+  // Polyphase filter bank front end (rpf_engine_create_pfb, --pfb): T taps, 0 = none; pfb_coeffs: T x N values, empty =
+  // pfb_coefficients(N, T), the default prototype.  A frame then spans T N samples and the step is N.
+  int pfb_taps = 0;
+  std::vector<float> pfb_coeffs;
+  int64_t span_samples() const { return static_cast<int64_t>(N) * std::max(pfb_taps, 1); }
+  // bytes `frames` frames span (rpf_frame_span): b span + bS (frames - 1), b bytes per sample, span = N (T N with PFB)
+  int64_t frame_span(int64_t frames) const { return frames < 1 ? 0 : sample_bytes() * (span_samples() + step() * (frames - 1)); }
+  // frames a stream of nbytes holds (rpf_frames_in)
+  int64_t frames_in(int64_t nbytes) const {
+    const int64_t frame = sample_bytes() * span_samples();
+    return nbytes < frame ? 0 : (nbytes - frame) / (sample_bytes() * step()) + 1;
+  }
+  // a sample budget of r0 side-by-side frames as frames at step S: floor((r0 - 1) N / S) + 1 (r0 at S = N); with a PFB
+  // of T taps r0 - (T - 1), at least one
+  int64_t frames_for_budget(int64_t r0) const {
+    if (r0 < 1) return r0;
+    if (pfb_taps > 1) return std::max<int64_t>(r0 - (pfb_taps - 1), 1);
+    return (r0 - 1) * N / step() + 1;
+  }
   int sample_rate = 2000000;
   int64_t cfreq = 1420405752;
   bool linear = false;
@@ -63,6 +78,27 @@ struct Params {
   // Per-bin statistics beside the power (RPF_FLAG_BIN_STATS, --stats): Datastore::sum_sq, Datastore::peak.
   bool bin_stats = false;
 };
+
+// The default PFB prototype h[0 .. T N): sinc((j - (TN-1)/2) / N) (0.54 - 0.46 cos(2 pi j / (TN-1))), computed in double,
+// scaled so that the sum of h^2 is N and rounded to float32 once -- the formula of pfb.py's coefficients().
+inline std::vector<float> pfb_coefficients(int N, int taps) {
+  if (taps < 1 || taps > 32 || N < 2 || N % 2 != 0)
+    throw RPFexception("pfb_coefficients: taps must be in 1 .. 32 and N a positive even number.", ReturnValue::InvalidArgument);
+  const size_t M = static_cast<size_t>(taps) * static_cast<size_t>(N);
+  const double pi = 3.14159265358979323846;
+  std::vector<double> h(M);
+  double sum_sq = 0;
+  for (size_t j = 0; j < M; ++j) {
+    const double x = (static_cast<double>(j) - static_cast<double>(M - 1) / 2.0) / N;
+    const double y = pi * (x == 0 ? 1.0e-20 : x);
+    h[j] = std::sin(y) / y * (0.54 - 0.46 * std::cos(2.0 * pi * static_cast<double>(j) / static_cast<double>(M - 1)));
+    sum_sq += h[j] * h[j];
+  }
+  const double scale = std::sqrt(N / sum_sq);
+  std::vector<float> out(M);
+  for (size_t j = 0; j < M; ++j) out[j] = static_cast<float>(h[j] * scale);
+  return out;
+}
 
 // The spectral kurtosis estimator (Nita & Gary) from S1 = sum of the frame powers and S2 = sum of their squares over
 // M frames: SK = (M+1)/(M-1) (M S2 / S1^2 - 1), in double, in exactly this order of operations (stats.py's
@@ -135,7 +171,18 @@ public:
       peak.assign(params.N, 0.0);
     }
     cfg.frame_step = params.frame_step;
-    int rc = rpf_engine_create(&cfg, &engine_);
+    int rc;
+    if (params.pfb_taps != 0) {
+      if (!params.pfb_coeffs.empty() && params.pfb_coeffs.size() != static_cast<size_t>(std::max(params.pfb_taps, 0)) * params.N)
+        throw RPFexception("Error reading PFB coefficients. Expected " + std::to_string(static_cast<int64_t>(params.pfb_taps) * params.N)
+                           + " values, found " + std::to_string(params.pfb_coeffs.size()) + ".", ReturnValue::InvalidInput);
+      const bool in_range = params.pfb_taps >= 1 && params.pfb_taps <= 32;
+      const std::vector<float> h = !params.pfb_coeffs.empty() ? params.pfb_coeffs
+                                   : in_range ? pfb_coefficients(params.N, params.pfb_taps) : std::vector<float>(1);
+      rc = rpf_engine_create_pfb(&cfg, params.pfb_taps, h.data(), &engine_);
+    } else {
+      rc = rpf_engine_create(&cfg, &engine_);
+    }
     if (rc != RPF_OK) throw RPFexception(rpf_last_global_error(), (ReturnValue)rc);
   }
   // datastore.cxx:36-46

@@ -94,6 +94,37 @@ int rpf_host_plan(int argc, const char* const* argv, int samplerate, long long* 
     }
 }
 
+// The default PFB prototype (datastore.h's pfb_coefficients) into out[taps x N]; 0, or the exit code of a bad argument.
+int rpf_host_pfb_coefficients(int N, int taps, float* out)
+{
+    try {
+        const std::vector<float> h = pfb_coefficients(N, taps);
+        std::copy(h.begin(), h.end(), out);
+        return 0;
+    } catch (RPFexception& e) {
+        return static_cast<int>(e.returnValue());
+    }
+}
+
+// Params' byte formulas with a PFB of `taps` taps (0 = none) and b = 2, 4 or 8 bytes per sample (format cu8, cs16, cf32).
+long long rpf_host_pfb_frames_in(int N, int taps, int sample_bytes, long long nbytes)
+{
+    Params p;
+    p.N = N;
+    p.pfb_taps = taps;
+    p.sample_format = sample_bytes == 8 ? RPF_FORMAT_CF32 : sample_bytes == 4 ? RPF_FORMAT_CS16 : RPF_FORMAT_CU8;
+    return p.frames_in(nbytes);
+}
+
+long long rpf_host_pfb_frame_span(int N, int taps, int sample_bytes, long long frames)
+{
+    Params p;
+    p.N = N;
+    p.pfb_taps = taps;
+    p.sample_format = sample_bytes == 8 ? RPF_FORMAT_CF32 : sample_bytes == 4 ? RPF_FORMAT_CS16 : RPF_FORMAT_CU8;
+    return p.frame_span(frames);
+}
+
 long long rpf_host_next_read_size(long long total, long long done, int buf_length)
 {
     return next_read_size(total, done, buf_length);

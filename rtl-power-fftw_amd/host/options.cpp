@@ -75,6 +75,10 @@ const Spec kSpecs[] = {
      "leaves 1 +- sigma standard deviations are left out, bin by bin; one block with a kept-fraction column (implies "
      "--stats' engine; not with --series, --series-stats, a frequency range, -n, -t, -c, -e, -m or several --gpus)."},
     {0, "excise-sigma", Kind::Double, "sigma", "Width of the --excise thresholds in standard deviations of the estimator. Default 3."},
+    {0, "pfb", Kind::Int, "taps",
+     "Polyphase filter bank front end: every frame is <taps> x bins samples weighted by a windowed-sinc prototype and "
+     "folded to <bins> before the FFT, 1 <= taps <= 32 (not with -w, --frame-overlap, --stats, --series, --series-stats, "
+     "--excise or several --gpus)."},
     {0, "reduce", Kind::Text, "rccl|host", "With --gpus: where a scan's per-device spectra are added (default: rccl if it loads, else host)."},
     {'h', "help", Kind::Flag, "", "Displays usage information and exits."},
     {0, "version", Kind::Flag, "", "Displays version information and exits."},
@@ -293,6 +297,30 @@ Options parse_command_line(int argc, const char* const* argv)
         if (o.sample_format != RPF_FORMAT_CU8 && !p.has("input"))
             throw RPFexception("Option --format " + text + " needs --input: a dongle and --synthetic deliver cu8 "
                                "(one of cu8, cs8, cs16, cf32). Exiting.", ReturnValue::InvalidArgument);
+    }
+    if (p.has("pfb")) {
+        // (before the repeats: the default and -t are sample budgets, which the span of a PFB frame turns into frames)
+        o.pfb_taps = to_number<int>(*find_spec("--pfb"), p.get("pfb"));
+        if (o.pfb_taps < 1 || o.pfb_taps > 32)
+            throw RPFexception("Invalid number of taps given to --pfb: " + p.get("pfb") + ".\n"
+                               "Expecting a number between 1 and 32. Exiting.", ReturnValue::InvalidArgument);
+        // (all follow-ups: coefficients from a file; overlapped PFB frames; PFB in front of the statistics kernels;
+        // a span carried across the shards of several devices)
+        const struct { const char* name; const char* shown; const char* why; } refused[] = {
+            {"window", "-w", "the PFB coefficients are the window"},
+            {"frame-overlap", "--frame-overlap", "PFB frames advance by the number of bins"},
+            {"stats", "--stats", "PFB with statistics is not built"},
+            {"series", "--series", "PFB with a series is not built"},
+            {"series-stats", "--series-stats", "PFB with a series is not built"},
+            {"excise", "--excise", "PFB with excision is not built"},
+        };
+        for (const auto& r : refused)
+            if (p.has(r.name))
+                throw RPFexception(std::string("Option --pfb does not combine with ") + r.shown + ": " + r.why + ". Exiting.",
+                                   ReturnValue::InvalidArgument);
+        if (o.devices.size() > 1)
+            throw RPFexception("Option --pfb does not combine with several devices in --gpus. Exiting.",
+                               ReturnValue::InvalidArgument);
     }
     if (p.has("repeats")) o.repeats = to_number<int64_t>(*find_spec("--repeats"), p.get("repeats"));
     else o.repeats = o.frames_for_budget(o.buf_length / (o.sample_bytes() * o.N));  // params.cxx:214-217, as a sample budget

@@ -57,6 +57,7 @@ struct Options : Params {
     bool series_stats = false;       // --series-stats <frames>: the same with the --stats columns per block (sets both above)
     int64_t excise_frames = 0;       // --excise <frames>: the replay's average without the SK-flagged integrations (0 = off)
     double excise_sigma = 3.0;       // --excise-sigma <s>: its thresholds, sk_limits(frames, s)
+    // (--pfb <taps> sets Params::pfb_taps; the coefficients are the default prototype)
     bool show_help = false, show_version = false;
 };
 
