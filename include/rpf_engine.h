@@ -115,8 +115,7 @@ typedef struct rpf_config {
  * of the cs16 stream of those values.  (3 is not a format: 4 is cf32.)
  * The LDS-resident kernel (powers of two 64 .. 8192) reads all four natively; at every other size a cs8 / cs16 / cf32
  * engine runs on the catch-all Stockham path (rpf_supported_n(N) holds for all four formats), which is several
- * times slower than the tuned kernel a cu8 engine gets at that size; so does a cf32 engine with RPF_FLAG_BIN_STATS
- * at every size (README.md, "Sample formats"). */
+ * times slower than the tuned kernel a cu8 engine gets at that size (README.md, "Sample formats"). */
 #define RPF_FORMAT_CU8  0   /* unsigned 8-bit I,Q; x = v - 127   (the reference; the default) */
 #define RPF_FORMAT_CS8  1   /* signed 8-bit I,Q;   x = v                                       */
 #define RPF_FORMAT_CS16 2   /* signed 16-bit little-endian I,Q; x = v                          */
@@ -136,8 +135,9 @@ typedef struct rpf_config {
  * An engine created with the flag keeps S2 and PK beside the power on the buffer-queue path (rpf_begin .. rpf_finish,
  * rpf_accumulate; rpf_get_bin_stats) and in rpf_accumulate_device_stats; rpf_get_power, rpf_accumulate and
  * rpf_accumulate_device keep their meaning and return S1.  Served natively by the LDS-resident kernel (powers of two
- * 64 .. 8192, the three integer sample formats, any frame step) with two more register accumulators per bin; at every other
- * size, and with cf32 at every size, a stats engine runs on the catch-all Stockham path (README.md, "Per-bin statistics").
+ * 64 .. 8192, every sample format, any frame step) with two more register accumulators per bin; at every other
+ * size a stats engine runs on the catch-all Stockham path (README.md, "Per-bin statistics").  A NaN sample makes S1 and
+ * S2 of every bin NaN and leaves PK the peak of the other frames (the maximum drops a NaN operand), on both paths.
  * Without the flag nothing changes: same kernels, same scratch, same results.
  * RPF_ERR_INVALID_ARGUMENT from rpf_engine_create, before any device is touched: together with RPF_FLAG_FOURSTEP_FUSED
  * or with RPF_FLAG_VARIANT(k), k != 0.  On a stats engine rpf_device_fused, rpf_device_fused_hops and rpf_device_reduce

@@ -27,7 +27,9 @@ namespace {
 // scan kernel (a hop's frames; one 64-bit multiply less per DMA instruction).
 // FMT: the sample format (fft_core.h); 4-byte samples double the pieces and the frame, cf32's 8-byte samples double
 // them again (P / 2 pieces: 8 at P = 16, under the 6-bit vmcnt field at every ring depth in use).
-template <class G, bool DMA, typename IDX, int FMT = kFmtCu8>
+// BATCH > 0 (VGPR staging of the windowed cf32 kernels with statistics only, k1_body.inc): no more than BATCH 16-byte
+// loads in flight, the pieces go to LDS batch by batch; 0, everywhere else: the compiler's own order, all at once.
+template <class G, bool DMA, typename IDX, int FMT = kFmtCu8, int BATCH = 0>
 __device__ __forceinline__ void stage_raw(const uint8_t* __restrict__ stream, IDX fb, IDX nframes,
                                           uint8_t* wave_raw, int wave, int lane)
 {
@@ -46,13 +48,16 @@ __device__ __forceinline__ void stage_raw(const uint8_t* __restrict__ stream, ID
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(wave_raw + i * 1024), 16, 0, 0);
         } else {
             *reinterpret_cast<uint4*>(wave_raw + j) = *reinterpret_cast<const uint4*>(src);
+            if constexpr (BATCH > 0) {
+                if ((i + 1) % BATCH == 0) asm volatile("" ::: "memory");
+            }
         }
     }
 }
 
 // The same at a run-time frame pitch (bytes from one frame's start to the next): the frames of a stream with frame
 // step S < N (rpf_config::frame_step) lie 2S apart.  Only the strided K1 uses it.
-template <class G, bool DMA, int FMT = kFmtCu8>
+template <class G, bool DMA, int FMT = kFmtCu8, int BATCH = 0>
 __device__ __forceinline__ void stage_raw_pitched(const uint8_t* __restrict__ stream, long fb, long nframes, long pitch,
                                                   uint8_t* wave_raw, int wave, int lane)
 {
@@ -69,6 +74,9 @@ __device__ __forceinline__ void stage_raw_pitched(const uint8_t* __restrict__ st
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(wave_raw + i * 1024), 16, 0, 0);
         } else {
             *reinterpret_cast<uint4*>(wave_raw + j) = *reinterpret_cast<const uint4*>(src);
+            if constexpr (BATCH > 0) {
+                if ((i + 1) % BATCH == 0) asm volatile("" ::: "memory");
+            }
         }
     }
 }
@@ -249,23 +257,28 @@ struct Variant {
 
 // Variant 0 of every K1 size, one finder per translation unit so that the units compile side by side; each answers
 // for its own sample formats and returns null for the others.  find_variant (rpf_kernels.hip) is the one entry the
-// launch code uses and picks among the first five; the series kernels are looked up where they are launched.
-// cf32 has the plain kernels only: a cf32 engine with statistics runs on the catch-all path and its series run
-// spectrum by spectrum (rpf_engine.cpp).
-//   k1_variant              rpf_kernels.hip                cu8        single, scan, strided
-//   k1_format_variant       rpf_kernels_formats.hip        cs8, cs16  single, scan, strided
-//   k1_cf32_variant         rpf_kernels_cf32.hip           cf32       single, scan, strided
-//   k1_stats_variant        rpf_kernels_stats.hip          cu8        single, strided with per-bin statistics
-//   k1_stats_format_variant rpf_kernels_stats_formats.hip  cs8, cs16  single, strided with per-bin statistics
-//   k1_series_variant       rpf_kernels_series.hip         cu8, cs8, cs16 (null for cf32)  series
-//   k1_series_stats_variant rpf_kernels_series_stats.hip   cu8, cs8, cs16 (null for cf32)  series with per-bin statistics
+// launch code uses and picks among the first six; the series kernels are looked up where they are launched.
+// cf32 has no series kernel without statistics: its plain series run spectrum by spectrum (rpf_engine.cpp).  No form
+// of any finder is null: every size x window x staging form is instantiated, none with scratch.
+//   k1_variant                   rpf_kernels.hip                   cu8        single, scan, strided
+//   k1_format_variant            rpf_kernels_formats.hip           cs8, cs16  single, scan, strided
+//   k1_cf32_variant              rpf_kernels_cf32.hip              cf32       single, scan, strided
+//   k1_stats_variant             rpf_kernels_stats.hip             cu8        single, strided with per-bin statistics
+//   k1_stats_format_variant      rpf_kernels_stats_formats.hip     cs8, cs16  single, strided with per-bin statistics
+//   k1_stats_cf32_variant        rpf_kernels_stats_cf32.hip        cf32       single, strided with per-bin statistics
+//   k1_series_variant            rpf_kernels_series.hip            cu8, cs8, cs16 (null for cf32)  series
+//   k1_series_stats_variant      rpf_kernels_series_stats.hip      cu8, cs8, cs16, and cf32 by way of the next
+//                                                                             series with per-bin statistics
+//   k1_series_stats_cf32_variant rpf_kernels_series_stats_cf32.hip cf32       series with per-bin statistics
 const Variant* k1_variant(int N, int fmt);
 const Variant* k1_format_variant(int N, int fmt);
 const Variant* k1_cf32_variant(int N, int fmt);
 const Variant* k1_stats_variant(int N, int fmt);
 const Variant* k1_stats_format_variant(int N, int fmt);
+const Variant* k1_stats_cf32_variant(int N, int fmt);
 const Variant* k1_series_variant(int N, int fmt);
 const Variant* k1_series_stats_variant(int N, int fmt);
+const Variant* k1_series_stats_cf32_variant(int N, int fmt);
 
 // The resident grid of kernels that share one launch geometry on `device`: for each kernel (null entries skipped) the
 // dynamic-LDS attribute is set and its occupancy asked; *grid = max(the smallest, 1) x CUs.  rpf_kernels.hip.

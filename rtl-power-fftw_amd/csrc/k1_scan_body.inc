@@ -23,6 +23,13 @@
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     constexpr int RAW_SLOT = raw_chunk_of(FMT) * P;   // bytes one wave stages per frame
     constexpr int PIECES = P / 8 * (sample_bytes_of(FMT) / 2);   // DMA instructions per wave per frame
+    // WREG: the window values stay in registers across the frame loop, and a frame's raw bytes are staged all at once.
+    // Everywhere but in the windowed VGPR-staging cf32 kernels with statistics at P = 16, where eight 16-byte loads in
+    // flight, three double accumulators per bin and the window are more than 256 registers: those read the P window values
+    // again for every frame (L1 hits; the same products, so the same bits) and stage in two batches (stage_raw,
+    // BATCH).  With WREG true -- every other instantiation -- nothing here changes what the kernel compiles to.
+    constexpr bool WREG = !(FMT == kFmtCf32 && STATS && !DMA && WINDOW && P == 16);
+    constexpr int SBATCH = WREG ? 0 : P / 4;
     static_assert((RAWD - 1) * PIECES <= 63, "the counted wait below: vmcnt is a 6-bit field");
     uint8_t* const wave_raw = raw_base + wave * (RAWD * RAW_SLOT);
 
@@ -70,7 +77,7 @@
         }
     };
     auto stage_next = [&](uint8_t* dst) {
-        stage_raw<G, DMA, int, FMT>(ahead.stream, ahead_fb, ahead.nframes, dst, wave, lane);
+        stage_raw<G, DMA, int, FMT, SBATCH>(ahead.stream, ahead_fb, ahead.nframes, dst, wave, lane);
         ahead_fb += ahead_fstep;
         if (--ahead_run == 0) ahead_turn();
     };
@@ -89,7 +96,7 @@
     }
     const float sgn = (t & 1) ? -1.0f : 1.0f;
     float wsgn[P];
-    if constexpr (WINDOW) {
+    if constexpr (WINDOW && WREG) {
 #pragma unroll
         for (int a = 0; a < P; ++a) wsgn[a] = window[t + T * a] * sgn;
     }
@@ -131,6 +138,12 @@
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RAWD - 1) * PIECES) : "memory");
             exchange_sync<false>();
             RPF_STAMP(clk, 0);                   // waiting for the staged bytes
+            if constexpr (WINDOW && !WREG) {
+                const float* wp = window + t;
+                asm volatile("" : "+v"(wp));      // (opaque: the loads stay inside the frame loop)
+#pragma unroll
+                for (int a = 0; a < P; ++a) wsgn[a] = wp[T * a] * sgn;
+            }
             phase_unpack<G, WINDOW, FMT>(ring_slot + sample_bytes_of(FMT) * lane, sgn, wsgn, x);
             // The slot is refilled next: its LDS reads must have RETURNED first (a DMA
             // that hits in L2/MALL can land before queued LDS reads execute -- seen as

@@ -96,6 +96,12 @@ constexpr int kLdsPerCU = 160 * 1024;
 // and 256 and the plain ones of 1024 take two (256 registers).  None of them had a third workgroup's LDS on the CU
 // to begin with (66 KB, 66 KB and 102 KB per workgroup), so no resident workgroup is lost
 // (profiles/cf32_resources.txt).
+// cf32 with statistics departs twice more, for the VGPR-staging forms, whose eight 16-byte loads in flight meet the
+// three double accumulators per bin: 8192 reads the twiddles of passes 2 and 3 from the LDS table in its plain form
+// as well (4 KB more: 136 KB of 160), and windowed 1024 takes one wave per SIMD -- its 102 KB of LDS admit one
+// workgroup per CU whatever the registers say, so no resident workgroup is lost and the compiler may use 512
+// registers.  The windowed VGPR-staging forms also stop holding the window across the frame (k1_body.inc, WREG).  No
+// instantiation spills (profiles/cf32_stats_resources.txt).
 constexpr K1Size k1_size(int i, int fmt, bool stats)
 {
     K1Size s = kK1Sizes[i];
@@ -109,6 +115,8 @@ constexpr K1Size k1_size(int i, int fmt, bool stats)
         if (s.N == 128 || s.N == 256 || s.N == 1024) s.OCC = s.OCCW = 2;
         if (s.N == 512) s.OCCW = 3;
         if (s.N == 8192) s.TWLDSW = true;
+        if (fmt == kFmtCf32 && s.N == 8192) s.TWLDS = true;
+        if (fmt == kFmtCf32 && s.N == 1024) s.OCCW = 1;
     }
     return s;
 }

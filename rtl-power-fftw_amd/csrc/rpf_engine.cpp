@@ -948,9 +948,8 @@ int create_engine(const rpf_config* cfg, const PfbSpec* pfb, bool inner_of_pfb, 
     // The catch-all path is the one that reads every format at every N: it takes the engines that ask for it and the
     // signed formats on every size K1 does not serve, whatever family that size runs on with cu8.
     // ... and so do the statistics: a stats engine at any size K1 does not serve runs there.
-    // ... and a cf32 engine with statistics at every size: K1 has no cf32 kernels with statistics.
-    const bool catch_all = (cfg->flags & RPF_FLAG_CATCH_ALL) != 0 || ((format != RPF_FORMAT_CU8 || stats) && !native_k1) ||
-                           (format == RPF_FORMAT_CF32 && stats);
+    // (cf32 with statistics included: K1 has every size x window x staging form of it, rpf_kernels_stats_cf32.hip.)
+    const bool catch_all = (cfg->flags & RPF_FLAG_CATCH_ALL) != 0 || ((format != RPF_FORMAT_CU8 || stats) && !native_k1);
     const int variant = static_cast<int>((cfg->flags >> 8) & 0xffu);
     // (asking for the fused four-step kernel is asking for the four-step path)
     // 32768 is served twice, by the split form 2 x 16384 and by the four-step kernels.  Plain runs are faster on the

@@ -221,7 +221,7 @@ const Variant* find_variant(int N, int vid, int fmt = kFmtCu8, bool stats = fals
 {
     if (vid == 0) {
         if (fmt == kFmtCu8) return stats ? k1_stats_variant(N, fmt) : k1_variant(N, fmt);
-        if (fmt == kFmtCf32) return stats ? nullptr : k1_cf32_variant(N, fmt);     // (no native statistics: catch-all)
+        if (fmt == kFmtCf32) return stats ? k1_stats_cf32_variant(N, fmt) : k1_cf32_variant(N, fmt);
         return stats ? k1_stats_format_variant(N, fmt) : k1_format_variant(N, fmt);
     }
 #ifdef RPF_TUNING

@@ -1,6 +1,7 @@
 // rpf_kernels_series_stats.hip -- K1 for a uniform series of per-bin statistics
 // (rpf_accumulate_device_series_stats): fft_accum_series_stats_kernel (k1_kernels.h, k1_scan_body.inc under STATS) for
-// variant 0 of every K1 size x {plain, windowed} x {LDS-DMA, VGPR staging} x {cu8, cs8, cs16}, and the fix-up kernel
+// variant 0 of every K1 size x {plain, windowed} x {LDS-DMA, VGPR staging} x {cu8, cs8, cs16} (cf32: the unit beside
+// this one, rpf_kernels_series_stats_cf32.hip, behind the same finder), and the fix-up kernel
 // that combines the segments of the spectra a workgroup boundary cuts, plane by plane.  A translation unit of its own,
 // as rpf_kernels_series.hip: it compiles beside the others and none of their kernels moves.
 #include "k1_kernels.h"
@@ -58,6 +59,8 @@ __global__ __launch_bounds__(PAIRS* GROUPS) void series_stats_fixup_kernel(const
 
 const Variant* k1_series_stats_variant(int N, int fmt)
 {
+    // (cf32: the kernels of rpf_kernels_series_stats_cf32.hip; plan, launch and fix-up below are format-free)
+    if (fmt == kFmtCf32) return k1_series_stats_cf32_variant(N, fmt);
     return fmt == kFmtCu8 ? find_default_variant<kK1SeriesStats, kFmtCu8>(N) : find_signed_variant<kK1SeriesStats>(N, fmt);
 }
 
