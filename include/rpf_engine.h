@@ -37,7 +37,9 @@ extern "C" {
                                rpf_accumulate_device_series, rpf_accumulate_series, rpf_series_launches;
                                rpf_accumulate_device_series_stats, rpf_accumulate_series_stats;
                                rpf_accumulate_device_excised, rpf_accumulate_excised;
-                               rpf_engine_create_pfb, rpf_pfb_taps */
+                               rpf_engine_create_pfb, rpf_pfb_taps;
+                               rpf_quantile_reset, rpf_quantile_append_device, rpf_quantile_append,
+                               rpf_quantile_select_device, rpf_quantile_select, rpf_quantile_rows, rpf_quantile_max_rows */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -384,6 +386,52 @@ int rpf_accumulate_device_excised(rpf_engine* e, const void* d_stream, size_t nb
 int rpf_accumulate_excised(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
                            int64_t max_spectra, double sk_lo, double sk_hi, double* out /* 3 x N, host */,
                            uint8_t* mask /* K x N or NULL, host */, int64_t* spectra_done);
+/* Per-bin quantiles of the integrations: order statistics across time, where everything above is a sum.  Everything
+ * that computes or checks them refers to this definition.
+ *   Row store.  An engine keeps up to rpf_quantile_max_rows(e) = max(1, 2^27 / N) rows of N doubles, device-resident and
+ *     engine-owned: 1 GiB at most.  It is allocated at the first append and grows by doubling; a growth synchronises once
+ *     (the caller's stream and the engine's), moves the stored rows and frees the old block.
+ *   Row.  What rpf_accumulate_device_series writes: the sum of |X_f|^2 over L = frames_per_spectrum consecutive frames,
+ *     bin N/2 = DC.  An append adds K = min(max_spectra, rpf_frames_in(e, nbytes) / L) rows (a trailing partial group is
+ *     dropped) after the rows stored so far; *appended = K (may be NULL).
+ *   Selection.  Let v_(0) <= ... <= v_(K-1) be the K stored values of a bin in ascending order; a NaN counts as larger
+ *     than every number, whatever its sign bit, as np.sort places it (-0.0 sorts below +0.0, which compare equal).  For
+ *     0 <= q <= 1, in IEEE double with every operation rounded on its own and no contraction:
+ *         h = q * (K - 1);  j = floor(h);  g = h - j;  a = v_(j);  b = v_(min(j + 1, K - 1))
+ *         Q = (g == 0 || a == b) ? a : a + g * (b - a)
+ *     so q = 0 is the minimum, q = 1 the maximum and q = 0.5 the median; a NaN among a, b with g != 0 gives NaN.  The
+ *     output of quantile i is out[i N .. i N + N).  With no rows stored every output is NaN.  stats.quantiles states the
+ *     same in numpy.
+ *   The rows are not modified by a selection: selecting again with other q, or appending more rows and selecting again,
+ *     is defined.  rpf_quantile_reset forgets the rows and keeps the allocation.
+ * rpf_quantile_append_device runs the series once, straight into the store behind the rows it holds: the rows are bit for
+ * bit those of rpf_accumulate_device_series for the same call on the same engine -- the one-launch route or spectrum by
+ * spectrum, so every size, format, frame step and RPF_FLAG_CATCH_ALL works, and rpf_series_launches reports the route of
+ * the last append.  Same stream, alignment and no-synchronise rules as rpf_accumulate_device_series (a growth excepted).
+ * rpf_quantile_append moves a host stream in the pieces rpf_accumulate_series uses, so its rows are that call's rows bit
+ * for bit; not through the buffer queues: the queues, pwr and repeats_done are not touched.  Synchronises before it returns.
+ * rpf_quantile_select_device (q: nq values on the HOST, d_out: nq x N device doubles, 16-byte aligned) enqueues an
+ * MSB-first radix select over order-preserving 64-bit keys (csrc/quantile_core.h, csrc/rpf_quantile.hip): 16 passes of
+ * 4 bits count, per (quantile, bin), the stored values that share the digits chosen so far by their next digit; where
+ * v_(j+1) is needed and the counts show no tie one further pass finds it as the smallest key above v_(j).  Exact,
+ * read-only, integer counts and no floating-point atomics: the same bits for any grid.  It reads (16 + 1) K N 8 bytes
+ * at most, all nq quantiles sharing each pass.  Returns without synchronising (its first call allocates the selection
+ * state).  rpf_quantile_select is the same into host memory on the engine's stream, and synchronises.
+ * Ordering between appends and selects is the caller's: the same stream, or synchronise.  One quantile call at a time per
+ * engine: the store and the selection state are the engine's.
+ * RPF_ERR_INVALID_ARGUMENT, before any device work and before the stream is touched: a NULL argument, a running
+ * acquisition, frames_per_spectrum < 1, max_spectra < 0; a PFB engine; an engine with RPF_FLAG_BIN_STATS; an append that
+ * would take the store over rpf_quantile_max_rows (nothing is appended: raise the frames per integration or cap
+ * max_spectra); nq < 1 or nq > 8; a q that is NaN or outside [0, 1]; a misaligned d_stream or d_out, by the series' rules. */
+int rpf_quantile_reset(rpf_engine* e);   /* rows = 0; keeps the allocation */
+int rpf_quantile_append_device(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
+                               int64_t max_spectra, void* hip_stream, int64_t* appended);
+int rpf_quantile_append(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
+                        int64_t max_spectra, int64_t* appended);
+int rpf_quantile_select_device(rpf_engine* e, const double* q /* host */, int nq, double* d_out /* nq x N */, void* hip_stream);
+int rpf_quantile_select(rpf_engine* e, const double* q, int nq, double* out /* nq x N, host */);
+int64_t rpf_quantile_rows(const rpf_engine* e);       /* -1 for NULL */
+int64_t rpf_quantile_max_rows(const rpf_engine* e);   /* -1 for NULL */
 /* Transform-kernel launches the engine's last series call (either kind) enqueued: 1 on the one-launch path (whatever K is), K on the
  * spectrum-by-spectrum path, summed over the pieces of rpf_accumulate_series; 0 before any series call and for K = 0.
  * rpf_last_launch_info reports the geometry of the last of them. */

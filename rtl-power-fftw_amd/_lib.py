@@ -110,6 +110,16 @@ _SYMBOLS = [
     ("rpf_accumulate_excised", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_quantile_reset", ctypes.c_int, [_P]),
+    ("rpf_quantile_append_device", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64, _P,
+                                                  ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_quantile_append", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_quantile_select_device", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.c_int, _P, _P]),
+    ("rpf_quantile_select", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_double)]),
+    ("rpf_quantile_rows", ctypes.c_int64, [_P]),
+    ("rpf_quantile_max_rows", ctypes.c_int64, [_P]),
     ("rpf_series_launches", ctypes.c_int, [_P]),
     ("rpf_device_fused", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P,
                                         ctypes.POINTER(ctypes.c_int64)]),

@@ -166,6 +166,13 @@ struct rpf_engine {
     double* d_excise_state = nullptr;     // the (row group, bin) accumulators, then 3 N doubles: the host entry's result
     uint8_t* d_excise_mask = nullptr;     // the host entry's mask bytes of one piece
     size_t excise_mask_bytes = 0;
+    // per-bin quantiles (rpf_quantile_*): the row store, grown by doubling up to quantile_max_rows(), and what a
+    // selection works in; all allocated at the first call that needs them
+    double* d_quantile_rows = nullptr;    // quantile_cap rows of N doubles, the first quantile_rows of them stored
+    int64_t quantile_rows = 0, quantile_cap = 0;
+    void* d_quantile_work = nullptr;      // rpf::quantile_work_bytes(N): the selection state of one call at a time
+    double* d_quantile_out = nullptr;     // rpf_quantile_select: the result on the device, quantile_out_planes x N doubles
+    int quantile_out_planes = 0;
     // polyphase filter bank front end (rpf_engine_create_pfb): this engine owns the queues and the fold, `inner` the transform
     int taps = 0;                         // T; 0 = an engine without PFB
     float* d_pfb_coeffs = nullptr;        // h[T x N]
@@ -840,6 +847,9 @@ void release_device(rpf_engine* e)
     if (e->d_series_out) (void)hipFree(e->d_series_out);
     if (e->d_excise_state) (void)hipFree(e->d_excise_state);
     if (e->d_excise_mask) (void)hipFree(e->d_excise_mask);
+    if (e->d_quantile_rows) (void)hipFree(e->d_quantile_rows);
+    if (e->d_quantile_work) (void)hipFree(e->d_quantile_work);
+    if (e->d_quantile_out) (void)hipFree(e->d_quantile_out);
     if (e->d_pfb_coeffs) (void)hipFree(e->d_pfb_coeffs);
     if (e->d_pfb_z) (void)hipFree(e->d_pfb_z);
     if (e->inner) {
@@ -2063,6 +2073,214 @@ int rpf_accumulate_excised(rpf_engine* e, const uint8_t* stream, size_t nbytes, 
     double* d_result = e->d_excise_state + rpf::excise_state_doubles(e->N);
     HIP_TRY(e, rpf::launch_excise_combine(e->d_excise_state, e->N, d_result, s));
     HIP_TRY(e, hipMemcpyAsync(out, d_result, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return RPF_OK;
+}
+
+// ---- per-bin quantiles: rows of the series kept in HBM, order statistics by radix select -----------------------------
+
+constexpr int64_t kQuantileStoreDoubles = static_cast<int64_t>(1) << 27;      // 1 GiB of rows
+
+static int64_t quantile_max_rows(const rpf_engine* e) { return std::max<int64_t>(1, kQuantileStoreDoubles / e->N); }
+
+// What every quantile entry refuses, before anything else: the store holds the rows of the plain series.
+static int quantile_check(rpf_engine* e, const char* who)
+{
+    if (!e) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+    if (e->taps)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": not on a PFB engine (quantiles of PFB spectra are not built)");
+    if (e->stats)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": not on an engine with RPF_FLAG_BIN_STATS (the row store holds the rows of rpf_accumulate_device_series)");
+    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": acquisition running");
+    return RPF_OK;
+}
+
+// The append entries' checks; *K = the rows the call appends.  Nothing on the device is touched.
+static int quantile_append_check(rpf_engine* e, const char* who, const void* stream, size_t nbytes, int64_t L,
+                                 int64_t max_spectra, int64_t* K)
+{
+    int rc = quantile_check(e, who);
+    if (rc != RPF_OK) return rc;
+    if ((rc = series_check(e, who, stream, nbytes, L, max_spectra, /*out=*/e)) != RPF_OK) return rc;
+    *K = std::min(max_spectra, frames_in(e, nbytes) / L);
+    if (e->quantile_rows + *K > quantile_max_rows(e))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": " + std::to_string(e->quantile_rows) + " rows stored and " + std::to_string(*K) +
+                        " to append, the store holds at most " + std::to_string(quantile_max_rows(e)) + " rows of " +
+                        std::to_string(e->N) + " bins (1 GiB): raise the frames per integration or cap max_spectra");
+    return RPF_OK;
+}
+
+// Room for `rows` rows (<= quantile_max_rows): the capacity doubles until they fit.  A growth synchronises `s` and the
+// engine's stream once, moves the stored rows and frees the old block.
+static int ensure_quantile_rows(rpf_engine* e, int64_t rows, hipStream_t s)
+{
+    if (rows <= e->quantile_cap) return RPF_OK;
+    int64_t cap = std::max<int64_t>(e->quantile_cap, 1);
+    while (cap < rows) cap *= 2;
+    cap = std::min(cap, quantile_max_rows(e));
+    const size_t row_bytes = sizeof(double) * static_cast<size_t>(e->N);
+    double* grown = nullptr;
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (s != e->compute_stream) HIP_TRY(e, hipStreamSynchronize(e->compute_stream));
+    HIP_TRY(e, hipMalloc(&grown, row_bytes * static_cast<size_t>(cap)));
+    if (e->quantile_rows > 0) {
+        const hipError_t err = hipMemcpy(grown, e->d_quantile_rows, row_bytes * static_cast<size_t>(e->quantile_rows), hipMemcpyDeviceToDevice);
+        if (err != hipSuccess) {
+            (void)hipFree(grown);
+            HIP_TRY(e, err);
+        }
+    }
+    if (e->d_quantile_rows) (void)hipFree(e->d_quantile_rows);
+    e->d_quantile_rows = grown;
+    e->quantile_cap = cap;
+    return RPF_OK;
+}
+
+int rpf_quantile_reset(rpf_engine* e)
+{
+    if (!e) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_quantile_reset: NULL argument");
+    e->quantile_rows = 0;
+    return RPF_OK;
+}
+
+int64_t rpf_quantile_rows(const rpf_engine* e) { return e ? e->quantile_rows : -1; }
+
+int64_t rpf_quantile_max_rows(const rpf_engine* e) { return e ? quantile_max_rows(e) : -1; }
+
+int rpf_quantile_append_device(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t frames_per_spectrum,
+                               int64_t max_spectra, void* hip_stream, int64_t* appended)
+{
+    const char* who = "rpf_quantile_append_device";
+    int64_t K = 0;
+    int rc = quantile_append_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, &K);
+    if (rc != RPF_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
+    e->series_launches = 0;
+    if (appended) *appended = K;
+    if (K == 0) return RPF_OK;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if ((rc = ensure_quantile_rows(e, e->quantile_rows + K, s)) != RPF_OK) return rc;
+    // (N is even: every row of the store is 16-byte aligned, as the series wants its output)
+    rc = series_enqueue(e, static_cast<const uint8_t*>(d_stream), frames_per_spectrum, K,
+                        e->d_quantile_rows + static_cast<size_t>(e->quantile_rows) * e->N, s);
+    if (rc != RPF_OK) return rc;
+    e->quantile_rows += K;
+    return RPF_OK;
+}
+
+int rpf_quantile_append(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
+                        int64_t max_spectra, int64_t* appended)
+{
+    int64_t K = 0;
+    int rc = quantile_append_check(e, "rpf_quantile_append", stream, nbytes, frames_per_spectrum, max_spectra, &K);
+    if (rc != RPF_OK) return rc;
+    e->series_launches = 0;
+    if (appended) *appended = K;
+    if (K == 0) return RPF_OK;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    // the pieces of series_host: whole spectra whose frames span at most 64 MB, at least one -- the same launches, so
+    // the same rows
+    constexpr size_t kSeriesPiece = static_cast<size_t>(64) << 20;
+    const int64_t L = frames_per_spectrum;
+    const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
+    const int64_t fit = frames_in(e, kSeriesPiece) / L;
+    const int64_t per_piece = std::min(K, std::max<int64_t>(1, fit));
+    const size_t piece_bytes = frame_span(e, per_piece * L);
+    hipStream_t s = e->compute_stream;
+    if (piece_bytes > e->series_in_bytes) {
+        HIP_TRY(e, hipStreamSynchronize(s));
+        if (e->d_series_in) (void)hipFree(e->d_series_in);
+        e->d_series_in = nullptr;
+        e->series_in_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->d_series_in, piece_bytes));
+        e->series_in_bytes = piece_bytes;
+    }
+    if ((rc = ensure_quantile_rows(e, e->quantile_rows + K, s)) != RPF_OK) return rc;
+    for (int64_t k0 = 0; k0 < K; k0 += per_piece) {
+        const int64_t kc = std::min(per_piece, K - k0);
+        HIP_TRY(e, hipMemcpyAsync(e->d_series_in, stream + static_cast<size_t>(k0) * hop, frame_span(e, kc * L),
+                                  hipMemcpyHostToDevice, s));
+        rc = series_enqueue(e, e->d_series_in, L, kc, e->d_quantile_rows + static_cast<size_t>(e->quantile_rows) * e->N, s);
+        const hipError_t err = hipStreamSynchronize(s);      // the piece's input is reused by the next one
+        if (rc != RPF_OK) return rc;
+        HIP_TRY(e, err);
+        e->quantile_rows += kc;
+    }
+    return RPF_OK;
+}
+
+// The select entries' checks and the ranks of the call (the same in every bin).
+static int quantile_select_check(rpf_engine* e, const char* who, const double* q, int nq, const void* out,
+                                 rpf::QuantileRanks* ranks)
+{
+    const int rc = quantile_check(e, who);
+    if (rc != RPF_OK) return rc;
+    if (nq < 1 || nq > rpf::kQuantileMaxQ)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": nq must be in 1 .. " + std::to_string(rpf::kQuantileMaxQ) + ", got " + std::to_string(nq));
+    if (!q || !out) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+    ranks->nq = nq;
+    for (int i = 0; i < rpf::kQuantileMaxQ; ++i) {
+        ranks->j[i] = 0;
+        ranks->g[i] = 0.0;
+    }
+    for (int i = 0; i < nq; ++i) {
+        if (!(q[i] >= 0.0 && q[i] <= 1.0))
+            return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                        std::string(who) + ": q[" + std::to_string(i) + "] = " + std::to_string(q[i]) + " is not in [0, 1]");
+        if (e->quantile_rows > 0) {
+            int64_t j = 0;
+            rpf::quantile_rank(q[i], e->quantile_rows, j, ranks->g[i]);
+            ranks->j[i] = static_cast<uint32_t>(j);
+        }
+    }
+    return RPF_OK;
+}
+
+static int quantile_select_enqueue(rpf_engine* e, const rpf::QuantileRanks& ranks, double* d_out, hipStream_t s)
+{
+    if (!e->d_quantile_work && e->quantile_rows > 0) HIP_TRY(e, hipMalloc(&e->d_quantile_work, rpf::quantile_work_bytes(e->N)));
+    HIP_TRY(e, rpf::launch_quantile_select(e->d_quantile_rows, e->quantile_rows, e->N, ranks, e->d_quantile_work, d_out, s));
+    return RPF_OK;
+}
+
+int rpf_quantile_select_device(rpf_engine* e, const double* q, int nq, double* d_out, void* hip_stream)
+{
+    const char* who = "rpf_quantile_select_device";
+    rpf::QuantileRanks ranks;
+    const int rc = quantile_select_check(e, who, q, nq, d_out, &ranks);
+    if (rc != RPF_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(d_out) & 15)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    return quantile_select_enqueue(e, ranks, d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+int rpf_quantile_select(rpf_engine* e, const double* q, int nq, double* out)
+{
+    rpf::QuantileRanks ranks;
+    int rc = quantile_select_check(e, "rpf_quantile_select", q, nq, out, &ranks);
+    if (rc != RPF_OK) return rc;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = e->compute_stream;
+    if (nq > e->quantile_out_planes) {
+        HIP_TRY(e, hipStreamSynchronize(s));
+        if (e->d_quantile_out) (void)hipFree(e->d_quantile_out);
+        e->d_quantile_out = nullptr;
+        e->quantile_out_planes = 0;
+        HIP_TRY(e, hipMalloc(&e->d_quantile_out, sizeof(double) * static_cast<size_t>(nq) * e->N));
+        e->quantile_out_planes = nq;
+    }
+    if ((rc = quantile_select_enqueue(e, ranks, e->d_quantile_out, s)) != RPF_OK) return rc;
+    HIP_TRY(e, hipMemcpyAsync(out, e->d_quantile_out, sizeof(double) * static_cast<size_t>(nq) * e->N, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     return RPF_OK;
 }

@@ -11,6 +11,7 @@
 #include "fft_core.h"
 #include "hop_partition.h"
 #include "pfb_core.h"
+#include "quantile_core.h"
 #include "series_partition.h"
 
 namespace rpf {
@@ -93,6 +94,15 @@ hipError_t launch_excise_rows(const double* d_rows, int64_t kc, int64_t k0, int 
                               double* d_state, uint8_t* d_mask, bool first, hipStream_t stream);
 // After the last piece: d_out[3 x N] = clean, kept, total (16-byte aligned), the accumulators added in the fixed order.
 hipError_t launch_excise_combine(const double* d_state, int N, double* d_out, hipStream_t stream);
+
+// ---- per-bin quantiles of stored rows (rpf_quantile.hip, quantile_core.h) ----
+// Bins whose selection state the workspace holds at a time (a call walks N in such chunks), and the workspace's size.
+int quantile_chunk(int N);
+size_t quantile_work_bytes(int N);
+// d_out[q N + b] = the quantile of ranks (j[q], g[q]) over d_rows[0 .. K)[b], K x N doubles which are only read; d_work:
+// quantile_work_bytes(N) bytes, owned by one call at a time (not read for K = 0: every output is then NaN).  j[q] < K.
+hipError_t launch_quantile_select(const double* d_rows, int64_t K, int N, const QuantileRanks& ranks, void* d_work,
+                                  double* d_out, hipStream_t stream);
 
 // d_out[bin] = (accumulate ? d_out[bin] : 0) + sum_{s < nslots} d_partial[s*stride + bin],
 // summed in a fixed order (deterministic).

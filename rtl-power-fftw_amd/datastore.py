@@ -333,6 +333,69 @@ class Datastore:
             mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if want_mask else None, ctypes.byref(done)))
         return out, (mask[:done.value] if want_mask else None), done.value
 
+    # -- per-bin quantiles of the integrations (rpf_quantile_*; include/rpf_engine.h has the definition) ----------
+    def quantile_reset(self):
+        """rpf_quantile_reset: forget the stored rows (the allocation stays)."""
+        self._check(self._lib.rpf_quantile_reset(self._handle))
+
+    @property
+    def quantile_rows(self):
+        """rpf_quantile_rows: rows the store holds."""
+        return self._lib.rpf_quantile_rows(self._handle)
+
+    @property
+    def quantile_max_rows(self):
+        """rpf_quantile_max_rows: rows the store can hold, max(1, 2^27 / N)."""
+        return self._lib.rpf_quantile_max_rows(self._handle)
+
+    def quantile_append_device(self, d_stream_ptr, nbytes, frames_per_spectrum, max_spectra, hip_stream=0):
+        """rpf_quantile_append_device: the rows accumulate_device_series would write for this call, appended to the
+        engine's row store; asynchronous.  Returns the number of rows appended."""
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_quantile_append_device(
+            self._handle, ctypes.c_void_p(d_stream_ptr), nbytes, frames_per_spectrum, max_spectra,
+            ctypes.c_void_p(hip_stream), ctypes.byref(done)))
+        return done.value
+
+    def quantile_append(self, stream, frames_per_spectrum, max_spectra=None):
+        """rpf_quantile_append: the same on a host byte stream (not through the buffer queues).  Returns the number of
+        rows appended; max_spectra None = every whole spectrum the stream holds."""
+        stream = _as_bytes(stream)
+        if max_spectra is None:
+            max_spectra = max(self.frames_in(stream.size) // frames_per_spectrum, 0) if frames_per_spectrum >= 1 else 0
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_quantile_append(
+            self._handle, ctypes.c_void_p(stream.ctypes.data), stream.size, frames_per_spectrum, max_spectra,
+            ctypes.byref(done)))
+        return done.value
+
+    @staticmethod
+    def _quantile_list(q):
+        q = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        return q, q.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+    def quantile_select_device(self, q, d_out_ptr, hip_stream=0):
+        """rpf_quantile_select_device: the quantiles q (host values in [0, 1], at most 8) of the stored rows into
+        d_out = len(q) x N device doubles; asynchronous."""
+        q, qp = self._quantile_list(q)
+        self._check(self._lib.rpf_quantile_select_device(self._handle, qp, q.size, ctypes.c_void_p(d_out_ptr),
+                                                         ctypes.c_void_p(hip_stream)))
+
+    def quantile_select(self, q):
+        """rpf_quantile_select: the same into a (len(q), N) array; stats.quantiles(rows, q) of the stored rows."""
+        q, qp = self._quantile_list(q)
+        out = np.zeros((max(q.size, 1), self.params.N), dtype=np.float64)
+        self._check(self._lib.rpf_quantile_select(self._handle, qp, q.size,
+                                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return out[:q.size]
+
+    def accumulate_quantiles(self, stream, frames_per_spectrum, q=(0.5,), max_spectra=None):
+        """Reset, append, select: the per-bin quantiles q over the integrations of `frames_per_spectrum` frames of a
+        host stream.  Returns ((len(q), N) array, K)."""
+        self.quantile_reset()
+        done = self.quantile_append(stream, frames_per_spectrum, max_spectra)
+        return self.quantile_select(q), done
+
     def series_launches(self):
         """rpf_series_launches: transform launches of the last series call (1 = the one-launch path)."""
         return self._lib.rpf_series_launches(self._handle)

@@ -139,6 +139,18 @@ void write_text_header_excised(std::ostream& out, const std::string& start_stamp
     out << "# frequency [Hz] power spectral density [dB/Hz] kept fraction" << std::endl;
 }
 
+void write_text_header_quantiles(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp,
+                                 const std::vector<double>& q)
+{
+    out << "# rtl-power-fftw output" << std::endl;
+    out << "# Acquisition start: " << start_stamp << std::endl;
+    out << "# Acquisition end: " << end_stamp << std::endl;
+    out << "#" << std::endl;
+    out << "# frequency [Hz]";
+    for (double v : q) out << " quantile " << std::setprecision(6) << v << " [dB/Hz]";
+    out << std::endl;
+}
+
 void write_text_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, bool stats)
 {
     out << "# rtl-power-fftw output" << std::endl;
@@ -224,6 +236,27 @@ void write_spectrum_text_excised(std::ostream& out, const std::vector<double>& c
         const double freq = tuned_freq + (i - N / 2.0) * samplerate / N;
         out << std::setprecision(freq_digits) << freq << " " << std::setprecision(6)
             << bin_value(mean, i, N, 1, samplerate, linear, baseline) << " " << kept[i] / static_cast<double>(K) << std::endl;
+    }
+    out << std::endl;
+    out.flush();
+}
+
+void write_spectrum_text_quantiles(std::ostream& out, const std::vector<double>& planes, const std::vector<double>& q, int N,
+                                   int64_t L, int64_t tuned_freq, int samplerate, bool linear,
+                                   const std::vector<double>* baseline)
+{
+    std::vector<std::vector<double>> columns(q.size());
+    for (size_t c = 0; c < q.size(); ++c) {
+        columns[c].assign(planes.begin() + c * N, planes.begin() + (c + 1) * N);
+        interpolate_dc(columns[c], N);
+    }
+    const int freq_digits = static_cast<int>(
+        std::ceil(std::floor(std::log10(static_cast<double>(tuned_freq))) - std::log10(samplerate / N) + 1 + 2));
+    for (int i = 0; i < N; ++i) {
+        const double freq = tuned_freq + (i - N / 2.0) * samplerate / N;
+        out << std::setprecision(freq_digits) << freq << std::setprecision(6);
+        for (const std::vector<double>& column : columns) out << " " << bin_value(column, i, N, L, samplerate, linear, baseline);
+        out << std::endl;
     }
     out << std::endl;
     out.flush();

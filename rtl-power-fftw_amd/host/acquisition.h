@@ -115,6 +115,14 @@ void write_text_header_excised(std::ostream& out, const std::string& start_stamp
 void write_spectrum_text_excised(std::ostream& out, const std::vector<double>& clean, const std::vector<double>& kept,
                                  const std::vector<double>& total, int N, int64_t K, int64_t L, int64_t tuned_freq,
                                  int samplerate, bool linear, const std::vector<double>* baseline);
+// --quantile: the header, whose last line names one column per quantile ("quantile 0.5 [dB/Hz]"), and the block.
+// planes[i N .. i N + N) = quantile q[i] of the integrations of L frames; every column is its plane / L with the DC bin
+// the mean of its neighbours, then / N / samplerate, dB and baseline as the power column always.
+void write_text_header_quantiles(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp,
+                                 const std::vector<double>& q);
+void write_spectrum_text_quantiles(std::ostream& out, const std::vector<double>& planes, const std::vector<double>& q, int N,
+                                   int64_t L, int64_t tuned_freq, int samplerate, bool linear,
+                                   const std::vector<double>* baseline);
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,
                          const std::vector<double>* baseline, std::vector<float>& row);
 // Matrix mode: append one float32 row to options.bin_file and keep the row/column

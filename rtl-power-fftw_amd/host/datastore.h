@@ -291,6 +291,34 @@ public:
                                         d_mask, hip_stream, &done));
     return done;
   }
+  // Per-bin quantiles of the integrations (rpf_quantile_*; include/rpf_engine.h has the definition): the engine keeps the
+  // rows of the series in HBM, appended call by call, and selects order statistics of every bin from them.
+  void quantile_reset() { check(rpf_quantile_reset(engine_)); }
+  int64_t quantile_rows() const { return rpf_quantile_rows(engine_); }
+  int64_t quantile_max_rows() const { return rpf_quantile_max_rows(engine_); }
+  // the rows accumulate_series would return for this call, appended to the store; returns how many
+  int64_t quantile_append(const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra) {
+    int64_t done = 0;
+    check(rpf_quantile_append(engine_, stream, nbytes, frames_per_spectrum, max_spectra, &done));
+    return done;
+  }
+  // the same on a stream resident in HBM (rpf_quantile_append_device), asynchronous on hip_stream
+  int64_t quantile_append_device(const void* d_stream, size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra,
+                                 void* hip_stream = nullptr) {
+    int64_t done = 0;
+    check(rpf_quantile_append_device(engine_, d_stream, nbytes, frames_per_spectrum, max_spectra, hip_stream, &done));
+    return done;
+  }
+  // the quantiles q (each in [0, 1], at most 8) of the stored rows: `out` (resized to q.size() x N), plane i = q[i]
+  void quantile_select(const std::vector<double>& q, std::vector<double>& out) {
+    out.assign(std::max<size_t>(q.size(), 1) * params.N, 0.0);
+    check(rpf_quantile_select(engine_, q.data(), static_cast<int>(q.size()), out.data()));
+    out.resize(q.size() * params.N);
+  }
+  // the same into d_out = q.size() x N device doubles (rpf_quantile_select_device), asynchronous on hip_stream
+  void quantile_select_device(const std::vector<double>& q, double* d_out, void* hip_stream = nullptr) {
+    check(rpf_quantile_select_device(engine_, q.data(), static_cast<int>(q.size()), d_out, hip_stream));
+  }
   // transform launches of the last series call: 1 = the one-launch path
   int series_launches() const { return rpf_series_launches(engine_); }
   // the engine behind this Datastore (multi-device scans hand it to the scan reducer)

@@ -334,6 +334,72 @@ long rpf_host_format_text_excised(const double* clean, const double* kept, const
     return copy_out(os.str(), out, cap);
 }
 
+// rpf_host::Datastore's quantile calls (needs a device): the host stream cut into `pieces` parts of whole integrations,
+// each appended (quantile_append), then ONE quantile_select of q[nq] into out[nq x N]; rows_out: quantile_rows() before
+// the select.  Returns the rows appended, or -(exit code) with the message in `msg`.
+long long rpf_host_accumulate_quantiles(int N, int sample_format, int frame_step, const unsigned char* stream, size_t nbytes,
+                                        long long L, int pieces, const double* q, int nq, double* out, long long* rows_out,
+                                        int* launches, char* msg, size_t cap)
+{
+    try {
+        Params params;
+        params.N = N;
+        params.sample_format = sample_format;
+        params.frame_step = frame_step;
+        std::vector<float> no_window;
+        Datastore data(params, no_window);
+        data.quantile_reset();
+        const long long total = L >= 1 ? params.frames_in(static_cast<int64_t>(nbytes)) / L : 0;
+        const long long per_piece = std::max<long long>(1, (total + std::max(pieces, 1) - 1) / std::max(pieces, 1));
+        const size_t hop = static_cast<size_t>(std::max<long long>(L, 0)) * params.sample_bytes() * params.step();
+        long long done = 0;
+        do {
+            const long long got = data.quantile_append(stream + static_cast<size_t>(done) * hop,
+                                                       nbytes - static_cast<size_t>(done) * hop, L, per_piece);
+            if (got == 0) break;
+            done += got;
+        } while (done < total);
+        if (rows_out) *rows_out = data.quantile_rows();
+        if (launches) *launches = data.series_launches();
+        std::vector<double> planes;
+        data.quantile_select(std::vector<double>(q, q + std::max(nq, 0)), planes);
+        std::memcpy(out, planes.data(), sizeof(double) * planes.size());
+        return done;
+    } catch (RPFexception& e) {
+        copy_out(e.what(), msg, cap);
+        return -static_cast<long long>(e.returnValue());
+    }
+}
+
+// The --quantile header and block writers.
+long rpf_host_format_text_quantiles(const double* planes, const double* q, int nq, int N, long long L, long long tuned_freq,
+                                    int samplerate, int linear, const double* baseline, char* out, size_t cap)
+{
+    std::vector<double> p(planes, planes + static_cast<size_t>(nq) * N), qs(q, q + nq), b;
+    if (baseline) b.assign(baseline, baseline + N);
+    std::ostringstream os;
+    write_text_header_quantiles(os, "a", "b", qs);
+    write_spectrum_text_quantiles(os, p, qs, N, L, tuned_freq, samplerate, linear != 0, baseline ? &b : nullptr);
+    return copy_out(os.str(), out, cap);
+}
+
+// The --quantile options of a parsed command line: frames, and the list into q[cap_q]; returns the number of quantiles
+// (0 without --quantile), or -(exit code) with the message in `msg`.
+int rpf_host_parse_quantiles(int argc, const char* const* argv, long long* frames, double* q, int cap_q, char* msg, size_t cap)
+{
+    try {
+        Options o = parse_command_line(argc, argv);
+        *frames = o.quantile_frames;
+        int n = 0;
+        for (double v : o.quantiles)
+            if (n < cap_q) q[n++] = v;
+        return n;
+    } catch (RPFexception& e) {
+        copy_out(e.what(), msg, cap);
+        return -static_cast<int>(e.returnValue());
+    }
+}
+
 void rpf_host_synthetic(unsigned long long seed, unsigned long long first, unsigned long long n, unsigned char* out)
 {
     SyntheticSource::generate(seed, first, n, out);

@@ -75,6 +75,12 @@ const Spec kSpecs[] = {
      "leaves 1 +- sigma standard deviations are left out, bin by bin; one block with a kept-fraction column (implies "
      "--stats' engine; not with --series, --series-stats, a frequency range, -n, -t, -c, -e, -m or several --gpus)."},
     {0, "excise-sigma", Kind::Double, "sigma", "Width of the --excise thresholds in standard deviations of the estimator. Default 3."},
+    {0, "quantile", Kind::Int64, "frames",
+     "Per-bin quantiles of --input over time: the replay is cut into integrations of <frames> consecutive FFT frames and "
+     "every bin's quantiles over them are written as one block, one column per quantile (not with --series, "
+     "--series-stats, --excise, --stats, --pfb, a frequency range, -n, -t, -c, -e, -m or several --gpus)."},
+    {0, "quantiles", Kind::Text, "a,b,...",
+     "The quantiles --quantile writes, each in [0, 1], at most 8; the first is the power column. Default 0.5 (the median)."},
     {0, "pfb", Kind::Int, "taps",
      "Polyphase filter bank front end: every frame is <taps> x bins samples weighted by a windowed-sinc prototype and "
      "folded to <bins> before the FFT, 1 <= taps <= 32 (not with -w, --frame-overlap, --stats, --series, --series-stats, "
@@ -415,6 +421,46 @@ Options parse_command_line(int argc, const char* const* argv)
         if (o.matrixMode) conflict("does not combine with -m (matrix mode): the average is one text block.");
         if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
         o.bin_stats = true;
+    }
+    if (p.has("quantiles") && !p.has("quantile"))
+        throw RPFexception("Option --quantiles needs --quantile: it lists the quantiles that one writes. Exiting.",
+                           ReturnValue::InvalidArgument);
+    if (p.has("quantile")) {
+        o.quantile_frames = to_number<int64_t>(*find_spec("--quantile"), p.get("quantile"));
+        auto conflict = [](const std::string& what) {
+            throw RPFexception("Option --quantile " + what + " Exiting.", ReturnValue::InvalidArgument);
+        };
+        if (o.quantile_frames < 1) conflict("needs a number of frames of at least 1, got " + p.get("quantile") + ".");
+        o.quantiles.assign(1, 0.5);
+        if (p.has("quantiles")) {
+            const std::string list = p.get("quantiles");
+            o.quantiles.clear();
+            size_t pos = 0;
+            while (pos <= list.size()) {
+                const size_t comma = std::min(list.find(',', pos), list.size());
+                const std::string item = list.substr(pos, comma - pos);
+                char* end = nullptr;
+                const double v = std::strtod(item.c_str(), &end);
+                if (item.empty() || *end != '\0' || !(v >= 0.0 && v <= 1.0))
+                    conflict("could not use the list given to --quantiles: " + list + ". Expecting comma-separated numbers in [0, 1].");
+                o.quantiles.push_back(v);
+                pos = comma + 1;
+            }
+            if (o.quantiles.size() > 8) conflict("takes at most 8 values in --quantiles, got " + std::to_string(o.quantiles.size()) + ".");
+        }
+        if (!p.has("input")) conflict("needs --input: it ranks the integrations of a replayed stream.");
+        for (const char* name : {"series", "series-stats", "excise"})
+            if (p.has(name))
+                conflict(std::string("does not combine with --") + name + ": one product of the integrations per run.");
+        if (p.has("stats")) conflict("does not combine with --stats: the row store holds the plain series.");
+        if (p.has("pfb")) conflict("does not combine with --pfb: quantiles of PFB spectra are not built.");
+        if (o.freq_hopping_isSet) conflict("does not combine with a frequency range in -f: a replay is one stream.");
+        for (const char* name : {"repeats", "time", "continue", "elapsed"})
+            if (p.has(name))
+                conflict(std::string("does not combine with --") + name + " (-" + find_spec(std::string("--") + name)->short_name +
+                         "): the integration length is its own argument and the replay is read once.");
+        if (o.matrixMode) conflict("does not combine with -m (matrix mode): the quantiles are columns of one text block.");
+        if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
     }
     if (p.has("input")) o.input_file = p.get("input");
     o.synthetic = p.has("synthetic");

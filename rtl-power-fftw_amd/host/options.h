@@ -57,6 +57,8 @@ struct Options : Params {
     bool series_stats = false;       // --series-stats <frames>: the same with the --stats columns per block (sets both above)
     int64_t excise_frames = 0;       // --excise <frames>: the replay's average without the SK-flagged integrations (0 = off)
     double excise_sigma = 3.0;       // --excise-sigma <s>: its thresholds, sk_limits(frames, s)
+    int64_t quantile_frames = 0;     // --quantile <frames>: per-bin quantiles over the replay's integrations of <frames> frames (0 = off)
+    std::vector<double> quantiles;   // --quantiles a,b,...: which (each in [0, 1], at most 8); default 0.5
     // (--pfb <taps> sets Params::pfb_taps; the coefficients are the default prototype)
     bool show_help = false, show_version = false;
 };

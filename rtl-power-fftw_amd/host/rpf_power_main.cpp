@@ -486,6 +486,67 @@ int run_excise(const Options& options, AuxData& aux, int actual_samplerate, int6
     return 0;
 }
 
+// --quantile <frames> [--quantiles a,b,...]: every bin's quantiles over the replay's integrations of <frames> frames
+// (rpf_quantile_append per piece, ONE rpf_quantile_select at the end), one block for the file.  The file is read in
+// pieces of whole integrations as run_series reads it; the rows stay in the engine's store on the device.
+int run_quantile(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
+{
+    Datastore data(options, aux.window_values);
+    std::FILE* file = options.input_file == "-" ? stdin : std::fopen(options.input_file.c_str(), "rb");
+    if (!file) throw RPFexception("Could not open " + options.input_file + ".", ReturnValue::InvalidInput);
+    struct CloseOnExit {
+        std::FILE* f;
+        ~CloseOnExit() { if (f != stdin) std::fclose(f); }
+    } close_file{file};
+    const int64_t L = options.quantile_frames;
+    const int64_t b = options.sample_bytes();
+    const int64_t frame = b * options.N, pitch = b * options.step();
+    const int64_t piece_budget = static_cast<int64_t>(64) << 20;
+    const int64_t fit = piece_budget < frame ? 0 : ((piece_budget - frame) / pitch + 1) / L;
+    const int64_t per_piece = std::max<int64_t>(1, fit);
+    std::vector<uint8_t> bytes(static_cast<size_t>(options.frame_span(per_piece * L)));
+    size_t have = 0;
+    int64_t K = 0;
+    bool ended = false, one_launch = true;
+    set_CtrlC_handler(true);
+    const std::string start_stamp = Acquisition::utc_now();
+    data.quantile_reset();
+    while (!checkInterrupt(InterruptState::FinishNow)) {
+        while (!ended && have < bytes.size()) {
+            const size_t got = std::fread(bytes.data() + have, 1, bytes.size() - have, file);
+            if (got == 0) ended = true;
+            have += got;
+        }
+        const int64_t coming = std::min(per_piece, options.frames_in(static_cast<int64_t>(have)) / L);
+        if (K + coming > data.quantile_max_rows())
+            throw RPFexception("Option --quantile: the input holds more than " + std::to_string(data.quantile_max_rows()) +
+                               " integrations of " + std::to_string(L) + " frames, which is what the device keeps of " +
+                               std::to_string(options.N) + " bins (1 GiB of rows): raise <frames>. Exiting.",
+                               ReturnValue::InvalidArgument);
+        const int64_t done = data.quantile_append(bytes.data(), have, L, per_piece);
+        if (done == 0) break;
+        one_launch = one_launch && data.series_launches() == 1;
+        K += done;
+        const size_t used = static_cast<size_t>(done * L * pitch);      // the next integration starts here
+        std::memmove(bytes.data(), bytes.data() + used, have - used);
+        have -= used;
+        if (ended && static_cast<int64_t>(have) < options.frame_span(L)) break;
+    }
+    if (K == 0)
+        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+    std::vector<double> planes;
+    data.quantile_select(options.quantiles, planes);
+    const std::string end_stamp = Acquisition::utc_now();
+    write_text_header_quantiles(std::cout, start_stamp, end_stamp, options.quantiles);
+    write_spectrum_text_quantiles(std::cout, planes, options.quantiles, options.N, L, tuned_freq, actual_samplerate,
+                                  options.linear, options.baseline ? &aux.baseline_values : nullptr);
+    std::cout << std::endl;          // (the blank line that closes a pass)
+    std::cerr << "Quantiles: " << options.quantiles.size() << " of " << K << " integrations of " << L << " frames ("
+              << (one_launch ? "one launch per piece" : "one launch per spectrum") << ")" << std::endl;
+    if (chatty(options)) print_acquisition_summary(options.N, K * L, 0, 0, actual_samplerate);
+    return 0;
+}
+
 int run(int argc, char** argv)
 {
     Options options = parse_command_line(argc, argv);
@@ -535,6 +596,7 @@ int run(int argc, char** argv)
     Plan plan(options, actual_samplerate);
     plan.print();
 
+    if (options.quantile_frames > 0) return run_quantile(options, aux, actual_samplerate, source->frequency());
     if (options.excise_frames > 0) return run_excise(options, aux, actual_samplerate, source->frequency());
     if (options.series_frames > 0) return run_series(options, aux, actual_samplerate, source->frequency());
 

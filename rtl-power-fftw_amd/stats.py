@@ -54,3 +54,33 @@ def excise(rows, L, sk_lo, sk_hi):
     out[1] = keep.sum(axis=0)
     out[2] = s1.sum(axis=0)
     return out, (~keep).astype(np.uint8)
+
+
+def quantiles(rows, q):
+    """The per-bin quantiles of include/rpf_engine.h (rpf_quantile_select_device) stated in numpy, on (K, N) rows: with
+    v_(0) <= ... <= v_(K-1) the values of a bin in np.sort's order (a NaN last), h = q (K - 1), j = floor(h), g = h - j,
+    a = v_(j), b = v_(min(j + 1, K - 1)) and Q = a where g == 0 or a == b, else a + g (b - a) -- float64, one operation
+    at a time.  Returns (nq, N); all NaN for K = 0.  q: values in [0, 1]."""
+    rows = np.asarray(rows, dtype=np.float64)
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if rows.ndim != 2 or q.ndim != 1:
+        raise ValueError("quantiles: rows must be (K, N) and q one-dimensional")
+    if not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError("quantiles: every q must be in [0, 1]")
+    K, N = rows.shape
+    out = np.full((q.size, N), np.nan)
+    if K == 0:
+        return out
+    ordered = np.sort(rows, axis=0)
+    for i, qi in enumerate(q):
+        h = qi * np.float64(K - 1)
+        j = int(np.floor(h))
+        g = h - np.float64(j)
+        a = ordered[j]
+        b = ordered[min(j + 1, K - 1)]
+        with np.errstate(invalid="ignore", over="ignore"):
+            d = b - a
+            gd = g * d
+            mid = a + gd
+            out[i] = np.where((g == 0.0) | (a == b), a, mid)
+    return out
