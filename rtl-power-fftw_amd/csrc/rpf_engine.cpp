@@ -37,6 +37,7 @@
 
 #include "bluestein_tables.h"
 #include "rpf_kernels.h"
+#include "series_pieces.h"
 
 namespace {
 
@@ -172,7 +173,7 @@ struct rpf_engine {
     int64_t quantile_rows = 0, quantile_cap = 0;
     void* d_quantile_work = nullptr;      // rpf::quantile_work_bytes(N): the selection state of one call at a time
     double* d_quantile_out = nullptr;     // rpf_quantile_select: the result on the device, quantile_out_planes x N doubles
-    int quantile_out_planes = 0;
+    size_t quantile_out_planes = 0;
     // polyphase filter bank front end (rpf_engine_create_pfb): this engine owns the queues and the fold, `inner` the transform
     int taps = 0;                         // T; 0 = an engine without PFB
     float* d_pfb_coeffs = nullptr;        // h[T x N]
@@ -211,21 +212,17 @@ int fail(rpf_engine* e, int rc, const std::string& msg)
     return rc;
 }
 
-// Samples one frame spans: N, or T N on a PFB engine (whose frames advance by N).
-size_t span_samples(const rpf_engine* e) { return static_cast<size_t>(e->N) * static_cast<size_t>(std::max(e->taps, 1)); }
-
-// frames(B) of a stream of B bytes at frame step S: frame f is bytes [bfS, bfS + b span), b bytes per sample.
-int64_t frames_in(const rpf_engine* e, size_t nbytes)
+// Frame f of a stream is bytes [bfS, bfS + b span), b bytes per sample; span: N samples, or T N on a PFB engine (whose
+// frames advance by N).  series_pieces.h has the two formulas.
+rpf::FrameBytes frame_bytes(const rpf_engine* e)
 {
-    const size_t frame = e->sample_bytes * span_samples(e), step = e->sample_bytes * static_cast<size_t>(e->step);
-    return nbytes < frame ? 0 : static_cast<int64_t>((nbytes - frame) / step + 1);
+    const size_t span = static_cast<size_t>(e->N) * static_cast<size_t>(std::max(e->taps, 1));
+    return {e->sample_bytes * span, e->sample_bytes * static_cast<size_t>(e->step)};
 }
 
-// Bytes `frames` frames span: b span + bS (frames - 1).
-size_t frame_span(const rpf_engine* e, int64_t frames)
-{
-    return frames < 1 ? 0 : e->sample_bytes * (span_samples(e) + static_cast<size_t>(e->step) * static_cast<size_t>(frames - 1));
-}
+// frames(B) of a stream of B bytes at frame step S, and the bytes `frames` frames span: b span + bS (frames - 1)
+int64_t frames_in(const rpf_engine* e, size_t nbytes) { return frame_bytes(e).frames_in(nbytes); }
+size_t frame_span(const rpf_engine* e, int64_t frames) { return frame_bytes(e).span(frames); }
 
 bool overlapped(const rpf_engine* e) { return e->step != e->N; }
 
@@ -264,6 +261,49 @@ private:
             return fail(e, RPF_ERR_HARDWARE,                                             \
                         std::string(#call) + ": " + hipGetErrorString(err__));           \
     } while (0)
+
+// Engine-owned device scratch of *have units of `unit` bytes holds `need` of them.  Grows, never shrinks: a call that
+// needs more than any before it synchronises `s` and the engine's stream once, frees and allocates.
+template <class T>
+int grow_scratch(rpf_engine* e, T** d_ptr, size_t* have, size_t need, size_t unit, hipStream_t s)
+{
+    if (need <= *have) return RPF_OK;
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (s != e->compute_stream) HIP_TRY(e, hipStreamSynchronize(e->compute_stream));
+    if (*d_ptr) (void)hipFree(*d_ptr);
+    *d_ptr = nullptr;
+    *have = 0;
+    HIP_TRY(e, hipMalloc(d_ptr, need * unit));
+    *have = need;
+    return RPF_OK;
+}
+
+// The series family's host loop: the K integrations of `stream` in the pieces of series_pieces.h through d_series_in.
+// prepare(per_piece) makes room for what a piece leaves; body(k0, kc, s) enqueues integrations [k0, k0 + kc) and at most
+// one copy back.  A piece is ONE copy in from the caller's pointer (a registered stream from where it lies), the body
+// and ONE synchronise; a failed body's rc is looked at first, then the stream is synchronised and the rc returns.
+// *landed: the integrations whose synchronise succeeded, which comes after the body, so a body cannot count them.
+template <class Prepare, class Body>
+int series_host_pieces(rpf_engine* e, const uint8_t* stream, int64_t L, int64_t K, int64_t row_cap, Prepare prepare,
+                              Body body, int64_t* landed = nullptr)
+{
+    hipStream_t s = e->compute_stream;
+    const rpf::SeriesPieces p = rpf::series_pieces(frame_bytes(e), L, K, rpf::kSeriesPieceBytes, row_cap);
+    int rc = grow_scratch(e, &e->d_series_in, &e->series_in_bytes, p.bytes, 1, s);
+    if (rc != RPF_OK || (rc = prepare(p.per_piece)) != RPF_OK) return rc;
+    for (int64_t k0 = 0; k0 < K; k0 += p.per_piece) {
+        const int64_t kc = std::min(p.per_piece, K - k0);
+        HIP_TRY(e, hipMemcpyAsync(e->d_series_in, stream + static_cast<size_t>(k0) * p.hop, frame_span(e, kc * L),
+                                  hipMemcpyHostToDevice, s));
+        if ((rc = body(k0, kc, s)) != RPF_OK) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        HIP_TRY(e, hipStreamSynchronize(s));
+        if (landed) *landed = k0 + kc;
+    }
+    return RPF_OK;
+}
 
 // K1 over up to rpf::kMaxHops acquisitions in ONE launch (hop_partition.h): leaves the partial
 // spectra of hop h in the slots [slots->begin[h], slots->begin[h+1]) of e->d_partial.
@@ -1225,7 +1265,7 @@ int create_engine(const rpf_config* cfg, const PfbSpec* pfb, bool inner_of_pfb, 
     }
     // device staging ring: head room for a carried partial frame + one buffer
     // (a PFB engine carries up to a whole span, b T N bytes, less one sample)
-    e->head_room = ((e->sample_bytes * span_samples(e)) + 255) / 256 * 256;
+    e->head_room = (frame_bytes(e).frame + 255) / 256 * 256;
     // a slot (= one transform launch) holds as many buffers as fit 32 MB, at least one -- more than the pool has where the
     // buffers are small: they return to the producer when their copy lands, not when the slot is launched
     e->coalesce = inner_of_pfb ? 1 : std::max<size_t>(1, (32u << 20) / e->buffer_capacity);
@@ -1759,9 +1799,10 @@ static bool series_native(const rpf_engine* e, int64_t L)
            (e->stats ? rpf::series_stats_supported(e->N, e->format) : rpf::series_supported(e->N, e->format));
 }
 
-// want_stats: the _series_stats entries, which need the flag as the plain ones need its absence.
+// want_stats: the _series_stats entries, which need the flag as the plain ones need its absence.  *K = the spectra of
+// the call.
 static int series_check(rpf_engine* e, const char* who, const void* stream, size_t nbytes, int64_t L, int64_t max_spectra,
-                        const void* out, bool want_stats = false)
+                        const void* out, bool want_stats, int64_t* K)
 {
     if (!e || !out || (!stream && nbytes)) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
     if (e->taps)
@@ -1774,6 +1815,20 @@ static int series_check(rpf_engine* e, const char* who, const void* stream, size
     if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": acquisition running");
     if (L < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": frames_per_spectrum must be at least 1");
     if (max_spectra < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": max_spectra must not be negative");
+    *K = std::min(max_spectra, frames_in(e, nbytes) / L);
+    return RPF_OK;
+}
+
+// What all six entries of the family do after their own checks, before any device work: a device entry's pointers
+// (null in a host entry) are refused if misaligned, the launch count starts over and the caller learns K.
+static int series_begin(rpf_engine* e, const char* who, const void* d_stream, const void* d_out, int64_t K, int64_t* done)
+{
+    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
+    e->series_launches = 0;
+    if (done) *done = K;
     return RPF_OK;
 }
 
@@ -1824,15 +1879,9 @@ static int series_device(rpf_engine* e, const char* who, bool want_stats, const 
                          int64_t frames_per_spectrum, int64_t max_spectra, double* d_out, void* hip_stream,
                          int64_t* spectra_done)
 {
-    int rc = series_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out, want_stats);
-    if (rc != RPF_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
-    e->series_launches = 0;
-    const int64_t K = std::min(max_spectra, frames_in(e, nbytes) / frames_per_spectrum);
-    if (spectra_done) *spectra_done = K;
+    int64_t K = 0;
+    int rc = series_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, d_out, want_stats, &K);
+    if (rc != RPF_OK || (rc = series_begin(e, who, d_stream, d_out, K, spectra_done)) != RPF_OK) return rc;
     if (K == 0) return RPF_OK;
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
@@ -1854,68 +1903,32 @@ int rpf_accumulate_device_series_stats(rpf_engine* e, const void* d_stream, size
                          d_out, hip_stream, spectra_done);
 }
 
-// The engine's row scratch holds `rows` rows (N doubles each; a stats engine's 3 N).  Grows, never shrinks: a call that
-// needs more than any before it synchronises `s` and the engine's stream once, frees and allocates.
+// The engine's row scratch holds `rows` rows (N doubles each; a stats engine's 3 N).
 static int ensure_series_rows(rpf_engine* e, int64_t rows, hipStream_t s)
 {
-    if (static_cast<size_t>(rows) <= e->series_out_rows) return RPF_OK;
-    const size_t row = static_cast<size_t>(e->N) * (e->stats ? rpf::kStatsPlanes : 1);
-    HIP_TRY(e, hipStreamSynchronize(s));
-    if (s != e->compute_stream) HIP_TRY(e, hipStreamSynchronize(e->compute_stream));
-    if (e->d_series_out) (void)hipFree(e->d_series_out);
-    e->d_series_out = nullptr;
-    e->series_out_rows = 0;
-    HIP_TRY(e, hipMalloc(&e->d_series_out, sizeof(double) * row * static_cast<size_t>(rows)));
-    e->series_out_rows = static_cast<size_t>(rows);
-    return RPF_OK;
+    const size_t row_bytes = sizeof(double) * e->N * (e->stats ? rpf::kStatsPlanes : 1);
+    return grow_scratch(e, &e->d_series_out, &e->series_out_rows, static_cast<size_t>(rows), row_bytes, s);
 }
 
-static int series_host(rpf_engine* e, const char* who, bool want_stats, const uint8_t* stream, size_t nbytes,
-                       int64_t frames_per_spectrum, int64_t max_spectra, double* out, int64_t* spectra_done)
+static int series_host(rpf_engine* e, const char* who, bool want_stats, const uint8_t* stream, size_t nbytes, int64_t L,
+                       int64_t max_spectra, double* out, int64_t* spectra_done)
 {
-    int rc = series_check(e, who, stream, nbytes, frames_per_spectrum, max_spectra, out, want_stats);
-    if (rc != RPF_OK) return rc;
-    e->series_launches = 0;
-    const int64_t L = frames_per_spectrum;
-    const int64_t K = std::min(max_spectra, frames_in(e, nbytes) / L);
-    if (spectra_done) *spectra_done = K;
+    int64_t K = 0;
+    int rc = series_check(e, who, stream, nbytes, L, max_spectra, out, want_stats, &K);
+    if (rc != RPF_OK || (rc = series_begin(e, who, nullptr, nullptr, K, spectra_done)) != RPF_OK) return rc;
     if (K == 0) return RPF_OK;
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
-    // A piece = the whole number of spectra whose frames span at most kSeriesPiece bytes, at least one spectrum;
-    // spectrum k starts at byte k L bS and p spectra span frame_span(p L) bytes.
-    constexpr size_t kSeriesPiece = static_cast<size_t>(64) << 20;
     const size_t row = static_cast<size_t>(e->N) * (e->stats ? rpf::kStatsPlanes : 1);       // doubles per row
-    const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
-    const int64_t fit = frames_in(e, kSeriesPiece) / L;
-    const int64_t per_piece = std::min(K, std::max<int64_t>(1, fit));
-    const size_t piece_bytes = frame_span(e, per_piece * L);
-    if (piece_bytes > e->series_in_bytes) {
-        HIP_TRY(e, hipStreamSynchronize(e->compute_stream));
-        if (e->d_series_in) (void)hipFree(e->d_series_in);
-        e->d_series_in = nullptr;
-        e->series_in_bytes = 0;
-        HIP_TRY(e, hipMalloc(&e->d_series_in, piece_bytes));
-        e->series_in_bytes = piece_bytes;
-    }
-    if ((rc = ensure_series_rows(e, per_piece, e->compute_stream)) != RPF_OK) return rc;
-    // (a stream pinned with rpf_stream_register is copied from where it lies, asynchronously; a pageable one through
-    // the runtime's own staging)
-    hipStream_t s = e->compute_stream;
-    for (int64_t k0 = 0; k0 < K; k0 += per_piece) {
-        const int64_t kc = std::min(per_piece, K - k0);
-        HIP_TRY(e, hipMemcpyAsync(e->d_series_in, stream + static_cast<size_t>(k0) * hop, frame_span(e, kc * L),
-                                  hipMemcpyHostToDevice, s));
-        rc = series_enqueue(e, e->d_series_in, L, kc, e->d_series_out, s);
-        if (rc != RPF_OK) {
-            (void)hipStreamSynchronize(s);
-            return rc;
-        }
-        HIP_TRY(e, hipMemcpyAsync(out + static_cast<size_t>(k0) * row, e->d_series_out, sizeof(double) * row * static_cast<size_t>(kc),
-                                  hipMemcpyDeviceToHost, s));
-        HIP_TRY(e, hipStreamSynchronize(s));       // the piece's buffers are reused by the next one
-    }
-    return RPF_OK;
+    return series_host_pieces(
+        e, stream, L, K, INT64_MAX, [&](int64_t per_piece) { return ensure_series_rows(e, per_piece, e->compute_stream); },
+        [&](int64_t k0, int64_t kc, hipStream_t s) -> int {
+            const int rc = series_enqueue(e, e->d_series_in, L, kc, e->d_series_out, s);
+            if (rc != RPF_OK) return rc;
+            HIP_TRY(e, hipMemcpyAsync(out + static_cast<size_t>(k0) * row, e->d_series_out, sizeof(double) * row * static_cast<size_t>(kc),
+                                      hipMemcpyDeviceToHost, s));
+            return RPF_OK;
+        });
 }
 
 int rpf_accumulate_series(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
@@ -1937,9 +1950,9 @@ constexpr size_t kExciseRowBytes = static_cast<size_t>(64) << 20;      // a piec
 
 // Everything series_check refuses for a stats entry, and what only the excised entries refuse.
 static int excise_check(rpf_engine* e, const char* who, const void* stream, size_t nbytes, int64_t L, int64_t max_spectra,
-                        double sk_lo, double sk_hi, const void* out)
+                        double sk_lo, double sk_hi, const void* out, int64_t* K)
 {
-    const int rc = series_check(e, who, stream, nbytes, L, max_spectra, out, /*want_stats=*/true);
+    const int rc = series_check(e, who, stream, nbytes, L, max_spectra, out, /*want_stats=*/true, K);
     if (rc != RPF_OK) return rc;
     if (L < 2)
         return fail(e, RPF_ERR_INVALID_ARGUMENT,
@@ -1951,10 +1964,9 @@ static int excise_check(rpf_engine* e, const char* who, const void* stream, size
     return RPF_OK;
 }
 
-static int64_t excise_rows_per_piece(const rpf_engine* e, int64_t K)
+static int64_t excise_row_cap(const rpf_engine* e)
 {
-    const size_t row_bytes = sizeof(double) * rpf::kStatsPlanes * static_cast<size_t>(e->N);
-    return std::min(K, std::max<int64_t>(1, static_cast<int64_t>(kExciseRowBytes / row_bytes)));
+    return std::max<int64_t>(1, static_cast<int64_t>(kExciseRowBytes / (sizeof(double) * rpf::kStatsPlanes * e->N)));
 }
 
 static int ensure_excise_state(rpf_engine* e)
@@ -1981,16 +1993,10 @@ int rpf_accumulate_device_excised(rpf_engine* e, const void* d_stream, size_t nb
                                   void* hip_stream, int64_t* spectra_done)
 {
     const char* who = "rpf_accumulate_device_excised";
-    int rc = excise_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi, d_out);
-    if (rc != RPF_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
-    e->series_launches = 0;
     const int64_t L = frames_per_spectrum;
-    const int64_t K = std::min(max_spectra, frames_in(e, nbytes) / L);
-    if (spectra_done) *spectra_done = K;
+    int64_t K = 0;
+    int rc = excise_check(e, who, d_stream, nbytes, L, max_spectra, sk_lo, sk_hi, d_out, &K);
+    if (rc != RPF_OK || (rc = series_begin(e, who, d_stream, d_out, K, spectra_done)) != RPF_OK) return rc;
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -1998,10 +2004,9 @@ int rpf_accumulate_device_excised(rpf_engine* e, const void* d_stream, size_t nb
         HIP_TRY(e, hipMemsetAsync(d_out, 0, sizeof(double) * rpf::kExcisePlanes * e->N, s));
         return RPF_OK;
     }
-    const int64_t per_piece = excise_rows_per_piece(e, K);
-    if ((rc = ensure_series_rows(e, per_piece, s)) != RPF_OK) return rc;
-    if ((rc = ensure_excise_state(e)) != RPF_OK) return rc;
-    const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
+    const int64_t per_piece = std::min(K, excise_row_cap(e));
+    if ((rc = ensure_series_rows(e, per_piece, s)) != RPF_OK || (rc = ensure_excise_state(e)) != RPF_OK) return rc;
+    const size_t hop = static_cast<size_t>(L) * frame_bytes(e).pitch;
     for (int64_t k0 = 0; k0 < K; k0 += per_piece) {
         const int64_t kc = std::min(per_piece, K - k0);
         rc = excise_piece(e, static_cast<const uint8_t*>(d_stream) + static_cast<size_t>(k0) * hop, L, k0, kc, sk_lo, sk_hi,
@@ -2016,12 +2021,11 @@ int rpf_accumulate_excised(rpf_engine* e, const uint8_t* stream, size_t nbytes, 
                            int64_t max_spectra, double sk_lo, double sk_hi, double* out, uint8_t* mask,
                            int64_t* spectra_done)
 {
-    int rc = excise_check(e, "rpf_accumulate_excised", stream, nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi, out);
-    if (rc != RPF_OK) return rc;
-    e->series_launches = 0;
+    const char* who = "rpf_accumulate_excised";
     const int64_t L = frames_per_spectrum;
-    const int64_t K = std::min(max_spectra, frames_in(e, nbytes) / L);
-    if (spectra_done) *spectra_done = K;
+    int64_t K = 0;
+    int rc = excise_check(e, who, stream, nbytes, L, max_spectra, sk_lo, sk_hi, out, &K);
+    if (rc != RPF_OK || (rc = series_begin(e, who, nullptr, nullptr, K, spectra_done)) != RPF_OK) return rc;
     const size_t out_doubles = rpf::kExcisePlanes * static_cast<size_t>(e->N);
     if (K == 0) {
         std::fill(out, out + out_doubles, 0.0);
@@ -2030,46 +2034,23 @@ int rpf_accumulate_excised(rpf_engine* e, const uint8_t* stream, size_t nbytes, 
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     hipStream_t s = e->compute_stream;
-    // a piece: whole spectra whose frames span at most 64 MB of input (series_host's pieces) and whose rows fit the
-    // row scratch, at least one
-    constexpr size_t kSeriesPiece = static_cast<size_t>(64) << 20;
-    const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
-    const int64_t fit = frames_in(e, kSeriesPiece) / L;
-    const int64_t per_piece = std::min(excise_rows_per_piece(e, K), std::max<int64_t>(1, fit));
-    const size_t piece_bytes = frame_span(e, per_piece * L);
-    if (piece_bytes > e->series_in_bytes) {
-        HIP_TRY(e, hipStreamSynchronize(s));
-        if (e->d_series_in) (void)hipFree(e->d_series_in);
-        e->d_series_in = nullptr;
-        e->series_in_bytes = 0;
-        HIP_TRY(e, hipMalloc(&e->d_series_in, piece_bytes));
-        e->series_in_bytes = piece_bytes;
-    }
-    const size_t mask_bytes = mask ? static_cast<size_t>(per_piece) * e->N : 0;
-    if (mask_bytes > e->excise_mask_bytes) {
-        HIP_TRY(e, hipStreamSynchronize(s));
-        if (e->d_excise_mask) (void)hipFree(e->d_excise_mask);
-        e->d_excise_mask = nullptr;
-        e->excise_mask_bytes = 0;
-        HIP_TRY(e, hipMalloc(&e->d_excise_mask, mask_bytes));
-        e->excise_mask_bytes = mask_bytes;
-    }
-    if ((rc = ensure_series_rows(e, per_piece, s)) != RPF_OK) return rc;
-    if ((rc = ensure_excise_state(e)) != RPF_OK) return rc;
-    for (int64_t k0 = 0; k0 < K; k0 += per_piece) {
-        const int64_t kc = std::min(per_piece, K - k0);
-        HIP_TRY(e, hipMemcpyAsync(e->d_series_in, stream + static_cast<size_t>(k0) * hop, frame_span(e, kc * L),
-                                  hipMemcpyHostToDevice, s));
-        rc = excise_piece(e, e->d_series_in, L, k0, kc, sk_lo, sk_hi, mask ? e->d_excise_mask : nullptr, s);
-        if (rc != RPF_OK) {
-            (void)hipStreamSynchronize(s);
-            return rc;
-        }
-        if (mask)
-            HIP_TRY(e, hipMemcpyAsync(mask + static_cast<size_t>(k0) * e->N, e->d_excise_mask, static_cast<size_t>(kc) * e->N,
-                                      hipMemcpyDeviceToHost, s));
-        HIP_TRY(e, hipStreamSynchronize(s));       // the piece's buffers are reused by the next one
-    }
+    // (a piece's rows are capped as the device entry's are, on top of its input's 64 MB)
+    rc = series_host_pieces(
+        e, stream, L, K, excise_row_cap(e),
+        [&](int64_t per_piece) -> int {
+            int rc = grow_scratch(e, &e->d_excise_mask, &e->excise_mask_bytes, mask ? static_cast<size_t>(per_piece) * e->N : 0, 1, s);
+            if (rc == RPF_OK) rc = ensure_series_rows(e, per_piece, s);
+            return rc != RPF_OK ? rc : ensure_excise_state(e);
+        },
+        [&](int64_t k0, int64_t kc, hipStream_t s) -> int {
+            const int rc = excise_piece(e, e->d_series_in, L, k0, kc, sk_lo, sk_hi, mask ? e->d_excise_mask : nullptr, s);
+            if (rc != RPF_OK) return rc;
+            if (mask)
+                HIP_TRY(e, hipMemcpyAsync(mask + static_cast<size_t>(k0) * e->N, e->d_excise_mask, static_cast<size_t>(kc) * e->N,
+                                          hipMemcpyDeviceToHost, s));
+            return RPF_OK;
+        });
+    if (rc != RPF_OK) return rc;
     double* d_result = e->d_excise_state + rpf::excise_state_doubles(e->N);
     HIP_TRY(e, rpf::launch_excise_combine(e->d_excise_state, e->N, d_result, s));
     HIP_TRY(e, hipMemcpyAsync(out, d_result, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s));
@@ -2102,8 +2083,7 @@ static int quantile_append_check(rpf_engine* e, const char* who, const void* str
 {
     int rc = quantile_check(e, who);
     if (rc != RPF_OK) return rc;
-    if ((rc = series_check(e, who, stream, nbytes, L, max_spectra, /*out=*/e)) != RPF_OK) return rc;
-    *K = std::min(max_spectra, frames_in(e, nbytes) / L);
+    if ((rc = series_check(e, who, stream, nbytes, L, max_spectra, /*out=*/e, /*want_stats=*/false, K)) != RPF_OK) return rc;
     if (e->quantile_rows + *K > quantile_max_rows(e))
         return fail(e, RPF_ERR_INVALID_ARGUMENT,
                     std::string(who) + ": " + std::to_string(e->quantile_rows) + " rows stored and " + std::to_string(*K) +
@@ -2155,11 +2135,7 @@ int rpf_quantile_append_device(rpf_engine* e, const void* d_stream, size_t nbyte
     const char* who = "rpf_quantile_append_device";
     int64_t K = 0;
     int rc = quantile_append_check(e, who, d_stream, nbytes, frames_per_spectrum, max_spectra, &K);
-    if (rc != RPF_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    e->series_launches = 0;
-    if (appended) *appended = K;
+    if (rc != RPF_OK || (rc = series_begin(e, who, d_stream, nullptr, K, appended)) != RPF_OK) return rc;
     if (K == 0) return RPF_OK;
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
@@ -2176,43 +2152,25 @@ int rpf_quantile_append_device(rpf_engine* e, const void* d_stream, size_t nbyte
 int rpf_quantile_append(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
                         int64_t max_spectra, int64_t* appended)
 {
+    const char* who = "rpf_quantile_append";
+    const int64_t L = frames_per_spectrum;
     int64_t K = 0;
-    int rc = quantile_append_check(e, "rpf_quantile_append", stream, nbytes, frames_per_spectrum, max_spectra, &K);
-    if (rc != RPF_OK) return rc;
-    e->series_launches = 0;
-    if (appended) *appended = K;
+    int rc = quantile_append_check(e, who, stream, nbytes, L, max_spectra, &K);
+    if (rc != RPF_OK || (rc = series_begin(e, who, nullptr, nullptr, K, appended)) != RPF_OK) return rc;
     if (K == 0) return RPF_OK;
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
-    // the pieces of series_host: whole spectra whose frames span at most 64 MB, at least one -- the same launches, so
-    // the same rows
-    constexpr size_t kSeriesPiece = static_cast<size_t>(64) << 20;
-    const int64_t L = frames_per_spectrum;
-    const size_t hop = static_cast<size_t>(L) * e->sample_bytes * static_cast<size_t>(e->step);
-    const int64_t fit = frames_in(e, kSeriesPiece) / L;
-    const int64_t per_piece = std::min(K, std::max<int64_t>(1, fit));
-    const size_t piece_bytes = frame_span(e, per_piece * L);
-    hipStream_t s = e->compute_stream;
-    if (piece_bytes > e->series_in_bytes) {
-        HIP_TRY(e, hipStreamSynchronize(s));
-        if (e->d_series_in) (void)hipFree(e->d_series_in);
-        e->d_series_in = nullptr;
-        e->series_in_bytes = 0;
-        HIP_TRY(e, hipMalloc(&e->d_series_in, piece_bytes));
-        e->series_in_bytes = piece_bytes;
-    }
-    if ((rc = ensure_quantile_rows(e, e->quantile_rows + K, s)) != RPF_OK) return rc;
-    for (int64_t k0 = 0; k0 < K; k0 += per_piece) {
-        const int64_t kc = std::min(per_piece, K - k0);
-        HIP_TRY(e, hipMemcpyAsync(e->d_series_in, stream + static_cast<size_t>(k0) * hop, frame_span(e, kc * L),
-                                  hipMemcpyHostToDevice, s));
-        rc = series_enqueue(e, e->d_series_in, L, kc, e->d_quantile_rows + static_cast<size_t>(e->quantile_rows) * e->N, s);
-        const hipError_t err = hipStreamSynchronize(s);      // the piece's input is reused by the next one
-        if (rc != RPF_OK) return rc;
-        HIP_TRY(e, err);
-        e->quantile_rows += kc;
-    }
-    return RPF_OK;
+    // the pieces of rpf_accumulate_series (the same launches, so the same rows) to the store's tail, counted once landed
+    const int64_t stored = e->quantile_rows;
+    int64_t landed = 0;
+    rc = series_host_pieces(
+        e, stream, L, K, INT64_MAX, [&](int64_t) { return ensure_quantile_rows(e, stored + K, e->compute_stream); },
+        [&](int64_t k0, int64_t kc, hipStream_t s) {
+            return series_enqueue(e, e->d_series_in, L, kc, e->d_quantile_rows + static_cast<size_t>(stored + k0) * e->N, s);
+        },
+        &landed);
+    e->quantile_rows = stored + landed;
+    return rc;
 }
 
 // The select entries' checks and the ranks of the call (the same in every bin).
@@ -2271,14 +2229,8 @@ int rpf_quantile_select(rpf_engine* e, const double* q, int nq, double* out)
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     hipStream_t s = e->compute_stream;
-    if (nq > e->quantile_out_planes) {
-        HIP_TRY(e, hipStreamSynchronize(s));
-        if (e->d_quantile_out) (void)hipFree(e->d_quantile_out);
-        e->d_quantile_out = nullptr;
-        e->quantile_out_planes = 0;
-        HIP_TRY(e, hipMalloc(&e->d_quantile_out, sizeof(double) * static_cast<size_t>(nq) * e->N));
-        e->quantile_out_planes = nq;
-    }
+    rc = grow_scratch(e, &e->d_quantile_out, &e->quantile_out_planes, static_cast<size_t>(nq), sizeof(double) * e->N, s);
+    if (rc != RPF_OK) return rc;
     if ((rc = quantile_select_enqueue(e, ranks, e->d_quantile_out, s)) != RPF_OK) return rc;
     HIP_TRY(e, hipMemcpyAsync(out, e->d_quantile_out, sizeof(double) * static_cast<size_t>(nq) * e->N, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));

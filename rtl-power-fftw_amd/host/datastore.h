@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/rpf_engine.h"
+#include "../csrc/series_pieces.h"
 
 namespace rpf_host {
 
@@ -56,13 +57,11 @@ struct Params {
   int pfb_taps = 0;
   std::vector<float> pfb_coeffs;
   int64_t span_samples() const { return static_cast<int64_t>(N) * std::max(pfb_taps, 1); }
-  // bytes `frames` frames span (rpf_frame_span): b span + bS (frames - 1), b bytes per sample, span = N (T N with PFB)
-  int64_t frame_span(int64_t frames) const { return frames < 1 ? 0 : sample_bytes() * (span_samples() + step() * (frames - 1)); }
-  // frames a stream of nbytes holds (rpf_frames_in)
-  int64_t frames_in(int64_t nbytes) const {
-    const int64_t frame = sample_bytes() * span_samples();
-    return nbytes < frame ? 0 : (nbytes - frame) / (sample_bytes() * step()) + 1;
-  }
+  // frame f of a stream is bytes [f bS, f bS + b span), b bytes per sample, span = N (T N with PFB): the bytes `frames`
+  // frames span (rpf_frame_span) and the frames a stream of nbytes holds (rpf_frames_in) by the engine's own formulas
+  rpf::FrameBytes frame_bytes() const { return {static_cast<size_t>(sample_bytes() * span_samples()), static_cast<size_t>(sample_bytes() * step())}; }
+  int64_t frame_span(int64_t frames) const { return static_cast<int64_t>(frame_bytes().span(frames)); }
+  int64_t frames_in(int64_t nbytes) const { return nbytes < 0 ? 0 : frame_bytes().frames_in(static_cast<size_t>(nbytes)); }
   // a sample budget of r0 side-by-side frames as frames at step S: floor((r0 - 1) N / S) + 1 (r0 at S = N); with a PFB
   // of T taps r0 - (T - 1), at least one
   int64_t frames_for_budget(int64_t r0) const {
@@ -228,13 +227,7 @@ public:
   // Returns K = min(max_spectra, frames / L).
   int64_t accumulate_series(const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra,
                             std::vector<double>& rows) {
-    const int64_t frames = rpf_frames_in(engine_, nbytes);
-    const int64_t fit = frames_per_spectrum >= 1 ? frames / frames_per_spectrum : 0;
-    rows.assign(static_cast<size_t>(std::max<int64_t>(1, std::min(fit, std::max<int64_t>(max_spectra, 0)))) * params.N, 0.0);
-    int64_t done = 0;
-    check(rpf_accumulate_series(engine_, stream, nbytes, frames_per_spectrum, max_spectra, rows.data(), &done));
-    rows.resize(static_cast<size_t>(done) * params.N);
-    return done;
+    return series_rows(rpf_accumulate_series, 1, stream, nbytes, frames_per_spectrum, max_spectra, rows);
   }
   // The same on a stream resident in HBM (rpf_accumulate_device_series): d_out = K x N device doubles, asynchronous
   // on hip_stream.
@@ -248,14 +241,7 @@ public:
   // (resized to K x 3 x N) = S1[N], S2[N], PK[N] of frames [k L, (k + 1) L); spectral_kurtosis with M = L per row.
   int64_t accumulate_series_stats(const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra,
                                   std::vector<double>& rows) {
-    const int64_t frames = rpf_frames_in(engine_, nbytes);
-    const int64_t fit = frames_per_spectrum >= 1 ? frames / frames_per_spectrum : 0;
-    const size_t row = static_cast<size_t>(3) * params.N;
-    rows.assign(static_cast<size_t>(std::max<int64_t>(1, std::min(fit, std::max<int64_t>(max_spectra, 0)))) * row, 0.0);
-    int64_t done = 0;
-    check(rpf_accumulate_series_stats(engine_, stream, nbytes, frames_per_spectrum, max_spectra, rows.data(), &done));
-    rows.resize(static_cast<size_t>(done) * row);
-    return done;
+    return series_rows(rpf_accumulate_series_stats, 3, stream, nbytes, frames_per_spectrum, max_spectra, rows);
   }
   // The same on a stream resident in HBM (rpf_accumulate_device_series_stats): d_out = K x 3 x N device doubles,
   // asynchronous on hip_stream.
@@ -271,10 +257,8 @@ public:
   // in a bin iff sk_lo <= SK <= sk_hi; mask: NULL, or resized to K x N bytes, 1 = flagged.  Returns K.
   int64_t accumulate_excised(const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra,
                              double sk_lo, double sk_hi, std::vector<double>& out, std::vector<uint8_t>* mask = nullptr) {
-    const int64_t frames = rpf_frames_in(engine_, nbytes);
-    const int64_t fit = frames_per_spectrum >= 1 ? frames / frames_per_spectrum : 0;
     out.assign(static_cast<size_t>(3) * params.N, 0.0);
-    if (mask) mask->assign(static_cast<size_t>(std::max<int64_t>(1, std::min(fit, std::max<int64_t>(max_spectra, 0)))) * params.N, 0);
+    if (mask) mask->assign(row_capacity(nbytes, frames_per_spectrum, max_spectra) * params.N, 0);
     int64_t done = 0;
     check(rpf_accumulate_excised(engine_, stream, nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi, out.data(),
                                  mask ? mask->data() : nullptr, &done));
@@ -335,6 +319,22 @@ public:
 private:
   void check(int rc) const {
     if (rc != RPF_OK) throw RPFexception(rpf_last_error(engine_), (ReturnValue)rc);
+  }
+  // Rows a host call of the series family can return, at least one (what the engine refuses, it refuses on a buffer).
+  size_t row_capacity(size_t nbytes, int64_t frames_per_spectrum, int64_t max_spectra) const {
+    const int64_t fit = frames_per_spectrum >= 1 ? rpf_frames_in(engine_, nbytes) / frames_per_spectrum : 0;
+    return static_cast<size_t>(std::max<int64_t>(1, std::min(fit, std::max<int64_t>(max_spectra, 0))));
+  }
+  // accumulate_series and accumulate_series_stats: `entry` into rows of `planes` x N doubles
+  typedef int (*SeriesEntry)(rpf_engine*, const uint8_t*, size_t, int64_t, int64_t, double*, int64_t*);
+  int64_t series_rows(SeriesEntry entry, int planes, const uint8_t* stream, size_t nbytes, int64_t frames_per_spectrum,
+                      int64_t max_spectra, std::vector<double>& rows) {
+    const size_t row = static_cast<size_t>(planes) * params.N;
+    rows.assign(row_capacity(nbytes, frames_per_spectrum, max_spectra) * row, 0.0);
+    int64_t done = 0;
+    check(entry(engine_, stream, nbytes, frames_per_spectrum, max_spectra, rows.data(), &done));
+    rows.resize(static_cast<size_t>(done) * row);
+    return done;
   }
   rpf_engine* engine_ = nullptr;
   int64_t fused_gave_up_ = 0;

@@ -11,6 +11,7 @@
 #include "acquisition.h"
 #include "aux_data.h"
 #include "options.h"
+#include "piece_reader.h"
 #include "sample_source.h"
 #include "scan_plan.h"
 #include "units.h"
@@ -24,6 +25,37 @@ int copy_out(const std::string& s, char* out, size_t cap)
     if (s.size() + 1 > cap) return -1;
     std::memcpy(out, s.c_str(), s.size() + 1);
     return static_cast<int>(s.size());
+}
+
+// What `call` returns, or -(the reference's exit code) of what it throws with the message in `msg`.
+template <class Call>
+long long or_exit_code(char* msg, size_t cap, Call call)
+{
+    try {
+        return call();
+    } catch (RPFexception& e) {
+        copy_out(e.what(), msg, cap);
+        return -static_cast<long long>(e.returnValue());
+    }
+}
+
+// The shims that need a device run `call` on a Datastore of their own without a window: what it returns (as above) and
+// the launches of its last series call.
+template <class Call>
+long long on_datastore(int N, int sample_format, int frame_step, bool bin_stats, int* launches, char* msg, size_t cap, Call call)
+{
+    return or_exit_code(msg, cap, [&]() -> long long {
+        Params params;
+        params.N = N;
+        params.sample_format = sample_format;
+        params.frame_step = frame_step;
+        params.bin_stats = bin_stats;
+        std::vector<float> no_window;
+        Datastore data(params, no_window);
+        const long long done = call(data);
+        if (launches) *launches = data.series_launches();
+        return done;
+    });
 }
 }  // namespace
 
@@ -223,27 +255,13 @@ long long rpf_host_accumulate_series(int N, int sample_format, int frame_step, c
                                      long long L, long long max_spectra, double* out, long long cap_rows, int device_resident,
                                      int* launches, char* msg, size_t cap)
 {
-    try {
-        Params params;
-        params.N = N;
-        params.sample_format = sample_format;
-        params.frame_step = frame_step;
-        std::vector<float> no_window;
-        Datastore data(params, no_window);
-        long long done = 0;
-        if (device_resident) {
-            done = data.accumulate_device_series(stream, nbytes, L, std::min(max_spectra, cap_rows), out);
-        } else {
-            std::vector<double> rows;
-            done = data.accumulate_series(stream, nbytes, L, std::min(max_spectra, cap_rows), rows);
-            std::memcpy(out, rows.data(), sizeof(double) * rows.size());
-        }
-        if (launches) *launches = data.series_launches();
+    return on_datastore(N, sample_format, frame_step, false, launches, msg, cap, [&](Datastore& data) -> long long {
+        if (device_resident) return data.accumulate_device_series(stream, nbytes, L, std::min(max_spectra, cap_rows), out);
+        std::vector<double> rows;
+        const long long done = data.accumulate_series(stream, nbytes, L, std::min(max_spectra, cap_rows), rows);
+        std::memcpy(out, rows.data(), sizeof(double) * rows.size());
         return done;
-    } catch (RPFexception& e) {
-        copy_out(e.what(), msg, cap);
-        return -static_cast<long long>(e.returnValue());
-    }
+    });
 }
 
 // The same for the two series calls with statistics, on a Datastore with params.bin_stats: out[cap_rows x 3 x N].
@@ -251,40 +269,19 @@ long long rpf_host_accumulate_series_stats(int N, int sample_format, int frame_s
                                            size_t nbytes, long long L, long long max_spectra, double* out, long long cap_rows,
                                            int device_resident, int* launches, char* msg, size_t cap)
 {
-    try {
-        Params params;
-        params.N = N;
-        params.sample_format = sample_format;
-        params.frame_step = frame_step;
-        params.bin_stats = true;
-        std::vector<float> no_window;
-        Datastore data(params, no_window);
-        long long done = 0;
-        if (device_resident) {
-            done = data.accumulate_device_series_stats(stream, nbytes, L, std::min(max_spectra, cap_rows), out);
-        } else {
-            std::vector<double> rows;
-            done = data.accumulate_series_stats(stream, nbytes, L, std::min(max_spectra, cap_rows), rows);
-            std::memcpy(out, rows.data(), sizeof(double) * rows.size());
-        }
-        if (launches) *launches = data.series_launches();
+    return on_datastore(N, sample_format, frame_step, true, launches, msg, cap, [&](Datastore& data) -> long long {
+        if (device_resident) return data.accumulate_device_series_stats(stream, nbytes, L, std::min(max_spectra, cap_rows), out);
+        std::vector<double> rows;
+        const long long done = data.accumulate_series_stats(stream, nbytes, L, std::min(max_spectra, cap_rows), rows);
+        std::memcpy(out, rows.data(), sizeof(double) * rows.size());
         return done;
-    } catch (RPFexception& e) {
-        copy_out(e.what(), msg, cap);
-        return -static_cast<long long>(e.returnValue());
-    }
+    });
 }
 
 // datastore.h's sk_limits; 0, or -(exit code) with the message in `msg`.
 int rpf_host_sk_limits(long long M, double sigma, double* lo, double* hi, char* msg, size_t cap)
 {
-    try {
-        sk_limits(M, sigma, *lo, *hi);
-        return 0;
-    } catch (RPFexception& e) {
-        copy_out(e.what(), msg, cap);
-        return -static_cast<int>(e.returnValue());
-    }
+    return static_cast<int>(or_exit_code(msg, cap, [&]() -> long long { sk_limits(M, sigma, *lo, *hi); return 0; }));
 }
 
 // rpf_host::Datastore's two excised calls on a Datastore with params.bin_stats (needs a device): out[3 x N], mask
@@ -295,31 +292,17 @@ long long rpf_host_accumulate_excised(int N, int sample_format, int frame_step, 
                                       unsigned char* mask, long long cap_rows, int device_resident, int* launches, char* msg,
                                       size_t cap)
 {
-    try {
-        Params params;
-        params.N = N;
-        params.sample_format = sample_format;
-        params.frame_step = frame_step;
-        params.bin_stats = true;
-        std::vector<float> no_window;
-        Datastore data(params, no_window);
-        long long done = 0;
-        if (device_resident) {
-            done = data.accumulate_device_excised(stream, nbytes, L, std::min(max_spectra, cap_rows), sk_lo, sk_hi, out, mask);
-        } else {
-            std::vector<double> res;
-            std::vector<uint8_t> flags;
-            done = data.accumulate_excised(stream, nbytes, L, std::min(max_spectra, cap_rows), sk_lo, sk_hi, res,
-                                           mask ? &flags : nullptr);
-            std::memcpy(out, res.data(), sizeof(double) * res.size());
-            if (mask) std::memcpy(mask, flags.data(), flags.size());
-        }
-        if (launches) *launches = data.series_launches();
+    return on_datastore(N, sample_format, frame_step, true, launches, msg, cap, [&](Datastore& data) -> long long {
+        if (device_resident)
+            return data.accumulate_device_excised(stream, nbytes, L, std::min(max_spectra, cap_rows), sk_lo, sk_hi, out, mask);
+        std::vector<double> res;
+        std::vector<uint8_t> flags;
+        const long long done = data.accumulate_excised(stream, nbytes, L, std::min(max_spectra, cap_rows), sk_lo, sk_hi, res,
+                                                       mask ? &flags : nullptr);
+        std::memcpy(out, res.data(), sizeof(double) * res.size());
+        if (mask) std::memcpy(mask, flags.data(), flags.size());
         return done;
-    } catch (RPFexception& e) {
-        copy_out(e.what(), msg, cap);
-        return -static_cast<long long>(e.returnValue());
-    }
+    });
 }
 
 // The excised block's writer (write_spectrum_text_excised).
@@ -341,13 +324,8 @@ long long rpf_host_accumulate_quantiles(int N, int sample_format, int frame_step
                                         long long L, int pieces, const double* q, int nq, double* out, long long* rows_out,
                                         int* launches, char* msg, size_t cap)
 {
-    try {
-        Params params;
-        params.N = N;
-        params.sample_format = sample_format;
-        params.frame_step = frame_step;
-        std::vector<float> no_window;
-        Datastore data(params, no_window);
+    return on_datastore(N, sample_format, frame_step, false, launches, msg, cap, [&](Datastore& data) -> long long {
+        const Params& params = data.params;
         data.quantile_reset();
         const long long total = L >= 1 ? params.frames_in(static_cast<int64_t>(nbytes)) / L : 0;
         const long long per_piece = std::max<long long>(1, (total + std::max(pieces, 1) - 1) / std::max(pieces, 1));
@@ -360,15 +338,44 @@ long long rpf_host_accumulate_quantiles(int N, int sample_format, int frame_step
             done += got;
         } while (done < total);
         if (rows_out) *rows_out = data.quantile_rows();
-        if (launches) *launches = data.series_launches();
+        if (launches) *launches = data.series_launches();      // (also if the select below is refused)
         std::vector<double> planes;
         data.quantile_select(std::vector<double>(q, q + std::max(nq, 0)), planes);
         std::memcpy(out, planes.data(), sizeof(double) * planes.size());
         return done;
-    } catch (RPFexception& e) {
-        copy_out(e.what(), msg, cap);
-        return -static_cast<long long>(e.returnValue());
-    }
+    });
+}
+
+// Walks a file as the CLI's series modes do (piece_reader.h), crediting every piece min(per_piece, whole integrations
+// held) as the series entries do.  Piece i: out4[4 i ..] = the file offset of its first byte, the bytes held, the
+// integrations credited and where in `bytes` the first frame_span(credited L) bytes handed over were copied.  Returns
+// the pieces (at most cap_pieces and cap_bytes), or -(exit code) with the message in `msg`.
+long long rpf_host_piece_walk(const char* path, long long frame_bytes, long long pitch_bytes, long long L, long long budget,
+                              long long* per_piece, long long* out4, int cap_pieces, unsigned char* bytes, size_t cap_bytes,
+                              char* msg, size_t cap)
+{
+    return or_exit_code(msg, cap, [&]() -> long long {
+        PieceReader in(path, frame_bytes, pitch_bytes, L, budget);
+        const rpf::FrameBytes fb{static_cast<size_t>(frame_bytes), static_cast<size_t>(pitch_bytes)};
+        *per_piece = in.per_piece();
+        long long offset = 0;
+        size_t copied = 0;
+        int n = 0;
+        for (bool more = true; more; ++n) {
+            const size_t have = in.fill();
+            const long long done = std::min<long long>(in.per_piece(), fb.frames_in(have) / L);
+            if (done == 0) break;
+            const size_t handed = fb.span(done * L);
+            if (n >= cap_pieces || copied + handed > cap_bytes) return -1;
+            std::memcpy(bytes + copied, in.data(), handed);
+            const long long v[4] = {offset, static_cast<long long>(have), done, static_cast<long long>(copied)};
+            std::copy(v, v + 4, out4 + 4 * n);
+            copied += handed;
+            offset += done * L * pitch_bytes;
+            more = in.consume(done);
+        }
+        return n;
+    });
 }
 
 // The --quantile header and block writers.
@@ -387,17 +394,14 @@ long rpf_host_format_text_quantiles(const double* planes, const double* q, int n
 // (0 without --quantile), or -(exit code) with the message in `msg`.
 int rpf_host_parse_quantiles(int argc, const char* const* argv, long long* frames, double* q, int cap_q, char* msg, size_t cap)
 {
-    try {
+    return static_cast<int>(or_exit_code(msg, cap, [&]() -> long long {
         Options o = parse_command_line(argc, argv);
         *frames = o.quantile_frames;
         int n = 0;
         for (double v : o.quantiles)
             if (n < cap_q) q[n++] = v;
         return n;
-    } catch (RPFexception& e) {
-        copy_out(e.what(), msg, cap);
-        return -static_cast<int>(e.returnValue());
-    }
+    }));
 }
 
 void rpf_host_synthetic(unsigned long long seed, unsigned long long first, unsigned long long n, unsigned char* out)

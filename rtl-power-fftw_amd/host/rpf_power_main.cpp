@@ -30,6 +30,7 @@
 #include "datastore.h"
 #include "interrupts.h"
 #include "options.h"
+#include "piece_reader.h"
 #include "sample_source.h"
 #include "scan_plan.h"
 
@@ -348,26 +349,15 @@ private:
 
 // --series <frames>: the replay cut into consecutive integrations of <frames> frames (rpf_accumulate_series), one text
 // block per integration -- what `-c -n <frames> --input` writes, block for block, without an acquisition per block.
-// The file is read in pieces of whole spectra (64 MB, or one spectrum if that is larger); with overlapped frames the
-// bytes a piece's last frames share with the next piece's first are carried over.
+// The file is read in pieces of whole spectra (64 MB, or one spectrum if that is larger) with the bytes two pieces share
+// carried over: piece_reader.h.
 // --series-stats <frames> (options.series_stats): the same through rpf_accumulate_series_stats, every block with the
 // --stats columns for M = <frames> -- what `--stats -c -n <frames> --input` writes.
 int run_series(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
 {
     Datastore data(options, aux.window_values);
-    std::FILE* file = options.input_file == "-" ? stdin : std::fopen(options.input_file.c_str(), "rb");
-    if (!file) throw RPFexception("Could not open " + options.input_file + ".", ReturnValue::InvalidInput);
-    struct CloseOnExit {
-        std::FILE* f;
-        ~CloseOnExit() { if (f != stdin) std::fclose(f); }
-    } close_file{file};
     const int64_t L = options.series_frames;
-    const int64_t b = options.sample_bytes();
-    const int64_t frame = b * options.N, pitch = b * options.step();
-    const int64_t piece_budget = static_cast<int64_t>(64) << 20;
-    const int64_t fit = piece_budget < frame ? 0 : ((piece_budget - frame) / pitch + 1) / L;
-    const int64_t per_piece = std::max<int64_t>(1, fit);
-    std::vector<uint8_t> bytes(static_cast<size_t>(options.frame_span(per_piece * L)));
+    PieceReader in(options.input_file, options.sample_bytes() * options.N, options.sample_bytes() * options.step(), L);
     const std::vector<double>* baseline = options.baseline ? &aux.baseline_values : nullptr;
     std::vector<double> rows, pwr(options.N), sum_sq, peak;
     const bool stats = options.series_stats;
@@ -376,19 +366,13 @@ int run_series(const Options& options, AuxData& aux, int actual_samplerate, int6
         sum_sq.resize(options.N);
         peak.resize(options.N);
     }
-    size_t have = 0;
     int64_t written = 0;
-    bool ended = false;
     set_CtrlC_handler(true);
     while (!checkInterrupt(InterruptState::FinishNow)) {
         const std::string start_stamp = Acquisition::utc_now();
-        while (!ended && have < bytes.size()) {
-            const size_t got = std::fread(bytes.data() + have, 1, bytes.size() - have, file);
-            if (got == 0) ended = true;
-            have += got;
-        }
-        const int64_t done = stats ? data.accumulate_series_stats(bytes.data(), have, L, per_piece, rows)
-                                   : data.accumulate_series(bytes.data(), have, L, per_piece, rows);
+        const size_t have = in.fill();
+        const int64_t done = stats ? data.accumulate_series_stats(in.data(), have, L, in.per_piece(), rows)
+                                   : data.accumulate_series(in.data(), have, L, in.per_piece(), rows);
         if (done == 0) break;
         const std::string end_stamp = Acquisition::utc_now();
         for (int64_t k = 0; k < done; ++k) {
@@ -406,10 +390,7 @@ int run_series(const Options& options, AuxData& aux, int actual_samplerate, int6
             std::cout << std::endl;          // (the blank line that closes a pass of -c)
         }
         written += done;
-        const size_t used = static_cast<size_t>(done * L * pitch);      // the next spectrum starts here
-        std::memmove(bytes.data(), bytes.data() + used, have - used);
-        have -= used;
-        if (ended && static_cast<int64_t>(have) < options.frame_span(L)) break;
+        if (!in.consume(done)) break;
     }
     if (chatty(options)) {
         std::cerr << "Spectra written: " << written << ", " << L << " frames each ("
@@ -428,35 +409,18 @@ int run_series(const Options& options, AuxData& aux, int actual_samplerate, int6
 int run_excise(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
 {
     Datastore data(options, aux.window_values);
-    std::FILE* file = options.input_file == "-" ? stdin : std::fopen(options.input_file.c_str(), "rb");
-    if (!file) throw RPFexception("Could not open " + options.input_file + ".", ReturnValue::InvalidInput);
-    struct CloseOnExit {
-        std::FILE* f;
-        ~CloseOnExit() { if (f != stdin) std::fclose(f); }
-    } close_file{file};
     const int64_t L = options.excise_frames;
+    PieceReader in(options.input_file, options.sample_bytes() * options.N, options.sample_bytes() * options.step(), L);
     double sk_lo = 0, sk_hi = 0;
     sk_limits(L, options.excise_sigma, sk_lo, sk_hi);
-    const int64_t b = options.sample_bytes();
-    const int64_t frame = b * options.N, pitch = b * options.step();
-    const int64_t piece_budget = static_cast<int64_t>(64) << 20;
-    const int64_t fit = piece_budget < frame ? 0 : ((piece_budget - frame) / pitch + 1) / L;
-    const int64_t per_piece = std::max<int64_t>(1, fit);
-    std::vector<uint8_t> bytes(static_cast<size_t>(options.frame_span(per_piece * L)));
     const size_t N = static_cast<size_t>(options.N);
     std::vector<double> piece, clean(N, 0.0), kept(N, 0.0), total(N, 0.0);
-    size_t have = 0;
     int64_t K = 0;
-    bool ended = false;
     set_CtrlC_handler(true);
     const std::string start_stamp = Acquisition::utc_now();
     while (!checkInterrupt(InterruptState::FinishNow)) {
-        while (!ended && have < bytes.size()) {
-            const size_t got = std::fread(bytes.data() + have, 1, bytes.size() - have, file);
-            if (got == 0) ended = true;
-            have += got;
-        }
-        const int64_t done = data.accumulate_excised(bytes.data(), have, L, per_piece, sk_lo, sk_hi, piece);
+        const size_t have = in.fill();
+        const int64_t done = data.accumulate_excised(in.data(), have, L, in.per_piece(), sk_lo, sk_hi, piece);
         if (done == 0) break;
         for (size_t i = 0; i < N; ++i) {
             clean[i] += piece[i];
@@ -464,10 +428,7 @@ int run_excise(const Options& options, AuxData& aux, int actual_samplerate, int6
             total[i] += piece[2 * N + i];
         }
         K += done;
-        const size_t used = static_cast<size_t>(done * L * pitch);      // the next integration starts here
-        std::memmove(bytes.data(), bytes.data() + used, have - used);
-        have -= used;
-        if (ended && static_cast<int64_t>(have) < options.frame_span(L)) break;
+        if (!in.consume(done)) break;
     }
     if (K == 0)
         throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
@@ -492,45 +453,26 @@ int run_excise(const Options& options, AuxData& aux, int actual_samplerate, int6
 int run_quantile(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
 {
     Datastore data(options, aux.window_values);
-    std::FILE* file = options.input_file == "-" ? stdin : std::fopen(options.input_file.c_str(), "rb");
-    if (!file) throw RPFexception("Could not open " + options.input_file + ".", ReturnValue::InvalidInput);
-    struct CloseOnExit {
-        std::FILE* f;
-        ~CloseOnExit() { if (f != stdin) std::fclose(f); }
-    } close_file{file};
     const int64_t L = options.quantile_frames;
-    const int64_t b = options.sample_bytes();
-    const int64_t frame = b * options.N, pitch = b * options.step();
-    const int64_t piece_budget = static_cast<int64_t>(64) << 20;
-    const int64_t fit = piece_budget < frame ? 0 : ((piece_budget - frame) / pitch + 1) / L;
-    const int64_t per_piece = std::max<int64_t>(1, fit);
-    std::vector<uint8_t> bytes(static_cast<size_t>(options.frame_span(per_piece * L)));
-    size_t have = 0;
+    PieceReader in(options.input_file, options.sample_bytes() * options.N, options.sample_bytes() * options.step(), L);
     int64_t K = 0;
-    bool ended = false, one_launch = true;
+    bool one_launch = true;
     set_CtrlC_handler(true);
     const std::string start_stamp = Acquisition::utc_now();
     data.quantile_reset();
     while (!checkInterrupt(InterruptState::FinishNow)) {
-        while (!ended && have < bytes.size()) {
-            const size_t got = std::fread(bytes.data() + have, 1, bytes.size() - have, file);
-            if (got == 0) ended = true;
-            have += got;
-        }
-        const int64_t coming = std::min(per_piece, options.frames_in(static_cast<int64_t>(have)) / L);
+        const size_t have = in.fill();
+        const int64_t coming = std::min(in.per_piece(), options.frames_in(static_cast<int64_t>(have)) / L);
         if (K + coming > data.quantile_max_rows())
             throw RPFexception("Option --quantile: the input holds more than " + std::to_string(data.quantile_max_rows()) +
                                " integrations of " + std::to_string(L) + " frames, which is what the device keeps of " +
                                std::to_string(options.N) + " bins (1 GiB of rows): raise <frames>. Exiting.",
                                ReturnValue::InvalidArgument);
-        const int64_t done = data.quantile_append(bytes.data(), have, L, per_piece);
+        const int64_t done = data.quantile_append(in.data(), have, L, in.per_piece());
         if (done == 0) break;
         one_launch = one_launch && data.series_launches() == 1;
         K += done;
-        const size_t used = static_cast<size_t>(done * L * pitch);      // the next integration starts here
-        std::memmove(bytes.data(), bytes.data() + used, have - used);
-        have -= used;
-        if (ended && static_cast<int64_t>(have) < options.frame_span(L)) break;
+        if (!in.consume(done)) break;
     }
     if (K == 0)
         throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
