@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "bluestein_tables.h"
+#include "engine_family.h"
 #include "rpf_kernels.h"
 #include "series_pieces.h"
 
@@ -78,7 +79,6 @@ struct rpf_engine {
     int n_buffers = 0;
     size_t buffer_capacity = 0;
     int device = 0;
-    uint32_t flags = 0;
     bool use_dma = true;
     int variant = 0;
     bool stats = false;           // RPF_FLAG_BIN_STATS: S2 and PK kept beside the power on every path
@@ -113,8 +113,8 @@ struct rpf_engine {
     bool recycle_stop = false;
     std::string recycler_error;
     rpf::cf* d_twiddles = nullptr;
-    bool fourstep = false;                // N handled by rpf_fourstep.hip
-    bool fused = false;                   // ... by the fused persistent kernel (Y stays in the XCDs' L2)
+    rpf::Family family = rpf::Family::K1; // the kernel family that serves N (engine_family.h), chosen once at creation
+    bool fused = false;                   // four-step: by the fused persistent kernel (Y stays in the XCDs' L2) -- until retire_fused
     void* d_fused_ctl = nullptr;          // its team counters / abort flag
     rpf::cf* d_fused_scratch = nullptr;   // its Y (two rounds per XCD); kept apart from d_scratch, the two-kernel path's
     // What became of the fused launches, written by their verdict kernels into pinned host memory:
@@ -126,13 +126,8 @@ struct rpf_engine {
     unsigned fused_aborts_seen = 0;       // h_fused_words[3] when the host last looked
     int64_t fused_recovered = 0;          // launches re-run on K2a/K2b after giving up (queue path)
     int fused_fault_mode = 0, fused_fault_skip = 0, fused_fault_count = 0;   // rpf_debug_fused_fault
-    bool bluestein = false;               // N handled by the Bluestein kernel (chirp tables below)
-    bool bigblu = false;                  // N handled by the large (four-step) Bluestein path
-    bool mixed = false;                   // N handled by the LDS mixed-radix kernel (rpf_mixed.hip)
-    bool generic = false;                 // N handled by the catch-all Stockham path (rpf_generic.hip)
-    int gen_h = 0;                        // its two-level twiddle split (d_tw_sub = T0, d_tw_sub2 = T1)
-    int blu_M = 0;                        // bigblu: convolution length (partial spectra have M entries)
-    rpf::cf* d_chirp = nullptr;           // g[n], N entries
+    int gen_h = 0;                        // catch-all path: its two-level twiddle split (d_tw_sub = T0, d_tw_sub2 = T1)
+    rpf::cf* d_chirp = nullptr;           // Bluestein families: g[n], N entries
     rpf::cf* d_bhat = nullptr;            // frequency-domain chirp, M entries
     rpf::cf* d_tw_sub = nullptr;          // four-step: twiddles of the N1-point column transforms
     rpf::cf* d_tw_sub2 = nullptr;         // four-step: twiddles of the N2-point row transforms
@@ -144,6 +139,7 @@ struct rpf_engine {
     int64_t gather_frames = 0;            // ... frames it holds (kGatherBytes / 2N, at least one)
     float* d_window = nullptr;
     double* d_partial = nullptr;
+    size_t partial_stride = 0;            // elements from one partial spectrum to the next (0: N; large Bluestein: its M)
     double* d_pwr = nullptr;              // N doubles; a stats engine's: 3 N, the planes S1 (= pwr), S2, PK
     size_t head_room = 0;                 // >= 2N, multiple of 256
     size_t coalesce = 1;                  // host buffers one staging slot holds (= one transform launch)
@@ -226,10 +222,7 @@ size_t frame_span(const rpf_engine* e, int64_t frames) { return frame_bytes(e).s
 
 bool overlapped(const rpf_engine* e) { return e->step != e->N; }
 
-bool is_k1(const rpf_engine* e)
-{
-    return !(e->fourstep || e->mixed || e->bluestein || e->bigblu || e->generic);
-}
+bool is_k1(const rpf_engine* e) { return e->family == rpf::Family::K1; }
 
 // Makes the engine's device current for the scope of an entry point and puts the
 // caller's back afterwards: in a multi-GPU process (one engine per device, or a
@@ -403,35 +396,14 @@ void note_device_path_aborts(rpf_engine* e)
     }
 }
 
-// Enqueue K1 (or the four-step pair K2a/K2b) for `nframes` frames starting at
-// d_frames; leaves *nslots partial spectra in e->d_partial.  K1 reads the frames at the engine's frame step; every
-// other family reads them side by side (launch_frames gathers overlapped frames for them first).
-int launch_transform(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hipStream_t stream,
-                     int* nslots)
+// ---- one transform launch per family: `nframes` frames side by side from d_frames -> *nslots partial spectra in
+// e->d_partial (launch_transform) ----
+
+// The fused persistent kernel while the engine has it, else the pair K2a/K2b.
+int transform_fourstep(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hipStream_t stream, int* nslots)
 {
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(d_frames);
-    e->last_was_fused = false;
-    if (e->fourstep && e->fused) {
-        const bool dma = e->use_dma && (addr % 4) == 0;
-        int fault = 0;                       // rpf_debug_fused_fault: `count` launches after `skip` untouched ones
-        if (e->fused_fault_count != 0) {
-            if (e->fused_fault_skip > 0) {
-                --e->fused_fault_skip;
-            } else {
-                fault = e->fused_fault_mode;
-                if (e->fused_fault_count > 0) --e->fused_fault_count;
-            }
-        }
-        HIP_TRY(e, rpf::launch_fourstep_fused(e->N, e->has_window, dma, d_frames, nframes, e->d_tw_sub, e->d_tw_sub2,
-                                              e->d_twiddles, e->d_window, e->d_fused_scratch, e->d_partial,
-                                              e->d_fused_ctl, stream, fault));
-        e->last = e->plan;
-        e->last_was_fused = true;
-        *nslots = rpf::fourstep_fused_slots(e->N);
-        return RPF_OK;
-    }
-    if (e->fourstep) {
-        const bool dma = e->use_dma && (addr % 4) == 0;
+    const bool dma = e->use_dma && (reinterpret_cast<uintptr_t>(d_frames) % 4) == 0;
+    if (!e->fused) {
         if (int rc = ensure_scratch(e, nframes, stream)) return rc;
         HIP_TRY(e, rpf::launch_fourstep(e->N, e->has_window, dma, d_frames, nframes, e->d_tw_sub,
                                         e->d_tw_sub2, e->d_twiddles, e->d_window, e->d_scratch, e->scratch_bytes,
@@ -440,47 +412,124 @@ int launch_transform(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hi
         *nslots = rpf::fourstep_partial_slots(e->N);
         return RPF_OK;
     }
-    if (e->generic) {
-        HIP_TRY(e, rpf::launch_generic(e->N, d_frames, nframes, e->d_window, e->d_chirp, e->d_bhat, e->d_tw_sub,
-                                       e->d_tw_sub2, e->gen_h, e->d_scratch, e->d_partial, /*accumulate=*/false, stream,
-                                       e->format, e->stats));
-        e->last = e->plan;
-        *nslots = 1;
-        return RPF_OK;
+    int fault = 0;                       // rpf_debug_fused_fault: `count` launches after `skip` untouched ones
+    if (e->fused_fault_count != 0) {
+        if (e->fused_fault_skip > 0) {
+            --e->fused_fault_skip;
+        } else {
+            fault = e->fused_fault_mode;
+            if (e->fused_fault_count > 0) --e->fused_fault_count;
+        }
     }
-    if (e->bigblu) {
-        const bool dma = e->use_dma && (addr % 4) == 0;
-        if (int rc = ensure_scratch(e, nframes, stream)) return rc;
-        HIP_TRY(e, rpf::launch_bigblu(e->N, dma, d_frames, nframes, e->d_tw_sub, e->d_tw_sub2, e->d_twiddles,
-                                      e->d_step2, e->d_chirp, e->d_bhat, e->d_scratch, e->scratch_bytes, e->d_partial,
-                                      e->plan.grid, stream));
-        e->last = e->plan;
-        *nslots = rpf::bigblu_partial_slots(e->N);
-        return RPF_OK;
-    }
-    if (e->mixed) {       // (trims the grid to the frames itself: the split form needs a multiple of its factor)
-        HIP_TRY(e, rpf::launch_mixed(e->N, e->variant, d_frames, nframes, e->d_twiddles, e->d_window, e->d_partial,
-                                     e->plan.grid, stream, &e->last));
-        *nslots = e->last.slots ? e->last.slots : e->last.grid;
-        return RPF_OK;
-    }
-    if (e->bluestein) {
-        const int64_t wanted = (nframes + e->plan.fpw - 1) / e->plan.fpw;
-        const int grid = static_cast<int>(std::min<int64_t>(e->plan.grid, wanted));
-        HIP_TRY(e, rpf::launch_bluestein(e->N, d_frames, nframes, e->d_twiddles, e->d_chirp, e->d_bhat,
-                                         e->d_partial, grid, stream, &e->last));
-        *nslots = grid;
-        return RPF_OK;
-    }
-    // K1, one acquisition per launch
-    // (RPF_TUNE_SCAN_KERNEL, tuning build: the scan kernel on a scan of one hop, A/B)
-    rpf::SlotRanges slots;
-    (void)addr;
-    return launch_fused_hops(e, &d_frames, &nframes, 1, stream, &slots, nslots);
+    HIP_TRY(e, rpf::launch_fourstep_fused(e->N, e->has_window, dma, d_frames, nframes, e->d_tw_sub, e->d_tw_sub2,
+                                          e->d_twiddles, e->d_window, e->d_fused_scratch, e->d_partial,
+                                          e->d_fused_ctl, stream, fault));
+    e->last = e->plan;
+    e->last_was_fused = true;
+    *nslots = rpf::fourstep_fused_slots(e->N);
+    return RPF_OK;
 }
 
+int transform_generic(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hipStream_t stream, int* nslots)
+{
+    HIP_TRY(e, rpf::launch_generic(e->N, d_frames, nframes, e->d_window, e->d_chirp, e->d_bhat, e->d_tw_sub,
+                                   e->d_tw_sub2, e->gen_h, e->d_scratch, e->d_partial, /*accumulate=*/false, stream,
+                                   e->format, e->stats));
+    e->last = e->plan;
+    *nslots = 1;
+    return RPF_OK;
+}
+
+int transform_bigblu(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hipStream_t stream, int* nslots)
+{
+    const bool dma = e->use_dma && (reinterpret_cast<uintptr_t>(d_frames) % 4) == 0;
+    if (int rc = ensure_scratch(e, nframes, stream)) return rc;
+    HIP_TRY(e, rpf::launch_bigblu(e->N, dma, d_frames, nframes, e->d_tw_sub, e->d_tw_sub2, e->d_twiddles,
+                                  e->d_step2, e->d_chirp, e->d_bhat, e->d_scratch, e->scratch_bytes, e->d_partial,
+                                  e->plan.grid, stream));
+    e->last = e->plan;
+    *nslots = rpf::bigblu_partial_slots(e->N);
+    return RPF_OK;
+}
+
+// (trims the grid to the frames itself: the split form needs a multiple of its factor)
+int transform_mixed(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hipStream_t stream, int* nslots)
+{
+    HIP_TRY(e, rpf::launch_mixed(e->N, e->variant, d_frames, nframes, e->d_twiddles, e->d_window, e->d_partial,
+                                 e->plan.grid, stream, &e->last));
+    *nslots = e->last.slots ? e->last.slots : e->last.grid;
+    return RPF_OK;
+}
+
+int transform_bluestein(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hipStream_t stream, int* nslots)
+{
+    const int64_t wanted = (nframes + e->plan.fpw - 1) / e->plan.fpw;
+    const int grid = static_cast<int>(std::min<int64_t>(e->plan.grid, wanted));
+    HIP_TRY(e, rpf::launch_bluestein(e->N, d_frames, nframes, e->d_twiddles, e->d_chirp, e->d_bhat,
+                                     e->d_partial, grid, stream, &e->last));
+    *nslots = grid;
+    return RPF_OK;
+}
+
+// Enqueue the engine's transform for `nframes` frames starting at
+// d_frames; leaves *nslots partial spectra in e->d_partial.  K1 reads the frames at the engine's frame step; every
+// other family reads them side by side (launch_frames gathers overlapped frames for them first).
+int launch_transform(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hipStream_t stream,
+                     int* nslots)
+{
+    e->last_was_fused = false;
+    switch (e->family) {
+    case rpf::Family::K1: {     // one acquisition per launch (RPF_TUNE_SCAN_KERNEL, tuning build: the scan kernel on one hop, A/B)
+        rpf::SlotRanges slots;
+        return launch_fused_hops(e, &d_frames, &nframes, 1, stream, &slots, nslots);
+    }
+    case rpf::Family::Mixed: return transform_mixed(e, d_frames, nframes, stream, nslots);
+    case rpf::Family::FourStep: return transform_fourstep(e, d_frames, nframes, stream, nslots);
+    case rpf::Family::Bluestein: return transform_bluestein(e, d_frames, nframes, stream, nslots);
+    case rpf::Family::BigBluestein: return transform_bigblu(e, d_frames, nframes, stream, nslots);
+    case rpf::Family::Generic: return transform_generic(e, d_frames, nframes, stream, nslots);
+    case rpf::Family::None: break;        // (a PFB engine: launch_pfb runs the inner engine's)
+    }
+    return fail(e, RPF_ERR_INVALID_ARGUMENT, "a PFB engine has no transform of its own");
+}
+
+// K3 over the e->last_slots partial spectra the last transform left (not a hop launch's, not a stats engine's).
+// slot_verdict: launch_frames' -- null: a fused launch that gave up leaves d_out NaN-filled and is counted in
+// h_fused_words[3]; else K3 leaves d_out alone and the word becomes 1.
+int reduce_last(rpf_engine* e, double* d_out, bool accumulate, hipStream_t stream, unsigned* slot_verdict)
+{
+    const bool fused = e->last_was_fused;
+    HIP_TRY(e, rpf::launch_reduce(e->d_partial, e->last_slots, e->N, d_out, accumulate, stream,
+                                  e->plan.partial_f32, e->partial_stride,
+                                  fused && slot_verdict ? rpf::fourstep_fused_abort_word(e->d_fused_ctl) : nullptr));
+    // a fused launch whose teams did not assemble must not leave something that looks like a spectrum
+    if (fused)
+        HIP_TRY(e, rpf::launch_fused_verdict(e->d_fused_ctl, slot_verdict ? nullptr : d_out, e->N,
+                                             slot_verdict ? slot_verdict : e->d_fused_words + 3, e->d_fused_words + 4, stream));
+    return RPF_OK;
+}
+
+// launch_frames for frames the transform reads where they lie (K1 at any frame step; the other families at step N)
 int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out, bool accumulate,
-                        hipStream_t stream, unsigned* slot_verdict, bool want_stats);
+                        hipStream_t stream, unsigned* slot_verdict, bool want_stats)
+{
+    if (e->fused && !slot_verdict) note_device_path_aborts(e);
+    int nslots = 0;
+    int rc = launch_transform(e, d_frames, nframes, stream, &nslots);
+    if (rc != RPF_OK) return rc;
+    e->last_slots = nslots;
+    e->last_hops = 0;
+    if (e->stats) {
+        // three planes per slot (K1: one slot per workgroup; the catch-all path: one slot)
+        if (want_stats)
+            HIP_TRY(e, rpf::launch_reduce_stats(e->d_partial, nslots, e->N, d_out, accumulate, stream));
+        else
+            HIP_TRY(e, rpf::launch_reduce(e->d_partial, nslots, e->N, d_out, accumulate, stream, false,
+                                          static_cast<size_t>(rpf::kStatsPlanes) * e->N));
+        return RPF_OK;
+    }
+    return reduce_last(e, d_out, accumulate, stream, slot_verdict);
+}
 
 // Overlapped frames on a family that reads frames side by side: chunks of at most kGatherBytes of frames are gathered
 // into e->d_gather (rpf_frames.hip) and the size's unchanged transform + reduce runs over each, the chunks after the
@@ -491,9 +540,7 @@ int launch_gathered(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, dou
     const size_t frame = e->sample_bytes * static_cast<size_t>(e->N);
     if (!e->d_gather) {
         e->gather_frames = std::max<int64_t>(1, static_cast<int64_t>(rpf::kGatherBytes / frame));
-        void* p = nullptr;
-        HIP_TRY(e, hipMalloc(&p, static_cast<size_t>(e->gather_frames) * frame));
-        e->d_gather = static_cast<uint8_t*>(p);
+        HIP_TRY(e, hipMalloc(&e->d_gather, static_cast<size_t>(e->gather_frames) * frame));
     }
     const long pitch = static_cast<long>(e->sample_bytes) * e->step;
     for (int64_t f0 = 0; f0 < nframes; f0 += e->gather_frames) {
@@ -514,9 +561,7 @@ int launch_pfb(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* 
     const size_t zframe = sizeof(float) * 2 * static_cast<size_t>(e->N);
     if (!e->d_pfb_z) {
         e->pfb_chunk_frames = std::max<int64_t>(1, static_cast<int64_t>(rpf::kGatherBytes / zframe));
-        void* p = nullptr;
-        HIP_TRY(e, hipMalloc(&p, static_cast<size_t>(e->pfb_chunk_frames) * zframe));
-        e->d_pfb_z = static_cast<float*>(p);
+        HIP_TRY(e, hipMalloc(&e->d_pfb_z, static_cast<size_t>(e->pfb_chunk_frames) * zframe));
     }
     const size_t row = e->sample_bytes * static_cast<size_t>(e->N);
     for (int64_t f0 = 0; f0 < nframes; f0 += e->pfb_chunk_frames) {
@@ -543,36 +588,6 @@ int launch_frames(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, doubl
     if (e->taps) return launch_pfb(e, d_frames, nframes, d_out, accumulate, stream);
     if (overlapped(e) && !is_k1(e)) return launch_gathered(e, d_frames, nframes, d_out, accumulate, stream, want_stats);
     return launch_side_by_side(e, d_frames, nframes, d_out, accumulate, stream, slot_verdict, want_stats);
-}
-
-// launch_frames for frames the transform reads where they lie (K1 at any frame step; the other families at step N)
-int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, double* d_out, bool accumulate,
-                        hipStream_t stream, unsigned* slot_verdict, bool want_stats)
-{
-    if (e->fused && !slot_verdict) note_device_path_aborts(e);
-    int nslots = 0;
-    int rc = launch_transform(e, d_frames, nframes, stream, &nslots);
-    if (rc != RPF_OK) return rc;
-    e->last_slots = nslots;
-    e->last_hops = 0;
-    const bool fused = e->last_was_fused;
-    if (e->stats) {
-        // three planes per slot (K1: one slot per workgroup; the catch-all path: one slot)
-        if (want_stats)
-            HIP_TRY(e, rpf::launch_reduce_stats(e->d_partial, nslots, e->N, d_out, accumulate, stream));
-        else
-            HIP_TRY(e, rpf::launch_reduce(e->d_partial, nslots, e->N, d_out, accumulate, stream, false,
-                                          static_cast<size_t>(rpf::kStatsPlanes) * e->N));
-        return RPF_OK;
-    }
-    HIP_TRY(e, rpf::launch_reduce(e->d_partial, nslots, e->N, d_out, accumulate, stream,
-                                  e->plan.partial_f32, e->bigblu ? static_cast<size_t>(e->blu_M) : 0,
-                                  fused && slot_verdict ? rpf::fourstep_fused_abort_word(e->d_fused_ctl) : nullptr));
-    // a fused launch whose teams did not assemble must not leave something that looks like a spectrum
-    if (fused)
-        HIP_TRY(e, rpf::launch_fused_verdict(e->d_fused_ctl, slot_verdict ? nullptr : d_out, e->N,
-                                             slot_verdict ? slot_verdict : e->d_fused_words + 3, e->d_fused_words + 4, stream));
-    return RPF_OK;
 }
 
 // Hands the pool's buffers back to the producer, each as soon as ITS copy has landed (datastore.cxx:91-94 returns a
@@ -869,35 +884,19 @@ void worker_main(rpf_engine* e)
 
 void release_device(rpf_engine* e)
 {
-    if (e->d_twiddles) (void)hipFree(e->d_twiddles);
-    if (e->d_tw_sub) (void)hipFree(e->d_tw_sub);
-    if (e->d_tw_sub2) (void)hipFree(e->d_tw_sub2);
-    if (e->d_scratch) (void)hipFree(e->d_scratch);
-    if (e->d_fused_ctl) (void)hipFree(e->d_fused_ctl);
-    if (e->d_fused_scratch) (void)hipFree(e->d_fused_scratch);
+    // every device block the engine owns (hipFree of a null pointer does nothing)
+    void* const blocks[] = {e->d_twiddles, e->d_tw_sub, e->d_tw_sub2, e->d_scratch, e->d_fused_ctl, e->d_fused_scratch,
+                            e->d_step2, e->d_gather, e->d_chirp, e->d_bhat, e->d_window, e->d_partial,
+                            e->d_series_partial, e->d_series_in, e->d_series_out, e->d_excise_state, e->d_excise_mask,
+                            e->d_quantile_rows, e->d_quantile_work, e->d_quantile_out, e->d_pfb_coeffs, e->d_pfb_z,
+                            e->d_pwr};
+    for (void* p : blocks) (void)hipFree(p);
     if (e->h_fused_words) (void)hipHostFree(e->h_fused_words);
-    if (e->d_step2) (void)hipFree(e->d_step2);
-    if (e->d_gather) (void)hipFree(e->d_gather);
-    if (e->d_chirp) (void)hipFree(e->d_chirp);
-    if (e->d_bhat) (void)hipFree(e->d_bhat);
-    if (e->d_window) (void)hipFree(e->d_window);
-    if (e->d_partial) (void)hipFree(e->d_partial);
-    if (e->d_series_partial) (void)hipFree(e->d_series_partial);
-    if (e->d_series_in) (void)hipFree(e->d_series_in);
-    if (e->d_series_out) (void)hipFree(e->d_series_out);
-    if (e->d_excise_state) (void)hipFree(e->d_excise_state);
-    if (e->d_excise_mask) (void)hipFree(e->d_excise_mask);
-    if (e->d_quantile_rows) (void)hipFree(e->d_quantile_rows);
-    if (e->d_quantile_work) (void)hipFree(e->d_quantile_work);
-    if (e->d_quantile_out) (void)hipFree(e->d_quantile_out);
-    if (e->d_pfb_coeffs) (void)hipFree(e->d_pfb_coeffs);
-    if (e->d_pfb_z) (void)hipFree(e->d_pfb_z);
     if (e->inner) {
         release_device(e->inner);
         delete e->inner;
         e->inner = nullptr;
     }
-    if (e->d_pwr) (void)hipFree(e->d_pwr);
     for (auto& s : e->staging) {
         if (s.base) (void)hipFree(s.base);
         if (s.kernel_done) (void)hipEventDestroy(s.kernel_done);
@@ -938,307 +937,304 @@ struct PfbSpec {
     const float* coeffs;      // taps x N
 };
 
-// rpf_engine_create (pfb null) and rpf_engine_create_pfb.  inner_of_pfb: the transform engine a PFB engine owns -- it is
-// never fed through its queues, so its staging slots hold one (minimal) buffer each.
-int create_engine(const rpf_config* cfg, const PfbSpec* pfb, bool inner_of_pfb, rpf_engine** out)
+// What check_config reads out of a configuration it accepts.
+struct Checked {
+    int step, format, variant;
+    size_t sample_bytes;
+    bool stats;
+    rpf::Family family;
+};
+
+// Every argument check of rpf_engine_create (pfb null) and rpf_engine_create_pfb, all of them before any device is
+// touched (include/rpf_engine.h) and in the order callers see them answered.
+int check_config(const rpf_config* cfg, const PfbSpec* pfb, rpf_engine** out, Checked* c)
 {
-    if (!out) return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "rpf_engine_create: out is NULL");
+    auto bad = [](const std::string& msg) { return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, msg); };
+    if (!out) return bad("rpf_engine_create: out is NULL");
     *out = nullptr;
     // (the config of ABI 2's first form ends at `flags`: frame step N)
     if (!cfg || (cfg->struct_size != sizeof(rpf_config) && cfg->struct_size != offsetof(rpf_config, frame_step)))
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "rpf_engine_create: bad rpf_config size");
-    if (cfg->N < 2 || (cfg->N % 2) != 0)
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                    "Number of bins must be a positive even number.");
+        return bad("rpf_engine_create: bad rpf_config size");
+    if (cfg->N < 2 || (cfg->N % 2) != 0) return bad("Number of bins must be a positive even number.");
+    const std::string bins = std::to_string(cfg->N);
     const int32_t frame_step = cfg->struct_size == sizeof(rpf_config) ? cfg->frame_step : 0;
     if (frame_step < 0 || frame_step > cfg->N)
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                    "Frame step must be between 1 and the number of bins (" + std::to_string(cfg->N) + "), or 0 for " +
-                        std::to_string(cfg->N) + "; got " + std::to_string(frame_step) + ".");
-    const int step = frame_step == 0 ? cfg->N : frame_step;
-    const int format = static_cast<int>((cfg->flags >> 16) & 0xfu);
-    if (format != RPF_FORMAT_CU8 && format != RPF_FORMAT_CS8 && format != RPF_FORMAT_CS16 && format != RPF_FORMAT_CF32)
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                    "Sample format must be 0 (cu8), 1 (cs8), 2 (cs16) or 4 (cf32); got " + std::to_string(format) + ".");
-    const size_t sample_bytes = static_cast<size_t>(rpf::sample_bytes_of(format));
-    const bool stats = (cfg->flags & RPF_FLAG_BIN_STATS) != 0;
-    if (stats && (cfg->flags & RPF_FLAG_FOURSTEP_FUSED))
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                    "RPF_FLAG_BIN_STATS does not combine with RPF_FLAG_FOURSTEP_FUSED: the statistics run on K1 or on the catch-all path.");
-    if (stats && ((cfg->flags >> 8) & 0xffu) != 0)
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                    "RPF_FLAG_BIN_STATS does not combine with a kernel variant other than 0.");
+        return bad("Frame step must be between 1 and the number of bins (" + bins + "), or 0 for " + bins + "; got " +
+                   std::to_string(frame_step) + ".");
+    c->step = frame_step == 0 ? cfg->N : frame_step;
+    c->format = static_cast<int>((cfg->flags >> 16) & 0xfu);
+    if (c->format != RPF_FORMAT_CU8 && c->format != RPF_FORMAT_CS8 && c->format != RPF_FORMAT_CS16 && c->format != RPF_FORMAT_CF32)
+        return bad("Sample format must be 0 (cu8), 1 (cs8), 2 (cs16) or 4 (cf32); got " + std::to_string(c->format) + ".");
+    c->sample_bytes = static_cast<size_t>(rpf::sample_bytes_of(c->format));
+    c->stats = (cfg->flags & RPF_FLAG_BIN_STATS) != 0;
+    c->variant = static_cast<int>((cfg->flags >> 8) & 0xffu);
+    const bool ask_fused = (cfg->flags & RPF_FLAG_FOURSTEP_FUSED) != 0;
+    if (c->stats && ask_fused)
+        return bad("RPF_FLAG_BIN_STATS does not combine with RPF_FLAG_FOURSTEP_FUSED: the statistics run on K1 or on the catch-all path.");
+    if (c->stats && c->variant != 0) return bad("RPF_FLAG_BIN_STATS does not combine with a kernel variant other than 0.");
     if (pfb) {
-        // (include/rpf_engine.h, rpf_engine_create_pfb: all of it before any device is touched)
         if (pfb->taps < 1 || pfb->taps > rpf::kPfbMaxTaps)
-            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                        "Number of PFB taps must be between 1 and " + std::to_string(rpf::kPfbMaxTaps) + "; got " +
-                            std::to_string(pfb->taps) + ".");
+            return bad("Number of PFB taps must be between 1 and " + std::to_string(rpf::kPfbMaxTaps) + "; got " +
+                       std::to_string(pfb->taps) + ".");
         if (static_cast<int64_t>(pfb->taps) * cfg->N > (static_cast<int64_t>(1) << 26))
-            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                        "PFB taps x bins must not exceed 67108864; got " + std::to_string(pfb->taps) + " x " +
-                            std::to_string(cfg->N) + ".");
-        if (!pfb->coeffs) return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "rpf_engine_create_pfb: coeffs is NULL");
-        if (cfg->window)
-            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                        "A PFB engine takes no window: the PFB coefficients are the window.");
-        if (step != cfg->N)
-            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                        "PFB frames advance by the number of bins: frame_step must be 0 or " + std::to_string(cfg->N) + "; got " +
-                            std::to_string(frame_step) + ".");
-        if (stats)
-            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "PFB does not combine with RPF_FLAG_BIN_STATS.");
-        if (cfg->flags & RPF_FLAG_FOURSTEP_FUSED)
-            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                        "PFB does not combine with RPF_FLAG_FOURSTEP_FUSED: the folded frames run on K1 or on the catch-all path.");
-        if (((cfg->flags >> 8) & 0xffu) != 0)
-            return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "PFB does not combine with a kernel variant other than 0.");
+            return bad("PFB taps x bins must not exceed 67108864; got " + std::to_string(pfb->taps) + " x " + bins + ".");
+        if (!pfb->coeffs) return bad("rpf_engine_create_pfb: coeffs is NULL");
+        if (cfg->window) return bad("A PFB engine takes no window: the PFB coefficients are the window.");
+        if (c->step != cfg->N)
+            return bad("PFB frames advance by the number of bins: frame_step must be 0 or " + bins + "; got " +
+                       std::to_string(frame_step) + ".");
+        if (c->stats) return bad("PFB does not combine with RPF_FLAG_BIN_STATS.");
+        if (ask_fused)
+            return bad("PFB does not combine with RPF_FLAG_FOURSTEP_FUSED: the folded frames run on K1 or on the catch-all path.");
+        if (c->variant != 0) return bad("PFB does not combine with a kernel variant other than 0.");
     }
-    const bool native_k1 = rpf::kernel_supported(cfg->N, 0);
-    // The catch-all path is the one that reads every format at every N: it takes the engines that ask for it and the
-    // signed formats on every size K1 does not serve, whatever family that size runs on with cu8.
-    // ... and so do the statistics: a stats engine at any size K1 does not serve runs there.
-    // (cf32 with statistics included: K1 has every size x window x staging form of it, rpf_kernels_stats_cf32.hip.)
-    const bool catch_all = (cfg->flags & RPF_FLAG_CATCH_ALL) != 0 || ((format != RPF_FORMAT_CU8 || stats) && !native_k1);
-    const int variant = static_cast<int>((cfg->flags >> 8) & 0xffu);
-    // (asking for the fused four-step kernel is asking for the four-step path)
-    // 32768 is served twice, by the split form 2 x 16384 and by the four-step kernels.  Plain runs are faster on the
-    // former (0.37 against 0.22 Tsample/s); WINDOWED runs are not: the 16384-point plan has no registers left for the
-    // window values next to its two-deep section pipeline (0.175, it was 0.27 before round 3's section sums), the
-    // four-step kernels multiply them in as they unpack (0.21 - 0.22).  profiles/r04_sizes.txt.
-    const bool windowed_32768 = cfg->N == 32768 && cfg->window != nullptr && variant == 0;
-    const bool mixed = !catch_all && rpf::mixed_supported(cfg->N, variant) && !windowed_32768 &&
-                       !(cfg->flags & (RPF_FLAG_NO_MIXED_RADIX | RPF_FLAG_FOURSTEP_FUSED));
-    const bool fourstep = !catch_all && !mixed && rpf::fourstep_supported(cfg->N) && variant == 0;
-    const bool bluestein = !catch_all && !mixed && rpf::bluestein_supported(cfg->N) && variant == 0;
-    const bool bigblu = !catch_all && !mixed && rpf::bigblu_supported(cfg->N) && variant == 0;
-    const bool tuned = !catch_all && (fourstep || mixed || bluestein || bigblu ||
-                                      (rpf::kernel_supported(cfg->N, variant) && (format == RPF_FORMAT_CU8 || variant == 0)));
-    const bool generic = !tuned && variant == 0 && rpf::generic_supported(cfg->N);
+    // the kernel family (engine_family.h has the rule), from what this build has at N
+    const int N = cfg->N, v = c->variant;
+    const rpf::FamilyQuery q{N, v, c->format == RPF_FORMAT_CU8, c->stats, cfg->window != nullptr,
+                             (cfg->flags & RPF_FLAG_CATCH_ALL) != 0, (cfg->flags & RPF_FLAG_NO_MIXED_RADIX) != 0, ask_fused,
+                             rpf::kernel_supported(N, 0), rpf::kernel_supported(N, v), rpf::mixed_supported(N, v),
+                             rpf::fourstep_supported(N), rpf::bluestein_supported(N), rpf::bigblu_supported(N),
+                             rpf::generic_supported(N)};
+    c->family = pfb ? rpf::Family::None : rpf::select_family(q);
     // (a PFB engine transforms nothing itself: what counts is that its inner cf32 engine has a kernel)
-    if (pfb ? !(native_k1 || rpf::generic_supported(cfg->N)) : (!tuned && !generic))
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                    "No gfx950 kernel for " + std::to_string(cfg->N) +
-                        " bins in this build (supported: every even N up to 8388608 and the powers of two up to 67108864).");
-    if (cfg->n_buffers < 1)
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "Argument to 'buffers' must be a positive number.");
+    if (pfb ? !(q.k1_v0 || q.generic) : c->family == rpf::Family::None)
+        return bad("No gfx950 kernel for " + bins +
+                   " bins in this build (supported: every even N up to 8388608 and the powers of two up to 67108864).");
+    if (cfg->n_buffers < 1) return bad("Argument to 'buffers' must be a positive number.");
     if (cfg->buffer_capacity < 2 || (cfg->buffer_capacity % 2) != 0)
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "Buffer size must be a positive even number of bytes.");
-    if (static_cast<size_t>(cfg->buffer_capacity) % sample_bytes != 0)
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT,
-                    "Buffer size must be a multiple of the sample size (" + std::to_string(sample_bytes) + " bytes).");
+        return bad("Buffer size must be a positive even number of bytes.");
+    if (static_cast<size_t>(cfg->buffer_capacity) % c->sample_bytes != 0)
+        return bad("Buffer size must be a multiple of the sample size (" + std::to_string(c->sample_bytes) + " bytes).");
+    return RPF_OK;
+}
 
-    int ndev = 0;
-    hipError_t err = hipGetDeviceCount(&ndev);
-    if (err != hipSuccess || ndev < 1)
-        return fail(nullptr, RPF_ERR_HARDWARE,
-                    std::string("No HIP device available (") +
-                        (err != hipSuccess ? hipGetErrorString(err) : "device count 0") +
-                        "); this engine has no CPU path.");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "Invalid HIP device ordinal.");
-
+rpf_engine* new_engine(const rpf_config* cfg, const Checked& c, const PfbSpec* pfb)
+{
     rpf_engine* e = new rpf_engine();
     e->N = cfg->N;
-    e->step = step;
-    e->format = format;
-    e->sample_bytes = sample_bytes;
+    e->step = c.step;
+    e->format = c.format;
+    e->sample_bytes = c.sample_bytes;
     e->has_window = cfg->window != nullptr;
     e->n_buffers = cfg->n_buffers;
     e->buffer_capacity = static_cast<size_t>(cfg->buffer_capacity);
     e->device = cfg->device;
-    e->flags = cfg->flags;
     e->use_dma = !(cfg->flags & RPF_FLAG_NO_LDS_DMA);
-    e->variant = variant;
-    e->stats = stats;
-    if (stats) {
+    e->variant = c.variant;
+    e->stats = c.stats;
+    if (c.stats) {
         e->sum_sq.assign(e->N, 0.0);
         e->peak.assign(e->N, 0.0);
     }
-    e->fourstep = !pfb && fourstep;
-    e->mixed = !pfb && mixed;
-    e->bluestein = !pfb && bluestein;
-    e->bigblu = !pfb && bigblu;
-    e->generic = !pfb && generic;
+    e->family = c.family;
     e->taps = pfb ? pfb->taps : 0;
     e->queue_histogram.assign(e->n_buffers + 1, 0);
     e->pwr.assign(e->N, 0.0);
+    return e;
+}
 
-    auto cleanup = [&](int rc) {
-        release_device(e);
-        delete e;
-        return rc;
-    };
-#define CREATE_TRY(call)                                                                 \
-    do {                                                                                 \
-        hipError_t err__ = (call);                                                       \
-        if (err__ != hipSuccess) {                                                       \
-            (void)hipGetLastError();     /* not the caller's next HIP call's problem */  \
-            return cleanup(fail(nullptr, RPF_ERR_HARDWARE,                               \
-                                std::string(#call) + ": " + hipGetErrorString(err__)));  \
-        }                                                                                \
-    } while (0)
+// ---- the steps of a creation: each returns its code, create_engine frees everything once on any but RPF_OK ----
 
-    DeviceScope on_device(e->device);       // the caller's current device is restored on return
-    CREATE_TRY(on_device.status());
-    for (hipStream_t& cs : e->copy_streams) CREATE_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    CREATE_TRY(hipStreamCreateWithFlags(&e->compute_stream, hipStreamNonBlocking));
+// *d_ptr = a device block holding the `count` values at `host`
+template <class T, class U>
+int upload(rpf_engine* e, T** d_ptr, const U* host, size_t count)
+{
+    HIP_TRY(e, hipMalloc(d_ptr, sizeof(U) * count));
+    HIP_TRY(e, hipMemcpy(*d_ptr, host, sizeof(U) * count, hipMemcpyHostToDevice));
+    return RPF_OK;
+}
 
-    if (!pfb) {
-        // "plan": twiddle table on the device (where fftwf_plan_dft_1d stands, datastore.cxx:32)
-        std::vector<rpf::cf> tw;
-        int blu_m1 = 0, blu_m2 = 0;
-        if (e->bigblu) rpf::bigblu_lengths(e->N, &e->blu_M, &blu_m1, &blu_m2);
-        if (!e->generic) {
-            rpf::make_twiddles(e->bluestein ? rpf::bluestein_length(e->N) : e->bigblu ? e->blu_M : e->N, tw);
-            CREATE_TRY(hipMalloc(&e->d_twiddles, sizeof(rpf::cf) * tw.size()));
-            CREATE_TRY(hipMemcpy(e->d_twiddles, tw.data(), sizeof(rpf::cf) * tw.size(), hipMemcpyHostToDevice));
-        }
-        if (e->has_window) {
-            CREATE_TRY(hipMalloc(&e->d_window, sizeof(float) * e->N));
-            CREATE_TRY(hipMemcpy(e->d_window, cfg->window, sizeof(float) * e->N, hipMemcpyHostToDevice));
-        }
-        size_t partial_slots = 0, partial_len = e->N;
-        std::vector<float> blu_g, blu_bhat;
-        const bool gen_blu = e->generic && rpf::generic_length(e->N) != e->N;
-        if (e->bluestein || e->bigblu || gen_blu) {
-            std::vector<float>&g = blu_g, &bhat = blu_bhat;
-            rpf::make_bluestein_tables(e->N, cfg->window, g, bhat);
-            CREATE_TRY(hipMalloc(&e->d_chirp, sizeof(float) * g.size()));
-            CREATE_TRY(hipMemcpy(e->d_chirp, g.data(), sizeof(float) * g.size(), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMalloc(&e->d_bhat, sizeof(float) * bhat.size()));
-            CREATE_TRY(hipMemcpy(e->d_bhat, bhat.data(), sizeof(float) * bhat.size(), hipMemcpyHostToDevice));
-        }
-        if (e->generic) {
-            std::vector<rpf::cf> t0, t1;
-            rpf::generic_twiddle_tables(e->N, t0, t1, &e->gen_h);
-            CREATE_TRY(hipMalloc(&e->d_tw_sub, sizeof(rpf::cf) * t0.size()));
-            CREATE_TRY(hipMemcpy(e->d_tw_sub, t0.data(), sizeof(rpf::cf) * t0.size(), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMalloc(&e->d_tw_sub2, sizeof(rpf::cf) * t1.size()));
-            CREATE_TRY(hipMemcpy(e->d_tw_sub2, t1.data(), sizeof(rpf::cf) * t1.size(), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMalloc(&e->d_scratch, rpf::generic_scratch_bytes(e->N)));
-            hipDeviceProp_t prop;
-            CREATE_TRY(hipGetDeviceProperties(&prop, e->device));
-            e->plan.grid = prop.multiProcessorCount;
-            e->plan.block = 256;
-            e->plan.fpw = rpf::generic_batch(e->N);
-            e->plan.lds_bytes = 0;
-            partial_slots = e->stats ? rpf::kStatsPlanes : 1;
-        } else if (e->mixed) {
-            CREATE_TRY(rpf::plan_mixed(e->N, e->variant, e->has_window, e->device, &e->plan));
-            partial_slots = e->plan.grid;
-        } else if (e->bluestein) {
-            CREATE_TRY(rpf::plan_bluestein(e->N, e->device, &e->plan));
-            partial_slots = e->plan.grid;
-        } else if (e->bigblu) {
-            CREATE_TRY(rpf::bigblu_prepare(e->N, e->device, &e->plan));
-            std::vector<rpf::cf> tws;
-            rpf::make_twiddles(blu_m1, tws);
-            CREATE_TRY(hipMalloc(&e->d_tw_sub, sizeof(rpf::cf) * tws.size()));
-            CREATE_TRY(hipMemcpy(e->d_tw_sub, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
-            rpf::make_twiddles(blu_m2, tws);
-            CREATE_TRY(hipMalloc(&e->d_tw_sub2, sizeof(rpf::cf) * tws.size()));
-            CREATE_TRY(hipMemcpy(e->d_tw_sub2, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
-            // (the intermediate starts at 256 MB and grows with the launches: ensure_scratch)
-            e->scratch_per_frame = rpf::bigblu_scratch_bytes_per_frame(e->N);
-            e->scratch_max = rpf::bigblu_scratch_bytes(e->N);
-            e->scratch_bytes = std::min<size_t>(e->scratch_max, std::max<size_t>(e->scratch_per_frame, static_cast<size_t>(256) << 20));
-            CREATE_TRY(hipMalloc(&e->d_scratch, e->scratch_bytes));
-            partial_slots = rpf::bigblu_partial_slots(e->N);
-            partial_len = e->blu_M;
-            // the kernels read chirp, kernel spectrum and inter-step twiddles in their own lane order
-            std::vector<rpf::cf> g_t, bhat_t, step_tw, step_tw2;
-            rpf::bigblu_tables(e->N, reinterpret_cast<const rpf::cf*>(blu_g.data()),
-                               reinterpret_cast<const rpf::cf*>(blu_bhat.data()), g_t, bhat_t, step_tw, step_tw2);
-            (void)hipFree(e->d_chirp);
-            e->d_chirp = nullptr;
-            CREATE_TRY(hipMalloc(&e->d_chirp, sizeof(rpf::cf) * g_t.size()));
-            CREATE_TRY(hipMemcpy(e->d_chirp, g_t.data(), sizeof(rpf::cf) * g_t.size(), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMemcpy(e->d_bhat, bhat_t.data(), sizeof(rpf::cf) * bhat_t.size(), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMemcpy(e->d_twiddles, step_tw.data(), sizeof(rpf::cf) * step_tw.size(), hipMemcpyHostToDevice));
-            CREATE_TRY(hipMalloc(&e->d_step2, sizeof(rpf::cf) * step_tw2.size()));
-            CREATE_TRY(hipMemcpy(e->d_step2, step_tw2.data(), sizeof(rpf::cf) * step_tw2.size(), hipMemcpyHostToDevice));
-        } else if (e->fourstep) {
-            CREATE_TRY(rpf::fourstep_prepare(e->N, e->device, &e->plan));
-            int n1 = 0, n2 = 0;
-            rpf::fourstep_sub_lengths(e->N, &n1, &n2);
-            std::vector<rpf::cf> tws;
-            rpf::make_twiddles(n1, tws);
-            CREATE_TRY(hipMalloc(&e->d_tw_sub, sizeof(rpf::cf) * tws.size()));
-            CREATE_TRY(hipMemcpy(e->d_tw_sub, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
-            rpf::make_twiddles(n2, tws);
-            CREATE_TRY(hipMalloc(&e->d_tw_sub2, sizeof(rpf::cf) * tws.size()));
-            CREATE_TRY(hipMemcpy(e->d_tw_sub2, tws.data(), sizeof(rpf::cf) * tws.size(), hipMemcpyHostToDevice));
-            // The fused kernel (one persistent launch, the intermediate stays in each XCD's L2) where
-            // the device is the 8 x 32-CU part it is written for and its teams assemble; else K2a/K2b.
-            int fused_grid = 0;
-            // (overlapped frames: the two-kernel path -- the fused kernel's give-up verdict is one word per staging slot,
-            // which the gather path's several launches per slot would share)
-            if (!(cfg->flags & RPF_FLAG_NO_FOURSTEP_FUSED) && step == e->N &&
-                rpf::fourstep_fused_prepare(e->N, e->device, &fused_grid) == hipSuccess) {
-                CREATE_TRY(hipMalloc(&e->d_fused_scratch, rpf::fourstep_fused_scratch_bytes(e->N)));
-                CREATE_TRY(hipMalloc(&e->d_fused_ctl, rpf::fourstep_fused_ctl_bytes()));
-                CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->h_fused_words), 64, hipHostMallocMapped));
-                std::memset(e->h_fused_words, 0, 64);
-                CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->d_fused_words), e->h_fused_words, 0));
-                e->fused = true;
-                // (room for either path's partial spectra: a fused launch that gives up is re-run on K2a/K2b)
-                partial_slots = std::max<size_t>(rpf::fourstep_fused_slots(e->N), rpf::fourstep_partial_slots(e->N));
-            } else {
-                (void)hipGetLastError();
-                e->scratch_per_frame = rpf::fourstep_scratch_bytes_per_frame(e->N);
-                e->scratch_max = rpf::fourstep_scratch_bytes(e->N);
-                e->scratch_bytes = std::min<size_t>(e->scratch_max, static_cast<size_t>(256) << 20);
-                CREATE_TRY(hipMalloc(&e->d_scratch, e->scratch_bytes));
-                partial_slots = rpf::fourstep_partial_slots(e->N);
-            }
-            // K2a reads the inter-step twiddles and the window in its own lane order
-            std::vector<rpf::cf> step_tw;
-            std::vector<float> window_t;
-            rpf::fourstep_tables(e->N, cfg->window, step_tw, window_t);
-            CREATE_TRY(hipMemcpy(e->d_twiddles, step_tw.data(), sizeof(rpf::cf) * step_tw.size(), hipMemcpyHostToDevice));
-            if (e->has_window)
-                CREATE_TRY(hipMemcpy(e->d_window, window_t.data(), sizeof(float) * window_t.size(), hipMemcpyHostToDevice));
-        } else {
-            CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, true, e->device, &e->plan, e->format, e->stats));
-            rpf::LaunchInfo tmp;
-            CREATE_TRY(rpf::plan_launch(e->N, e->variant, e->has_window, false, e->device, &tmp, e->format, e->stats));
-            e->plan.grid = std::min(e->plan.grid, tmp.grid);
-            partial_slots = e->plan.grid + rpf::kMaxHops;    // a workgroup leaves one partial per hop it touches
-            if (e->stats) partial_slots = static_cast<size_t>(e->plan.grid) * rpf::kStatsPlanes;   // three planes per workgroup, no scans
-        }
-        CREATE_TRY(hipMalloc(&e->d_partial, sizeof(double) * partial_len * partial_slots));
+// master twiddles W_n^k ("plan": where fftwf_plan_dft_1d stands, datastore.cxx:32)
+int upload_twiddles(rpf_engine* e, rpf::cf** d_ptr, int n)
+{
+    std::vector<rpf::cf> tw;
+    rpf::make_twiddles(n, tw);
+    return upload(e, d_ptr, tw.data(), tw.size());
+}
+
+// room for `slots` partial spectra of `len` doubles
+int alloc_partial(rpf_engine* e, size_t slots, size_t len)
+{
+    HIP_TRY(e, hipMalloc(&e->d_partial, sizeof(double) * len * slots));
+    return RPF_OK;
+}
+
+// ---- one prepare per family: its tables on the device, e->plan, the partial spectra, the scratch policy ----
+
+// master twiddles of the transform length and the window as it is given: what K1 and the mixed-radix kernels read
+int upload_twiddles_and_window(rpf_engine* e, const rpf_config* cfg)
+{
+    if (int rc = upload_twiddles(e, &e->d_twiddles, e->N)) return rc;
+    return cfg->window ? upload(e, &e->d_window, cfg->window, static_cast<size_t>(e->N)) : RPF_OK;
+}
+
+int prepare_k1(rpf_engine* e, const rpf_config* cfg)
+{
+    if (int rc = upload_twiddles_and_window(e, cfg)) return rc;
+    HIP_TRY(e, rpf::plan_launch(e->N, e->variant, e->has_window, true, e->device, &e->plan, e->format, e->stats));
+    rpf::LaunchInfo tmp;
+    HIP_TRY(e, rpf::plan_launch(e->N, e->variant, e->has_window, false, e->device, &tmp, e->format, e->stats));
+    e->plan.grid = std::min(e->plan.grid, tmp.grid);
+    // a workgroup leaves one partial per hop it touches; a stats engine's: three planes per workgroup, no scans
+    const size_t grid = e->plan.grid;
+    return alloc_partial(e, e->stats ? grid * rpf::kStatsPlanes : grid + rpf::kMaxHops, e->N);
+}
+
+int prepare_mixed(rpf_engine* e, const rpf_config* cfg)
+{
+    if (int rc = upload_twiddles_and_window(e, cfg)) return rc;
+    HIP_TRY(e, rpf::plan_mixed(e->N, e->variant, e->has_window, e->device, &e->plan));
+    return alloc_partial(e, e->plan.grid, e->N);
+}
+
+// bluestein_tables.h's g and bhat (the window is in g: the Bluestein families have no window table)
+int upload_chirp(rpf_engine* e, const rpf_config* cfg)
+{
+    std::vector<float> g, bhat;
+    rpf::make_bluestein_tables(e->N, cfg->window, g, bhat);
+    if (int rc = upload(e, &e->d_chirp, g.data(), g.size())) return rc;
+    return upload(e, &e->d_bhat, bhat.data(), bhat.size());
+}
+
+int prepare_bluestein(rpf_engine* e, const rpf_config* cfg)
+{
+    if (int rc = upload_twiddles(e, &e->d_twiddles, rpf::bluestein_length(e->N))) return rc;
+    if (int rc = upload_chirp(e, cfg)) return rc;
+    HIP_TRY(e, rpf::plan_bluestein(e->N, e->device, &e->plan));
+    return alloc_partial(e, e->plan.grid, e->N);
+}
+
+int prepare_bigblu(rpf_engine* e, const rpf_config* cfg)
+{
+    int M = 0, m1 = 0, m2 = 0;
+    rpf::bigblu_lengths(e->N, &M, &m1, &m2);
+    HIP_TRY(e, rpf::bigblu_prepare(e->N, e->device, &e->plan));
+    // the kernels read chirp, kernel spectrum and inter-step twiddles in their own lane order
+    std::vector<float> g, bhat;
+    rpf::make_bluestein_tables(e->N, cfg->window, g, bhat);
+    std::vector<rpf::cf> g_t, bhat_t, step_tw, step_tw2;
+    rpf::bigblu_tables(e->N, reinterpret_cast<const rpf::cf*>(g.data()), reinterpret_cast<const rpf::cf*>(bhat.data()), g_t,
+                       bhat_t, step_tw, step_tw2);
+    int rc = upload_twiddles(e, &e->d_tw_sub, m1);
+    if (rc == RPF_OK) rc = upload_twiddles(e, &e->d_tw_sub2, m2);
+    if (rc == RPF_OK) rc = upload(e, &e->d_chirp, g_t.data(), g_t.size());
+    if (rc == RPF_OK) rc = upload(e, &e->d_bhat, bhat_t.data(), bhat_t.size());
+    if (rc == RPF_OK) rc = upload(e, &e->d_twiddles, step_tw.data(), step_tw.size());
+    if (rc == RPF_OK) rc = upload(e, &e->d_step2, step_tw2.data(), step_tw2.size());
+    if (rc != RPF_OK) return rc;
+    // (the intermediate starts at 256 MB and grows with the launches: ensure_scratch)
+    e->scratch_per_frame = rpf::bigblu_scratch_bytes_per_frame(e->N);
+    e->scratch_max = rpf::bigblu_scratch_bytes(e->N);
+    e->scratch_bytes = std::min<size_t>(e->scratch_max, std::max<size_t>(e->scratch_per_frame, static_cast<size_t>(256) << 20));
+    HIP_TRY(e, hipMalloc(&e->d_scratch, e->scratch_bytes));
+    e->partial_stride = static_cast<size_t>(M);          // partial spectra of M (not N) doubles each
+    return alloc_partial(e, rpf::bigblu_partial_slots(e->N), M);
+}
+
+int prepare_fourstep(rpf_engine* e, const rpf_config* cfg)
+{
+    HIP_TRY(e, rpf::fourstep_prepare(e->N, e->device, &e->plan));
+    int n1 = 0, n2 = 0;
+    rpf::fourstep_sub_lengths(e->N, &n1, &n2);
+    // K2a reads the inter-step twiddles and the window in its own lane order
+    std::vector<rpf::cf> step_tw;
+    std::vector<float> window_t;
+    rpf::fourstep_tables(e->N, cfg->window, step_tw, window_t);
+    int rc = upload_twiddles(e, &e->d_tw_sub, n1);
+    if (rc == RPF_OK) rc = upload_twiddles(e, &e->d_tw_sub2, n2);
+    if (rc == RPF_OK) rc = upload(e, &e->d_twiddles, step_tw.data(), step_tw.size());
+    if (rc == RPF_OK && cfg->window) rc = upload(e, &e->d_window, window_t.data(), window_t.size());
+    if (rc != RPF_OK) return rc;
+    // The fused kernel (one persistent launch, the intermediate stays in each XCD's L2) where
+    // the device is the 8 x 32-CU part it is written for and its teams assemble; else K2a/K2b.
+    int fused_grid = 0;
+    // (overlapped frames: the two-kernel path -- the fused kernel's give-up verdict is one word per staging slot,
+    // which the gather path's several launches per slot would share)
+    if (!(cfg->flags & RPF_FLAG_NO_FOURSTEP_FUSED) && e->step == e->N &&
+        rpf::fourstep_fused_prepare(e->N, e->device, &fused_grid) == hipSuccess) {
+        HIP_TRY(e, hipMalloc(&e->d_fused_scratch, rpf::fourstep_fused_scratch_bytes(e->N)));
+        HIP_TRY(e, hipMalloc(&e->d_fused_ctl, rpf::fourstep_fused_ctl_bytes()));
+        HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_fused_words), 64, hipHostMallocMapped));
+        std::memset(e->h_fused_words, 0, 64);
+        HIP_TRY(e, hipHostGetDevicePointer(reinterpret_cast<void**>(&e->d_fused_words), e->h_fused_words, 0));
+        e->fused = true;
+        // (room for either path's partial spectra: a fused launch that gives up is re-run on K2a/K2b)
+        return alloc_partial(e, std::max<size_t>(rpf::fourstep_fused_slots(e->N), rpf::fourstep_partial_slots(e->N)), e->N);
     }
-    const size_t pwr_planes = e->stats ? rpf::kStatsPlanes : 1;
-    CREATE_TRY(hipMalloc(&e->d_pwr, sizeof(double) * e->N * pwr_planes));
-    CREATE_TRY(hipMemset(e->d_pwr, 0, sizeof(double) * e->N * pwr_planes));
-    if (e->fused) {
-        // Prove once that the eight teams assemble on this device (one round per team on a dummy
-        // stream); if they do not, this engine uses the two-kernel path.
-        const size_t round_bytes = 2u * 262144u * 8u;         // FR frames of N samples for each of 8 teams
-        void* d_dummy = nullptr;
-        struct FreeOnExit {                                   // (every exit of this block, CREATE_TRY's included)
-            void*& p;
-            ~FreeOnExit() { if (p) (void)hipFree(p); }
-        } free_dummy{d_dummy};
-        CREATE_TRY(hipMalloc(&d_dummy, round_bytes));
-        CREATE_TRY(hipMemset(d_dummy, 0x80, round_bytes));
-        bool aborted = true;
-        hipError_t lerr = rpf::launch_fourstep_fused(e->N, e->has_window, true, static_cast<const uint8_t*>(d_dummy),
-                                                     static_cast<long>(round_bytes / (2u * static_cast<size_t>(e->N))),
-                                                     e->d_tw_sub, e->d_tw_sub2, e->d_twiddles, e->d_window, e->d_fused_scratch,
-                                                     e->d_partial, e->d_fused_ctl, e->compute_stream);
-        if (lerr == hipSuccess) lerr = rpf::fourstep_fused_aborted(e->d_fused_ctl, e->compute_stream, &aborted);
-        if (lerr != hipSuccess || aborted) {
-            (void)hipGetLastError();
-            retire_fused(e);
-            (void)hipFree(e->d_fused_scratch);          // (nothing is in flight here)
-            e->d_fused_scratch = nullptr;
-            e->scratch_bytes = std::min<size_t>(e->scratch_max, static_cast<size_t>(256) << 20);
-            CREATE_TRY(hipMalloc(&e->d_scratch, e->scratch_bytes));
-        }
-    }
+    (void)hipGetLastError();
+    e->scratch_per_frame = rpf::fourstep_scratch_bytes_per_frame(e->N);
+    e->scratch_max = rpf::fourstep_scratch_bytes(e->N);
+    e->scratch_bytes = std::min<size_t>(e->scratch_max, static_cast<size_t>(256) << 20);
+    HIP_TRY(e, hipMalloc(&e->d_scratch, e->scratch_bytes));
+    return alloc_partial(e, rpf::fourstep_partial_slots(e->N), e->N);
+}
 
+int prepare_generic(rpf_engine* e, const rpf_config* cfg)
+{
+    std::vector<rpf::cf> t0, t1;
+    rpf::generic_twiddle_tables(e->N, t0, t1, &e->gen_h);
+    int rc = upload(e, &e->d_tw_sub, t0.data(), t0.size());
+    if (rc == RPF_OK) rc = upload(e, &e->d_tw_sub2, t1.data(), t1.size());
+    if (rc == RPF_OK && cfg->window) rc = upload(e, &e->d_window, cfg->window, static_cast<size_t>(e->N));
+    if (rc == RPF_OK && rpf::generic_length(e->N) != e->N) rc = upload_chirp(e, cfg);      // its Bluestein form
+    if (rc != RPF_OK) return rc;
+    HIP_TRY(e, hipMalloc(&e->d_scratch, rpf::generic_scratch_bytes(e->N)));
+    hipDeviceProp_t prop;
+    HIP_TRY(e, hipGetDeviceProperties(&prop, e->device));
+    e->plan.grid = prop.multiProcessorCount;
+    e->plan.block = 256;
+    e->plan.fpw = rpf::generic_batch(e->N);
+    e->plan.lds_bytes = 0;
+    return alloc_partial(e, e->stats ? rpf::kStatsPlanes : 1, e->N);
+}
+
+int prepare_family(rpf_engine* e, const rpf_config* cfg)
+{
+    switch (e->family) {
+    case rpf::Family::K1: return prepare_k1(e, cfg);
+    case rpf::Family::Mixed: return prepare_mixed(e, cfg);
+    case rpf::Family::FourStep: return prepare_fourstep(e, cfg);
+    case rpf::Family::Bluestein: return prepare_bluestein(e, cfg);
+    case rpf::Family::BigBluestein: return prepare_bigblu(e, cfg);
+    case rpf::Family::Generic: return prepare_generic(e, cfg);
+    case rpf::Family::None: break;        // (a PFB engine: create_pfb makes the inner engine, which has the tables)
+    }
+    return RPF_OK;
+}
+
+// Prove once that the eight teams assemble on this device (one round per team on a dummy
+// stream); if they do not, this engine uses the two-kernel path.
+int prove_fused(rpf_engine* e)
+{
+    const size_t round_bytes = 2u * 262144u * 8u;         // FR frames of N samples for each of 8 teams
+    void* d_dummy = nullptr;
+    struct FreeOnExit {                                   // (every exit of this function)
+        void*& p;
+        ~FreeOnExit() { (void)hipFree(p); }
+    } free_dummy{d_dummy};
+    HIP_TRY(e, hipMalloc(&d_dummy, round_bytes));
+    HIP_TRY(e, hipMemset(d_dummy, 0x80, round_bytes));
+    bool aborted = true;
+    hipError_t lerr = rpf::launch_fourstep_fused(e->N, e->has_window, true, static_cast<const uint8_t*>(d_dummy),
+                                                 static_cast<long>(round_bytes / (2u * static_cast<size_t>(e->N))),
+                                                 e->d_tw_sub, e->d_tw_sub2, e->d_twiddles, e->d_window, e->d_fused_scratch,
+                                                 e->d_partial, e->d_fused_ctl, e->compute_stream);
+    if (lerr == hipSuccess) lerr = rpf::fourstep_fused_aborted(e->d_fused_ctl, e->compute_stream, &aborted);
+    if (lerr != hipSuccess || aborted) {
+        (void)hipGetLastError();
+        retire_fused(e);
+        (void)hipFree(e->d_fused_scratch);          // (nothing is in flight here)
+        e->d_fused_scratch = nullptr;
+        e->scratch_bytes = std::min<size_t>(e->scratch_max, static_cast<size_t>(256) << 20);
+        HIP_TRY(e, hipMalloc(&e->d_scratch, e->scratch_bytes));
+    }
+    return RPF_OK;
+}
+
+// The buffer pool, the device staging ring and the verdict words of its slots.  inner_of_pfb: the transform engine a
+// PFB engine owns -- it is never fed through its queues, so its staging slots hold one (minimal) buffer each.
+int create_queues(rpf_engine* e, bool inner_of_pfb)
+{
     // buffer pool: pinned host memory (datastore.cxx:27-28)
     // ONE allocation, the buffers side by side: what the producer fills in order the consumer can send in one copy.
     // (If that much pinned memory is not to be had in one piece: buffer by buffer, as before.)
@@ -1256,11 +1252,11 @@ int create_engine(const rpf_config* cfg, const PfbSpec* pfb, bool inner_of_pfb, 
             b.data = e->pool_base + k * e->buffer_capacity;
         } else {
             void* p = nullptr;
-            CREATE_TRY(hipHostMalloc(&p, e->buffer_capacity, hipHostMallocDefault));
+            HIP_TRY(e, hipHostMalloc(&p, e->buffer_capacity, hipHostMallocDefault));
             b.data = static_cast<uint8_t*>(p);
         }
         b.size = e->buffer_capacity;
-        CREATE_TRY(hipEventCreateWithFlags(&b.copied, hipEventDisableTiming));
+        HIP_TRY(e, hipEventCreateWithFlags(&b.copied, hipEventDisableTiming));
         e->empty_buffers.push_back(&b);
     }
     // device staging ring: head room for a carried partial frame + one buffer
@@ -1271,33 +1267,73 @@ int create_engine(const rpf_config* cfg, const PfbSpec* pfb, bool inner_of_pfb, 
     e->coalesce = inner_of_pfb ? 1 : std::max<size_t>(1, (32u << 20) / e->buffer_capacity);
     e->staging.resize(kStagingSlots);
     for (auto& s : e->staging) {
-        void* p = nullptr;
-        CREATE_TRY(hipMalloc(&p, e->head_room + e->coalesce * e->buffer_capacity));
-        s.base = static_cast<uint8_t*>(p);
-        CREATE_TRY(hipEventCreateWithFlags(&s.kernel_done, hipEventDisableTiming));
-        for (hipEvent_t& ev : s.copy_done) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        HIP_TRY(e, hipMalloc(&s.base, e->head_room + e->coalesce * e->buffer_capacity));
+        HIP_TRY(e, hipEventCreateWithFlags(&s.kernel_done, hipEventDisableTiming));
+        for (hipEvent_t& ev : s.copy_done) HIP_TRY(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
     static_assert(kStagingSlots <= 3, "h_fused_words[0 .. 2]: one verdict word per staging slot");
     if (e->h_fused_words)
         for (size_t k = 0; k < e->staging.size(); ++k) e->staging[k].verdict = e->h_fused_words + k;
-    if (pfb) {
-        const size_t nco = static_cast<size_t>(e->taps) * static_cast<size_t>(e->N);
-        CREATE_TRY(hipMalloc(&e->d_pfb_coeffs, sizeof(float) * nco));
-        CREATE_TRY(hipMemcpy(e->d_pfb_coeffs, pfb->coeffs, sizeof(float) * nco, hipMemcpyHostToDevice));
-        // the transform: a rectangular cf32 engine of the same N, device and staging flag, with one minimal buffer
-        rpf_config icfg;
-        icfg.struct_size = sizeof(icfg);
-        icfg.N = e->N;
-        icfg.window = nullptr;
-        icfg.n_buffers = 1;
-        icfg.buffer_capacity = 8;
-        icfg.device = e->device;
-        icfg.flags = (cfg->flags & (RPF_FLAG_NO_LDS_DMA | RPF_FLAG_CATCH_ALL)) | RPF_FLAG_SAMPLE_FORMAT(RPF_FORMAT_CF32);
-        icfg.frame_step = 0;
-        const int rc = create_engine(&icfg, nullptr, /*inner_of_pfb=*/true, &e->inner);
-        if (rc != RPF_OK) return cleanup(rc);
+    return RPF_OK;
+}
+
+int create_engine(const rpf_config* cfg, const PfbSpec* pfb, bool inner_of_pfb, rpf_engine** out);
+
+// A PFB engine's coefficients and its transform: a rectangular cf32 engine of the same N, device and staging flag,
+// with one minimal buffer.
+int create_pfb(rpf_engine* e, const rpf_config* cfg, const PfbSpec* pfb)
+{
+    if (int rc = upload(e, &e->d_pfb_coeffs, pfb->coeffs, static_cast<size_t>(e->taps) * static_cast<size_t>(e->N))) return rc;
+    rpf_config icfg;
+    icfg.struct_size = sizeof(icfg);
+    icfg.N = e->N;
+    icfg.window = nullptr;
+    icfg.n_buffers = 1;
+    icfg.buffer_capacity = 8;
+    icfg.device = e->device;
+    icfg.flags = (cfg->flags & (RPF_FLAG_NO_LDS_DMA | RPF_FLAG_CATCH_ALL)) | RPF_FLAG_SAMPLE_FORMAT(RPF_FORMAT_CF32);
+    icfg.frame_step = 0;
+    return create_engine(&icfg, nullptr, /*inner_of_pfb=*/true, &e->inner);
+}
+
+// Everything a new engine owns on its device, step by step; the first step that fails has said why and ends it.
+int build_engine(rpf_engine* e, const rpf_config* cfg, const PfbSpec* pfb, bool inner_of_pfb)
+{
+    DeviceScope on_device(e->device);       // the caller's current device is restored on return
+    HIP_TRY(e, on_device.status());
+    for (hipStream_t& cs : e->copy_streams) HIP_TRY(e, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    HIP_TRY(e, hipStreamCreateWithFlags(&e->compute_stream, hipStreamNonBlocking));
+    if (int rc = prepare_family(e, cfg)) return rc;
+    const size_t pwr_bytes = sizeof(double) * e->N * (e->stats ? rpf::kStatsPlanes : 1);
+    HIP_TRY(e, hipMalloc(&e->d_pwr, pwr_bytes));
+    HIP_TRY(e, hipMemset(e->d_pwr, 0, pwr_bytes));
+    if (int rc = e->fused ? prove_fused(e) : RPF_OK) return rc;
+    if (int rc = create_queues(e, inner_of_pfb)) return rc;
+    return pfb ? create_pfb(e, cfg, pfb) : RPF_OK;
+}
+
+// rpf_engine_create (pfb null) and rpf_engine_create_pfb: check, new engine, build.  A failed build frees everything and
+// clears the sticky HIP error (it is not the caller's next HIP call's problem); rpf_last_global_error says what failed.
+int create_engine(const rpf_config* cfg, const PfbSpec* pfb, bool inner_of_pfb, rpf_engine** out)
+{
+    Checked c;
+    if (int rc = check_config(cfg, pfb, out, &c)) return rc;
+    int ndev = 0;
+    hipError_t err = hipGetDeviceCount(&ndev);
+    if (err != hipSuccess || ndev < 1)
+        return fail(nullptr, RPF_ERR_HARDWARE,
+                    std::string("No HIP device available (") + (err != hipSuccess ? hipGetErrorString(err) : "device count 0") +
+                        "); this engine has no CPU path.");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, RPF_ERR_INVALID_ARGUMENT, "Invalid HIP device ordinal.");
+    rpf_engine* e = new_engine(cfg, c, pfb);
+    const int rc = build_engine(e, cfg, pfb, inner_of_pfb);
+    if (rc != RPF_OK) {
+        (void)hipGetLastError();
+        DeviceScope on_device(e->device);
+        release_device(e);
+        delete e;
+        return rc;
     }
-#undef CREATE_TRY
     *out = e;
     return RPF_OK;
 }
@@ -1572,18 +1608,20 @@ int rpf_accumulate(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t 
     return rc;
 }
 
-int rpf_accumulate_device(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
-                          double* d_pwr_out, void* hip_stream, int64_t* repeats_done)
+// rpf_accumulate_device and rpf_accumulate_device_stats (want_stats: needs a stats engine, d_out is its three planes)
+static int accumulate_device(rpf_engine* e, const char* who, bool want_stats, const void* d_stream, size_t nbytes,
+                             int64_t repeats, double* d_out, void* hip_stream, int64_t* repeats_done)
 {
-    if (!e || !d_pwr_out || (!d_stream && nbytes))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: NULL argument");
-    if (e->worker_running)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: acquisition running");
+    const std::string me = who, out_name = want_stats ? "d_out" : "d_pwr_out";
+    if (!e || !d_out || (!d_stream && nbytes)) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+    if (want_stats && !e->stats)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": the engine was created without RPF_FLAG_BIN_STATS");
+    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": acquisition running");
     if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
     if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    if (reinterpret_cast<uintptr_t>(d_pwr_out) & 15)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device: d_pwr_out must be 16-byte aligned");
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": " + out_name + " must be 16-byte aligned");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the HIP null stream
@@ -1591,39 +1629,22 @@ int rpf_accumulate_device(rpf_engine* e, const void* d_stream, size_t nbytes, in
     nframes = std::min(nframes, repeats);
     if (repeats_done) *repeats_done = nframes;
     if (nframes == 0) {
-        HIP_TRY(e, hipMemsetAsync(d_pwr_out, 0, sizeof(double) * e->N, s));
+        HIP_TRY(e, hipMemsetAsync(d_out, 0, sizeof(double) * e->N * (want_stats ? rpf::kStatsPlanes : 1), s));
         return RPF_OK;
     }
-    return launch_frames(e, static_cast<const uint8_t*>(d_stream), nframes, d_pwr_out,
-                         /*accumulate=*/false, s);
+    return launch_frames(e, static_cast<const uint8_t*>(d_stream), nframes, d_out, /*accumulate=*/false, s, nullptr, want_stats);
+}
+
+int rpf_accumulate_device(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
+                          double* d_pwr_out, void* hip_stream, int64_t* repeats_done)
+{
+    return accumulate_device(e, "rpf_accumulate_device", false, d_stream, nbytes, repeats, d_pwr_out, hip_stream, repeats_done);
 }
 
 int rpf_accumulate_device_stats(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
                                 double* d_out, void* hip_stream, int64_t* repeats_done)
 {
-    if (!e || !d_out || (!d_stream && nbytes))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: NULL argument");
-    if (!e->stats)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: the engine was created without RPF_FLAG_BIN_STATS");
-    if (e->worker_running)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: acquisition running");
-    if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
-    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_stats: d_out must be 16-byte aligned");
-    DeviceScope on_device(e->device);
-    HIP_TRY(e, on_device.status());
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    int64_t nframes = frames_in(e, nbytes);
-    nframes = std::min(nframes, repeats);
-    if (repeats_done) *repeats_done = nframes;
-    if (nframes == 0) {
-        HIP_TRY(e, hipMemsetAsync(d_out, 0, sizeof(double) * e->N * rpf::kStatsPlanes, s));
-        return RPF_OK;
-    }
-    return launch_frames(e, static_cast<const uint8_t*>(d_stream), nframes, d_out, /*accumulate=*/false, s, nullptr,
-                         /*want_stats=*/true);
+    return accumulate_device(e, "rpf_accumulate_device_stats", true, d_stream, nbytes, repeats, d_out, hip_stream, repeats_done);
 }
 
 int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
@@ -1674,13 +1695,7 @@ int rpf_device_reduce(rpf_engine* e, double* d_pwr_out, void* hip_stream)
                                            /*accumulate=*/false, static_cast<hipStream_t>(hip_stream), e->plan.partial_f32));
         return RPF_OK;
     }
-    HIP_TRY(e, rpf::launch_reduce(e->d_partial, e->last_slots, e->N, d_pwr_out,
-                                  /*accumulate=*/false, static_cast<hipStream_t>(hip_stream),
-                                  e->plan.partial_f32, e->bigblu ? static_cast<size_t>(e->blu_M) : 0));
-    if (e->last_was_fused)
-        HIP_TRY(e, rpf::launch_fused_verdict(e->d_fused_ctl, d_pwr_out, e->N, e->d_fused_words + 3, e->d_fused_words + 4,
-                                             static_cast<hipStream_t>(hip_stream)));
-    return RPF_OK;
+    return reduce_last(e, d_pwr_out, /*accumulate=*/false, static_cast<hipStream_t>(hip_stream), nullptr);
 }
 
 // Shared argument checks of the hop entries; fills frames[h] = min(repeats[h], frames(nbytes[h])).
@@ -1727,7 +1742,7 @@ int rpf_accumulate_device_hops(rpf_engine* e, const void* const* d_streams, cons
     if (repeats_done)
         for (int h = 0; h < n_hops; ++h) repeats_done[h] = frames[h];
     const size_t N = static_cast<size_t>(e->N);
-    if (!is_k1(e) || overlapped(e) || e->stats || e->taps) {
+    if (e->taps || !is_k1(e) || overlapped(e) || e->stats) {
         // the other kernel families -- and overlapped frames (the scan kernel reads frames side by side), stats
         // engines (the scan kernel keeps no statistics; what comes back here is the power alone) and PFB engines (a
         // fold in front of every transform) -- run one acquisition per launch set
@@ -2273,7 +2288,7 @@ int rpf_fused_status(rpf_engine* e, int* active, int64_t* launches_gave_up, int6
 {
     if (!e) return RPF_ERR_INVALID_ARGUMENT;
     if (e->fused && !e->worker_running) note_device_path_aborts(e);
-    if (active) *active = (e->fourstep && e->fused) ? 1 : 0;
+    if (active) *active = (e->family == rpf::Family::FourStep && e->fused) ? 1 : 0;
     if (launches_gave_up) *launches_gave_up = e->h_fused_words ? __atomic_load_n(&e->h_fused_words[4], __ATOMIC_ACQUIRE) : 0;
     if (launches_recovered) *launches_recovered = e->fused_recovered;
     return RPF_OK;
