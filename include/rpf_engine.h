@@ -39,7 +39,8 @@ extern "C" {
                                rpf_accumulate_device_excised, rpf_accumulate_excised;
                                rpf_engine_create_pfb, rpf_pfb_taps;
                                rpf_quantile_reset, rpf_quantile_append_device, rpf_quantile_append,
-                               rpf_quantile_select_device, rpf_quantile_select, rpf_quantile_rows, rpf_quantile_max_rows */
+                               rpf_quantile_select_device, rpf_quantile_select, rpf_quantile_rows, rpf_quantile_max_rows;
+                               rpf_accumulate_device_cross, rpf_accumulate_cross */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -265,6 +266,57 @@ int rpf_accumulate_device(rpf_engine* e, const void* d_stream, size_t nbytes, in
  * rpf_accumulate_device of the same engine writes. */
 int rpf_accumulate_device_stats(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
                                 double* d_out /* 3 x N: S1, S2, PK */, void* hip_stream, int64_t* repeats_done);
+
+/* Cross-spectrum of two streams: Sab[k] = sum over the frames of A_f[k] conj(B_f[k]) beside Saa and Sbb, from FOUR power
+ * spectra and the polarisation identity
+ *     |A + B|^2 = |A|^2 + |B|^2 + 2 Re(A conj B),      |A + iB|^2 = |A|^2 + |B|^2 + 2 Im(A conj B)
+ * with no transform kernel of its own.  Everything that computes or checks it refers to this definition.
+ *   Inputs.  Two streams a and b in the engine's sample format, both of `nbytes` bytes, a multiple of b bytes per sample.
+ *     The samples are converted to float32 exactly, as the format defines it (cu8: v - 127; cs8, cs16, cf32: v).  Frames,
+ *     frame step, `repeats` and the dropped tail are those of rpf_accumulate_device on this engine: the frames used are
+ *     [0, min(repeats, rpf_frames_in(e, nbytes))).
+ *   Combined streams.  Sample by sample, I and Q as float32, one rounding per component and no contraction
+ *     (csrc/cross_core.h):
+ *         u = (aI + bI, aQ + bQ)   = a + b
+ *         v = (aI - bQ, aQ + bI)   = a + i b
+ *     exact for cu8, cs8 and cs16 (sums of 16-bit values are float32 integers), one float32 rounding for cf32.
+ *   Four power planes.  Paa and Pbb are what rpf_accumulate_device of THIS engine writes for a and for b.  Puu and Pvv are
+ *     what a cf32 engine with the same N, window, frame step, device and flags writes for u and v: bit for bit wherever
+ *     the launches use the same grid and staging route, and with more than one chunk of scratch up to the grouping of the
+ *     double additions.  A cf32 engine is its own cf32 engine.
+ *   Output.  d_out[4 x N] (device doubles, 16-byte aligned, overwritten; zeros for a stream without a whole frame), bin
+ *     N/2 = DC, computed in double, every operation rounded on its own, in exactly this order:
+ *         C = Paa + Pbb;   out[0] = Paa;  out[1] = Pbb;  out[2] = 0.5 (Puu - C);  out[3] = 0.5 (Pvv - C)
+ *     so that Sab = out[2] + i out[3], A and B being the transforms as the engine computes them: (-1)^n and the window
+ *     applied, forward, unnormalised.
+ *   Derived quantities (stats.coherence and stats.cross_phase; coherence and cross_phase of host/datastore.h):
+ *         gamma^2 = (out[2]^2 + out[3]^2) / (out[0] out[1])    NaN where the denominator is 0; NOT clamped
+ *         phase   = atan2(out[3], out[2])                      radians
+ *   What a user must know.  gamma^2 of M frames is a biased estimate: identically 1 for M = 1 and about 1/M for unrelated
+ *     streams.  Rounding can put it a few 1e-7 above 1.  The absolute error of Sab scales with Saa + Sbb, not with |Sab|:
+ *     two streams whose levels differ by 40 dB carry about 100 times the relative error in gamma of two streams of equal
+ *     level.  A NaN or an Inf in a cf32 stream propagates as it does for the power: into every bin of the planes that
+ *     stream enters (a NaN in b: out[1], out[2] and out[3]).
+ * The engine creates the cf32 engine at the first cross call (a windowed engine keeps its N window values on the host for
+ * that), together with its scratch: two cf32 streams of at most 64 MB of whole frames each (at least one frame) and the
+ * planes.  rpf_accumulate_device_cross puts every launch on `hip_stream` and returns without synchronising: this engine's
+ * transform over a and over b; per chunk of scratch ONE combine launch (csrc/rpf_cross.hip, memory-bound: 2b bytes in and
+ * 16 out per sample pair) and the cf32 engine's transform over u and over v, chunks after the first adding; one small
+ * finishing launch into d_out.  It costs four transforms where a two-stream kernel would need two.  It does not touch
+ * the buffer queues, pwr, repeats_done, the statistics or the quantile row store; *repeats_done (may be NULL) is the frame
+ * count; rpf_last_launch_info reports the last transform launch, the cf32 engine's.  One cross call at a time per engine.
+ * rpf_accumulate_cross is the same on two host streams, the counterpart of rpf_accumulate but not through the buffer
+ * queues: both streams move through engine-owned device memory in pieces of whole frames (the pieces of
+ * rpf_accumulate_series with one frame per integration), one piece of each at a time, every piece adds into the four
+ * planes, the finishing launch runs once at the end and 4 x N doubles come back.  Synchronises before it returns.
+ * RPF_ERR_INVALID_ARGUMENT, before any launch: a NULL argument; an engine created with RPF_FLAG_BIN_STATS; a PFB engine; a
+ * kernel variant other than 0; a running acquisition; repeats < 0; nbytes that is no multiple of b; d_a or d_b that is no
+ * multiple of b (each stream by the rules of rpf_accumulate_device: 16-byte aligned for the LDS-DMA path); d_out not
+ * 16-byte aligned.  An engine that never makes a cross call takes exactly the path it took. */
+int rpf_accumulate_device_cross(rpf_engine* e, const void* d_a, const void* d_b, size_t nbytes, int64_t repeats,
+                                double* d_out /* 4 x N */, void* hip_stream, int64_t* repeats_done);
+int rpf_accumulate_cross(rpf_engine* e, const uint8_t* a, const uint8_t* b, size_t nbytes, int64_t repeats,
+                         double* out /* 4 x N, host */, int64_t* repeats_done);
 
 /* The two halves of rpf_accumulate_device as separate enqueues, so that a
  * benchmark can bracket the dominant kernel alone with events on `hip_stream`:

@@ -18,4 +18,9 @@ for l in sys.stdin:
             f = re.search(r'pfb_fold_(sliding|reread)_kernelILi(\d+)E(?:Li(\d+)E)?Lb(\d)E', cur)
             if f:
                 tag = 'pfb_fold %s fmt=%s taps=%s aligned=%s' % (f.group(1), f.group(2), f.group(3) or 'any', f.group(4))
+            f = re.search(r'cross_combine_kernelILi(\d+)ELb(\d)ELb(\d)E', cur)
+            if f:
+                tag = 'cross_combine fmt=%s aligned_a=%s aligned_b=%s' % f.groups()
+            elif 'cross_finish_kernel' in cur:
+                tag = 'cross_finish'
             print(tag, {k: d.get(k) for k in ('VGPRs', 'AGPRs', 'ScratchSize', 'Occupancy', 'VGPRs Spill')})

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "bluestein_tables.h"
+#include "cross_core.h"
 #include "engine_family.h"
 #include "rpf_kernels.h"
 #include "series_pieces.h"
@@ -176,6 +177,15 @@ struct rpf_engine {
     rpf_engine* inner = nullptr;          // a rectangular cf32 engine of the same N, device and staging flag
     float* d_pfb_z = nullptr;             // one chunk of folded frames, float32 I/Q side by side; allocated at the first launch
     int64_t pfb_chunk_frames = 0;         // ... frames it holds (kGatherBytes / 8N, at least one)
+    // cross-spectrum of two streams (rpf_accumulate[_device]_cross); everything below `window` is made at the first call
+    uint32_t flags = 0;                   // rpf_config::flags as given, and
+    std::vector<float> window;            // ... the window as given (host): what the cf32 engine below is created from
+    rpf_engine* cross_inner = nullptr;    // the cf32 engine of the same N, window, frame step, device and flags; a cf32 engine: itself
+    float* d_cross_uv = nullptr;          // u = a + b, then v = a + i b: one chunk of whole frames each, cf32
+    size_t cross_v_offset = 0;            // ... floats from u to v
+    int64_t cross_chunk_frames = 0;       // ... frames a chunk holds (as many as span at most kGatherBytes, at least one)
+    double* d_cross_planes = nullptr;     // Paa, Pbb, Puu, Pvv, then the host entry's four output planes: 8 N doubles
+    bool last_was_cross = false;          // the last transform launched was a cross call's: rpf_last_launch_info reports cross_inner's
 
     mutable std::string last_error;
 };
@@ -514,6 +524,7 @@ int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes,
                         hipStream_t stream, unsigned* slot_verdict, bool want_stats)
 {
     if (e->fused && !slot_verdict) note_device_path_aborts(e);
+    e->last_was_cross = false;
     int nslots = 0;
     int rc = launch_transform(e, d_frames, nframes, stream, &nslots);
     if (rc != RPF_OK) return rc;
@@ -889,7 +900,7 @@ void release_device(rpf_engine* e)
                             e->d_step2, e->d_gather, e->d_chirp, e->d_bhat, e->d_window, e->d_partial,
                             e->d_series_partial, e->d_series_in, e->d_series_out, e->d_excise_state, e->d_excise_mask,
                             e->d_quantile_rows, e->d_quantile_work, e->d_quantile_out, e->d_pfb_coeffs, e->d_pfb_z,
-                            e->d_pwr};
+                            e->d_cross_uv, e->d_cross_planes, e->d_pwr};
     for (void* p : blocks) (void)hipFree(p);
     if (e->h_fused_words) (void)hipHostFree(e->h_fused_words);
     if (e->inner) {
@@ -897,6 +908,11 @@ void release_device(rpf_engine* e)
         delete e->inner;
         e->inner = nullptr;
     }
+    if (e->cross_inner && e->cross_inner != e) {
+        release_device(e->cross_inner);
+        delete e->cross_inner;
+    }
+    e->cross_inner = nullptr;
     for (auto& s : e->staging) {
         if (s.base) (void)hipFree(s.base);
         if (s.kernel_done) (void)hipEventDestroy(s.kernel_done);
@@ -1016,6 +1032,8 @@ rpf_engine* new_engine(const rpf_config* cfg, const Checked& c, const PfbSpec* p
     e->format = c.format;
     e->sample_bytes = c.sample_bytes;
     e->has_window = cfg->window != nullptr;
+    e->flags = cfg->flags;
+    if (cfg->window) e->window.assign(cfg->window, cfg->window + cfg->N);
     e->n_buffers = cfg->n_buffers;
     e->buffer_capacity = static_cast<size_t>(cfg->buffer_capacity);
     e->device = cfg->device;
@@ -1645,6 +1663,151 @@ int rpf_accumulate_device_stats(rpf_engine* e, const void* d_stream, size_t nbyt
                                 double* d_out, void* hip_stream, int64_t* repeats_done)
 {
     return accumulate_device(e, "rpf_accumulate_device_stats", true, d_stream, nbytes, repeats, d_out, hip_stream, repeats_done);
+}
+
+// ---- cross-spectrum of two streams: four power spectra and the polarisation identity (include/rpf_engine.h) ----------
+
+// Everything both cross entries refuse, before any launch.
+static int cross_check(rpf_engine* e, const char* who, const void* a, const void* b, size_t nbytes, int64_t repeats,
+                       const void* out)
+{
+    const std::string me = who;
+    if (!e || !out || ((!a || !b) && nbytes)) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+    if (e->stats)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not on an engine created with RPF_FLAG_BIN_STATS");
+    if (e->taps) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not on a PFB engine");
+    if (e->variant != 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not with a kernel variant other than 0");
+    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": acquisition running");
+    if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
+    if (nbytes % e->sample_bytes)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": nbytes must be a multiple of the sample size (" + std::to_string(e->sample_bytes) + " bytes)");
+    return RPF_OK;
+}
+
+// The cf32 engine (a cf32 engine: itself) and the scratch of the cross entries, made at the first call.
+static int ensure_cross(rpf_engine* e)
+{
+    if (!e->cross_inner) {
+        if (e->format == RPF_FORMAT_CF32) {
+            e->cross_inner = e;
+        } else {
+            rpf_config icfg;
+            icfg.struct_size = sizeof(icfg);
+            icfg.N = e->N;
+            icfg.window = e->window.empty() ? nullptr : e->window.data();
+            icfg.n_buffers = 1;
+            icfg.buffer_capacity = 8;
+            icfg.device = e->device;
+            icfg.flags = (e->flags & ~RPF_FLAG_SAMPLE_FORMAT(0xf)) | RPF_FLAG_SAMPLE_FORMAT(RPF_FORMAT_CF32);
+            icfg.frame_step = e->step;
+            const int rc = create_engine(&icfg, nullptr, /*inner_of_pfb=*/true, &e->cross_inner);
+            if (rc != RPF_OK) return fail(e, rc, g_last_error);
+        }
+    }
+    const size_t N = static_cast<size_t>(e->N), S = static_cast<size_t>(e->step);
+    if (!e->d_cross_uv) {
+        const rpf::FrameBytes fb{sizeof(float) * 2 * N, sizeof(float) * 2 * S};
+        const int64_t chunk = std::max<int64_t>(1, fb.frames_in(rpf::kGatherBytes));
+        const size_t floats = fb.span(chunk) / sizeof(float);              // of one stream
+        const size_t v_offset = (floats + 63) / 64 * 64;                   // v starts 256-byte aligned
+        HIP_TRY(e, hipMalloc(&e->d_cross_uv, sizeof(float) * (v_offset + floats)));
+        e->cross_chunk_frames = chunk;
+        e->cross_v_offset = v_offset;
+    }
+    if (!e->d_cross_planes) HIP_TRY(e, hipMalloc(&e->d_cross_planes, sizeof(double) * 2 * rpf::kCrossPlanes * N));
+    return RPF_OK;
+}
+
+// Paa, Pbb, Puu, Pvv of `nframes` frames of d_a and d_b into (accumulate: added to) e->d_cross_planes, on `s`: the two
+// streams through this engine's own path, then per chunk of whole frames one combine launch over the chunk's span of
+// samples and the cf32 engine's path over u and over v, the chunks after the first adding.
+static int cross_enqueue(rpf_engine* e, const uint8_t* d_a, const uint8_t* d_b, int64_t nframes, bool accumulate, hipStream_t s)
+{
+    const size_t N = static_cast<size_t>(e->N);
+    double* const planes = e->d_cross_planes;
+    rpf_engine* const in = e->cross_inner;
+    int rc = launch_frames(e, d_a, nframes, planes, accumulate, s);
+    if (rc == RPF_OK) rc = launch_frames(e, d_b, nframes, planes + N, accumulate, s);
+    if (rc != RPF_OK) return rc;
+    float* const u = e->d_cross_uv;
+    float* const v = u + e->cross_v_offset;
+    const size_t pitch = e->sample_bytes * static_cast<size_t>(e->step);
+    for (int64_t f0 = 0; f0 < nframes; f0 += e->cross_chunk_frames) {
+        const int64_t n = std::min(e->cross_chunk_frames, nframes - f0);
+        const long samples = static_cast<long>(e->N) + static_cast<long>(e->step) * static_cast<long>(n - 1);
+        HIP_TRY(e, rpf::launch_cross_combine(d_a + static_cast<size_t>(f0) * pitch, d_b + static_cast<size_t>(f0) * pitch, samples,
+                                             e->format, u, v, s));
+        rc = launch_frames(in, reinterpret_cast<const uint8_t*>(u), n, planes + 2 * N, accumulate || f0 > 0, s);
+        if (rc == RPF_OK) rc = launch_frames(in, reinterpret_cast<const uint8_t*>(v), n, planes + 3 * N, accumulate || f0 > 0, s);
+        if (rc != RPF_OK) return in == e ? rc : fail(e, rc, in->last_error);
+    }
+    e->last_was_cross = true;
+    return RPF_OK;
+}
+
+int rpf_accumulate_device_cross(rpf_engine* e, const void* d_a, const void* d_b, size_t nbytes, int64_t repeats, double* d_out,
+                                void* hip_stream, int64_t* repeats_done)
+{
+    const std::string me = "rpf_accumulate_device_cross";
+    int rc = cross_check(e, me.c_str(), d_a, d_b, nbytes, repeats, d_out);
+    if (rc != RPF_OK) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)) & (e->sample_bytes - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_a and d_b must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_out must be 16-byte aligned");
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const int64_t nframes = std::min(frames_in(e, nbytes), repeats);
+    if (repeats_done) *repeats_done = nframes;
+    if (nframes == 0) {
+        HIP_TRY(e, hipMemsetAsync(d_out, 0, sizeof(double) * rpf::kCrossPlanes * e->N, s));
+        return RPF_OK;
+    }
+    if ((rc = ensure_cross(e)) != RPF_OK) return rc;
+    rc = cross_enqueue(e, static_cast<const uint8_t*>(d_a), static_cast<const uint8_t*>(d_b), nframes, /*accumulate=*/false, s);
+    if (rc != RPF_OK) return rc;
+    HIP_TRY(e, rpf::launch_cross_finish(e->d_cross_planes, e->N, d_out, s));
+    return RPF_OK;
+}
+
+int rpf_accumulate_cross(rpf_engine* e, const uint8_t* a, const uint8_t* b, size_t nbytes, int64_t repeats, double* out,
+                         int64_t* repeats_done)
+{
+    int rc = cross_check(e, "rpf_accumulate_cross", a, b, nbytes, repeats, out);
+    if (rc != RPF_OK) return rc;
+    const int64_t nframes = std::min(frames_in(e, nbytes), repeats);
+    if (repeats_done) *repeats_done = nframes;
+    const size_t out_doubles = rpf::kCrossPlanes * static_cast<size_t>(e->N);
+    if (nframes == 0) {
+        std::fill(out, out + out_doubles, 0.0);
+        return RPF_OK;
+    }
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = e->compute_stream;
+    if ((rc = ensure_cross(e)) != RPF_OK) return rc;
+    // pieces of whole frames, series_pieces.h's rule with L = 1: one piece of each stream at a time, side by side
+    const rpf::FrameBytes fb = frame_bytes(e);
+    const rpf::SeriesPieces p = rpf::series_pieces(fb, 1, nframes);
+    const size_t half = (p.bytes + 255) / 256 * 256;
+    if ((rc = grow_scratch(e, &e->d_series_in, &e->series_in_bytes, 2 * half, 1, s)) != RPF_OK) return rc;
+    for (int64_t k0 = 0; k0 < nframes; k0 += p.per_piece) {
+        const int64_t kc = std::min(p.per_piece, nframes - k0);
+        const size_t at = static_cast<size_t>(k0) * p.hop, span = fb.span(kc);
+        HIP_TRY(e, hipMemcpyAsync(e->d_series_in, a + at, span, hipMemcpyHostToDevice, s));
+        HIP_TRY(e, hipMemcpyAsync(e->d_series_in + half, b + at, span, hipMemcpyHostToDevice, s));
+        if ((rc = cross_enqueue(e, e->d_series_in, e->d_series_in + half, kc, /*accumulate=*/k0 > 0, s)) != RPF_OK) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        HIP_TRY(e, hipStreamSynchronize(s));
+    }
+    double* const d_result = e->d_cross_planes + out_doubles;
+    HIP_TRY(e, rpf::launch_cross_finish(e->d_cross_planes, e->N, d_result, s));
+    HIP_TRY(e, hipMemcpyAsync(out, d_result, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return RPF_OK;
 }
 
 int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
@@ -2309,6 +2472,7 @@ int rpf_last_launch_info(const rpf_engine* e, int* grid, int* block, int* frames
 {
     if (!e) return RPF_ERR_INVALID_ARGUMENT;
     if (e->inner) e = e->inner;           // a PFB engine reports its transform launch
+    if (e->last_was_cross && e->cross_inner) e = e->cross_inner;      // ... and a cross call the cf32 engine's
     if (grid) *grid = e->last.grid ? e->last.grid : e->plan.grid;
     if (block) *block = e->plan.block;
     if (frames_per_wg) *frames_per_wg = e->plan.fpw;

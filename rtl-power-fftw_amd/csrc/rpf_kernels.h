@@ -221,6 +221,14 @@ int pfb_segment_frames(int taps, int fmt);
 hipError_t launch_pfb_fold(const uint8_t* d_src, long nframes, int N, int taps, int fmt, const float* d_coeffs, float* d_z,
                            hipStream_t stream);
 
+// ---- cross-spectrum front end (rpf_cross.hip, cross_core.h) ---------------------------------------------
+// d_u = a + b and d_v = a + i b (float32 I/Q, 16-byte aligned) for the first `nsamples` complex samples of d_a and d_b
+// (format `fmt`; each a multiple of the sample's bytes, read pair by pair where it is a multiple of the pair's).
+hipError_t launch_cross_combine(const uint8_t* d_a, const uint8_t* d_b, long nsamples, int fmt, float* d_u, float* d_v,
+                                hipStream_t stream);
+// d_out[4 x N] = the finishing expression of include/rpf_engine.h over d_planes[4 x N] = Paa, Pbb, Puu, Pvv (not in place).
+hipError_t launch_cross_finish(const double* d_planes, int N, double* d_out, hipStream_t stream);
+
 // Master twiddle table W_N^k = exp(-2 pi i k / N), k in [0,N), evaluated in
 // long double and rounded once to float.
 void make_twiddles(int N, std::vector<cf>& out);

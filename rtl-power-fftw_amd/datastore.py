@@ -258,6 +258,32 @@ class Datastore:
             ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(hip_stream), ctypes.byref(done)))
         return done.value
 
+    # -- cross-spectrum of two streams (rpf_accumulate[_device]_cross; include/rpf_engine.h has the definition) -------
+    def accumulate_device_cross(self, d_a_ptr, d_b_ptr, nbytes, repeats, d_out_ptr, hip_stream=0):
+        """rpf_accumulate_device_cross: two streams of nbytes each resident in HBM, d_out = 4 x N device doubles (Saa,
+        Sbb, Re Sab, Im Sab); asynchronous.  Returns the number of frames that will be summed."""
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_accumulate_device_cross(
+            self._handle, ctypes.c_void_p(d_a_ptr), ctypes.c_void_p(d_b_ptr), nbytes, repeats,
+            ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(hip_stream), ctypes.byref(done)))
+        return done.value
+
+    def accumulate_cross(self, a, b, repeats=None):
+        """rpf_accumulate_cross: the same on two host streams of equal length (not through the buffer queues).  Returns
+        ((4, N) array: Saa, Sbb, Re Sab, Im Sab; frames); stats.coherence and stats.cross_phase take the array.
+        repeats None = every whole frame the streams hold."""
+        a, b = _as_bytes(a), _as_bytes(b)
+        if a.size != b.size:
+            raise RPFError("accumulate_cross: the two streams must have the same length; got %d and %d bytes."
+                           % (a.size, b.size), ReturnValue.InvalidArgument)
+        out = np.zeros((4, self.params.N), dtype=np.float64)
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_accumulate_cross(
+            self._handle, ctypes.c_void_p(a.ctypes.data), ctypes.c_void_p(b.ctypes.data), a.size,
+            (1 << 62) if repeats is None else repeats,
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(done)))
+        return out, done.value
+
     def accumulate_device_series(self, d_stream_ptr, nbytes, frames_per_spectrum, max_spectra, d_out_ptr, hip_stream=0):
         """rpf_accumulate_device_series: consecutive spectra of `frames_per_spectrum` frames of a stream resident in
         HBM, row k of d_out (K x N device doubles) = frames [k L, (k + 1) L); asynchronous.  Returns K."""

@@ -262,6 +262,39 @@ void write_spectrum_text_quantiles(std::ostream& out, const std::vector<double>&
     out.flush();
 }
 
+void write_text_header_cross(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp)
+{
+    out << "# rtl-power-fftw output" << std::endl;
+    out << "# Acquisition start: " << start_stamp << std::endl;
+    out << "# Acquisition end: " << end_stamp << std::endl;
+    out << "#" << std::endl;
+    out << "# frequency [Hz] power spectral density a [dB/Hz] power spectral density b [dB/Hz] coherence phase [rad]"
+        << std::endl;
+}
+
+void write_spectrum_text_cross(std::ostream& out, const std::vector<double>& planes, int N, int64_t frames, int64_t tuned_freq,
+                               int samplerate, bool linear, const std::vector<double>* baseline)
+{
+    // the DC bin of each of the four planes is the mean of its neighbours; coherence and phase come from those
+    std::vector<std::vector<double>> plane(4);
+    for (size_t c = 0; c < 4; ++c) {
+        plane[c].assign(planes.begin() + c * N, planes.begin() + (c + 1) * N);
+        interpolate_dc(plane[c], N);
+    }
+    const int freq_digits = static_cast<int>(
+        std::ceil(std::floor(std::log10(static_cast<double>(tuned_freq))) - std::log10(samplerate / N) + 1 + 2));
+    for (int i = 0; i < N; ++i) {
+        const double freq = tuned_freq + (i - N / 2.0) * samplerate / N;
+        out << std::setprecision(freq_digits) << freq << " " << std::setprecision(6)
+            << bin_value(plane[0], i, N, frames, samplerate, linear, baseline) << " "
+            << bin_value(plane[1], i, N, frames, samplerate, linear, baseline) << " "
+            << coherence(plane[0][i], plane[1][i], plane[2][i], plane[3][i]) << " " << cross_phase(plane[2][i], plane[3][i])
+            << std::endl;
+    }
+    out << std::endl;
+    out.flush();
+}
+
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,
                          const std::vector<double>* baseline, std::vector<float>& row)
 {

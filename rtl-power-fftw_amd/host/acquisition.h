@@ -123,6 +123,13 @@ void write_text_header_quantiles(std::ostream& out, const std::string& start_sta
 void write_spectrum_text_quantiles(std::ostream& out, const std::vector<double>& planes, const std::vector<double>& q, int N,
                                    int64_t L, int64_t tuned_freq, int samplerate, bool linear,
                                    const std::vector<double>* baseline);
+// --cross: the header, whose last line names the five columns, and the block.  planes[4 x N] = Saa, Sbb, Re Sab, Im Sab
+// over `frames` frames (rpf_accumulate_cross); the DC bin of each of the four is the mean of its neighbours, then the
+// two power columns go / frames / N / samplerate, dB and baseline as always, and coherence (dimensionless: never dB, no
+// baseline, "nan" where undefined) and phase [rad] are derived from the four (datastore.h: coherence, cross_phase).
+void write_text_header_cross(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp);
+void write_spectrum_text_cross(std::ostream& out, const std::vector<double>& planes, int N, int64_t frames, int64_t tuned_freq,
+                               int samplerate, bool linear, const std::vector<double>* baseline);
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,
                          const std::vector<double>* baseline, std::vector<float>& row);
 // Matrix mode: append one float32 row to options.bin_file and keep the row/column

@@ -122,6 +122,16 @@ inline void sk_limits(int64_t M, double sigma, double& lo, double& hi) {
   hi = 1.0 + d;
 }
 
+// The magnitude-squared coherence of two streams from one bin of the four planes of rpf_accumulate_cross (Saa, Sbb,
+// Re Sab, Im Sab): (re^2 + im^2) / (Saa Sbb), in double, in exactly this order of operations (stats.py's coherence does
+// the same ones); NaN where Saa Sbb = 0; not clamped.  And arg Sab in radians (stats.py's cross_phase).
+inline double coherence(double saa, double sbb, double re, double im) {
+  const double den = saa * sbb;
+  if (den == 0.0) return std::nan("");
+  return (re * re + im * im) / den;
+}
+inline double cross_phase(double re, double im) { return std::atan2(im, re); }
+
 // A filled/empty hand-off buffer: what `Buffer&` is in acquisition.cxx:283,302-304
 // (data()/size()/resize()), backed by engine-owned pinned memory.
 class Buffer {
@@ -273,6 +283,23 @@ public:
     int64_t done = 0;
     check(rpf_accumulate_device_excised(engine_, d_stream, nbytes, frames_per_spectrum, max_spectra, sk_lo, sk_hi, d_out,
                                         d_mask, hip_stream, &done));
+    return done;
+  }
+  // Cross-spectrum of two host streams of nbytes each (rpf_accumulate_cross; include/rpf_engine.h has the definition):
+  // `planes` (resized to 4 x N) = Saa, Sbb, Re Sab, Im Sab over the first min(repeats, frames) frames; coherence and
+  // cross_phase above take one bin of them.  Not through the buffer queues: pwr and repeats_done stay.  Returns the frames.
+  int64_t accumulate_cross(const uint8_t* a, const uint8_t* b, size_t nbytes, int64_t repeats, std::vector<double>& planes) {
+    planes.assign(static_cast<size_t>(4) * params.N, 0.0);
+    int64_t done = 0;
+    check(rpf_accumulate_cross(engine_, a, b, nbytes, repeats, planes.data(), &done));
+    return done;
+  }
+  // The same on two streams resident in HBM (rpf_accumulate_device_cross): d_out = 4 x N device doubles, asynchronous
+  // on hip_stream.
+  int64_t accumulate_device_cross(const void* d_a, const void* d_b, size_t nbytes, int64_t repeats, double* d_out,
+                                  void* hip_stream = nullptr) {
+    int64_t done = 0;
+    check(rpf_accumulate_device_cross(engine_, d_a, d_b, nbytes, repeats, d_out, hip_stream, &done));
     return done;
   }
   // Per-bin quantiles of the integrations (rpf_quantile_*; include/rpf_engine.h has the definition): the engine keeps the

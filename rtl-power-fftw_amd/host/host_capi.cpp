@@ -236,6 +236,28 @@ void rpf_host_spectral_kurtosis(const double* s1, const double* s2, long long M,
     for (int i = 0; i < n; ++i) out[i] = spectral_kurtosis(s1[i], s2[i], M);
 }
 
+// datastore.h's coherence and cross_phase over planes[4 x n] = Saa, Sbb, Re Sab, Im Sab, element by element.
+void rpf_host_coherence(const double* planes, int n, double* out)
+{
+    for (int i = 0; i < n; ++i) out[i] = coherence(planes[i], planes[n + i], planes[2 * n + i], planes[3 * n + i]);
+}
+
+void rpf_host_cross_phase(const double* planes, int n, double* out)
+{
+    for (int i = 0; i < n; ++i) out[i] = cross_phase(planes[2 * n + i], planes[3 * n + i]);
+}
+
+// The --cross writer (write_spectrum_text_cross) over planes[4 x N].
+long rpf_host_format_text_cross(const double* planes, int N, long long frames, long long tuned_freq, int samplerate,
+                                int linear, const double* baseline, char* out, size_t cap)
+{
+    std::vector<double> p(planes, planes + 4 * static_cast<size_t>(N)), b;
+    if (baseline) b.assign(baseline, baseline + N);
+    std::ostringstream os;
+    write_spectrum_text_cross(os, p, N, frames, tuned_freq, samplerate, linear != 0, baseline ? &b : nullptr);
+    return copy_out(os.str(), out, cap);
+}
+
 void rpf_host_format_matrix(double* pwr, int N, long long repeats_done, int samplerate, int linear,
                             const double* baseline, float* row_out)
 {

@@ -85,6 +85,11 @@ const Spec kSpecs[] = {
      "Polyphase filter bank front end: every frame is <taps> x bins samples weighted by a windowed-sinc prototype and "
      "folded to <bins> before the FFT, 1 <= taps <= 32 (not with -w, --frame-overlap, --stats, --series, --series-stats, "
      "--excise or several --gpus)."},
+    {0, "cross", Kind::Text, "file",
+     "Cross-spectrum of --input (stream a) and <file> (stream b, same format, sample rate and tuning): one block with the "
+     "power of a, the power of b, the magnitude-squared coherence and the phase of the cross-spectrum [rad] over the whole "
+     "frames of the shorter file (not with a frequency range, -n, -t, -c, -e, -m, --stats, --series, --series-stats, "
+     "--excise, --quantile, --pfb or several --gpus)."},
     {0, "reduce", Kind::Text, "rccl|host", "With --gpus: where a scan's per-device spectra are added (default: rccl if it loads, else host)."},
     {'h', "help", Kind::Flag, "", "Displays usage information and exits."},
     {0, "version", Kind::Flag, "", "Displays version information and exits."},
@@ -461,6 +466,24 @@ Options parse_command_line(int argc, const char* const* argv)
                          "): the integration length is its own argument and the replay is read once.");
         if (o.matrixMode) conflict("does not combine with -m (matrix mode): the quantiles are columns of one text block.");
         if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
+    }
+    if (p.has("cross")) {
+        o.cross_file = p.get("cross");
+        auto conflict = [](const std::string& what) {
+            throw RPFexception("Option --cross " + what + " Exiting.", ReturnValue::InvalidArgument);
+        };
+        if (!p.has("input")) conflict("needs --input: that is stream a, and the file given here stream b.");
+        if (o.cross_file == "-" && p.get("input") == "-") conflict("cannot read both streams from stdin.");
+        for (const char* name : {"repeats", "time", "continue", "elapsed"})
+            if (p.has(name))
+                conflict(std::string("does not combine with --") + name + " (-" + find_spec(std::string("--") + name)->short_name +
+                         "): the two replays are read once, to the end of the shorter.");
+        if (o.freq_hopping_isSet) conflict("does not combine with a frequency range in -f: a replay is one stream.");
+        if (o.matrixMode) conflict("does not combine with -m (matrix mode): the cross-spectrum is one text block.");
+        if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
+        for (const char* name : {"stats", "series", "series-stats", "excise", "quantile", "pfb"})
+            if (p.has(name))
+                conflict(std::string("does not combine with --") + name + ": cross-spectra of those are not built.");
     }
     if (p.has("input")) o.input_file = p.get("input");
     o.synthetic = p.has("synthetic");

@@ -489,6 +489,51 @@ int run_quantile(const Options& options, AuxData& aux, int actual_samplerate, in
     return 0;
 }
 
+// --input a --cross b: the cross-spectrum of the two replays (rpf_accumulate_cross) over the whole frames of the shorter,
+// ONE block for the pair: power of a, power of b, coherence, phase.  Both files are read in pieces of whole frames
+// (piece_reader.h with one frame per integration), a piece of each at a time; every pair of pieces leaves its four
+// planes -- sums over its frames, so the pieces' planes are added here in file order.
+int run_cross(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
+{
+    Datastore data(options, aux.window_values);
+    const int64_t b = options.sample_bytes();
+    PieceReader in_a(options.input_file, b * options.N, b * options.step(), 1);
+    PieceReader in_b(options.cross_file, b * options.N, b * options.step(), 1);
+    const size_t N = static_cast<size_t>(options.N);
+    std::vector<double> piece, planes(4 * N, 0.0);
+    int64_t frames = 0;
+    size_t left_a = 0, left_b = 0;
+    set_CtrlC_handler(true);
+    const std::string start_stamp = Acquisition::utc_now();
+    while (!checkInterrupt(InterruptState::FinishNow)) {
+        left_a = in_a.fill();
+        left_b = in_b.fill();
+        const size_t have = std::min(left_a, left_b) / static_cast<size_t>(b) * static_cast<size_t>(b);
+        const int64_t done = data.accumulate_cross(in_a.data(), in_b.data(), have, in_a.per_piece(), piece);
+        if (done == 0) break;
+        for (size_t i = 0; i < 4 * N; ++i) planes[i] += piece[i];
+        frames += done;
+        const bool more_a = in_a.consume(done), more_b = in_b.consume(done);
+        if (!more_a || !more_b) {
+            left_a = in_a.fill();
+            left_b = in_b.fill();
+            break;
+        }
+    }
+    if (frames == 0)
+        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+    const std::string end_stamp = Acquisition::utc_now();
+    write_text_header_cross(std::cout, start_stamp, end_stamp);
+    write_spectrum_text_cross(std::cout, planes, options.N, frames, tuned_freq, actual_samplerate, options.linear,
+                              options.baseline ? &aux.baseline_values : nullptr);
+    std::cout << std::endl;          // (the blank line that closes a pass)
+    // what is left of each file once the last common frame is taken: the same unless the lengths differ
+    std::cerr << "Cross-spectrum: " << frames << " frames of " << options.N << " bins from each stream"
+              << (left_a != left_b ? " (the files differ in length: the whole frames of the shorter are used)" : "") << std::endl;
+    if (chatty(options)) print_acquisition_summary(options.N, frames, 0, 0, actual_samplerate);
+    return 0;
+}
+
 int run(int argc, char** argv)
 {
     Options options = parse_command_line(argc, argv);
@@ -538,6 +583,7 @@ int run(int argc, char** argv)
     Plan plan(options, actual_samplerate);
     plan.print();
 
+    if (!options.cross_file.empty()) return run_cross(options, aux, actual_samplerate, source->frequency());
     if (options.quantile_frames > 0) return run_quantile(options, aux, actual_samplerate, source->frequency());
     if (options.excise_frames > 0) return run_excise(options, aux, actual_samplerate, source->frequency());
     if (options.series_frames > 0) return run_series(options, aux, actual_samplerate, source->frequency());

@@ -56,6 +56,31 @@ def excise(rows, L, sk_lo, sk_hi):
     return out, (~keep).astype(np.uint8)
 
 
+def coherence(planes):
+    """The magnitude-squared coherence of include/rpf_engine.h (rpf_accumulate_device_cross) from the (4, N) planes Saa,
+    Sbb, Re Sab, Im Sab:  (re^2 + im^2) / (Saa Sbb), in double in exactly this order (the C++ host's coherence,
+    host/datastore.h, does the same operations).  NaN where Saa Sbb == 0; not clamped: rounding can put it a few 1e-7
+    above 1.  Of M frames it is a biased estimate: identically 1 for M = 1, about 1/M for unrelated streams."""
+    p = np.asarray(planes, dtype=np.float64)
+    if p.shape[0] != 4:
+        raise ValueError("coherence: planes must be (4, N)")
+    den = p[0] * p[1]
+    num = p[2] * p[2] + p[3] * p[3]
+    out = np.full(den.shape, np.nan)
+    ok = den != 0.0
+    with np.errstate(invalid="ignore", over="ignore"):
+        out[ok] = num[ok] / den[ok]
+    return out
+
+
+def cross_phase(planes):
+    """arg Sab = atan2(Im Sab, Re Sab) in radians, from the same (4, N) planes (host/datastore.h: cross_phase)."""
+    p = np.asarray(planes, dtype=np.float64)
+    if p.shape[0] != 4:
+        raise ValueError("cross_phase: planes must be (4, N)")
+    return np.arctan2(p[3], p[2])
+
+
 def quantiles(rows, q):
     """The per-bin quantiles of include/rpf_engine.h (rpf_quantile_select_device) stated in numpy, on (K, N) rows: with
     v_(0) <= ... <= v_(K-1) the values of a bin in np.sort's order (a NaN last), h = q (K - 1), j = floor(h), g = h - j,
