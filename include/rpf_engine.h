@@ -40,7 +40,8 @@ extern "C" {
                                rpf_engine_create_pfb, rpf_pfb_taps;
                                rpf_quantile_reset, rpf_quantile_append_device, rpf_quantile_append,
                                rpf_quantile_select_device, rpf_quantile_select, rpf_quantile_rows, rpf_quantile_max_rows;
-                               rpf_accumulate_device_cross, rpf_accumulate_cross */
+                               rpf_accumulate_device_cross, rpf_accumulate_cross;
+                               rpf_stft_device, rpf_stft */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -317,6 +318,44 @@ int rpf_accumulate_device_cross(rpf_engine* e, const void* d_a, const void* d_b,
                                 double* d_out /* 4 x N */, void* hip_stream, int64_t* repeats_done);
 int rpf_accumulate_cross(rpf_engine* e, const uint8_t* a, const uint8_t* b, size_t nbytes, int64_t repeats,
                          double* out /* 4 x N, host */, int64_t* repeats_done);
+
+/* Short-time Fourier transform: the complex spectrum of every frame, where every other entry ends in a sum of |X|^2.
+ * Everything that computes or checks it refers to this definition.
+ *   Frames.  F = min(max_frames, rpf_frames_in(e, nbytes)), max_frames >= 0; frame f starts at byte f b S of the stream (the
+ *     engine's frame step; on a PFB engine frame f is the fold of the input frames f .. f + T - 1).
+ *   Rows.  Row f is d_out[f N .. f N + N), interleaved float32 (re, im): F x N x 2 floats.  Rows < F are overwritten, rows
+ *     >= F are not touched.  F = 0 makes no launch and is RPF_OK.  *frames_done = F (may be NULL).
+ *   Values.  Row f is THE FLOAT32 TRANSFORM OF FRAME f EXACTLY AS THIS ENGINE COMPUTES IT BEFORE IT SQUARES: the engine's
+ *     sample format converted exactly; (-1)^n and the window applied as one rounding; forward and unnormalised, so bin N/2
+ *     is DC; on a PFB engine the folded frames.
+ *   The tie to the power.  With re and im of a row converted to double, re re + im im (both squares are exact in double,
+ *     so one rounding) is bit for bit what rpf_accumulate_device of the same engine writes for that frame alone (repeats =
+ *     1, the pointer at the frame), on either staging route and on both kernel routes: the power kernels add
+ *     fma(im, im, re re) to zero and every later addition adds zeros.  (An engine whose power comes from another family
+ *     -- mixed radix, four-step -- is tied to the power of the catch-all engine of its configuration, whose rows it gives.)
+ *   Routes.  N = 64 .. 8192 (the K1 sizes), any format, window, frame step and staging: K1's store kernels
+ *     (csrc/k1_stft_body.inc), one launch; rpf_last_launch_info reports it.  Every other power of two up to 2^26, and any
+ *     size with RPF_FLAG_CATCH_ALL: the catch-all Stockham transform, whatever family serves the size for power, in
+ *     batches of frames, its last pass writing straight into the rows (no copy, no further kernel); overlapped frames go
+ *     through the frame gather first.  An engine of another family creates its catch-all twin at the first call, as the
+ *     cross entries create their cf32 engine.  A PFB engine: the fold per chunk of scratch, then the inner cf32 engine's
+ *     route over the folded frames into the chunk's rows -- the channelizer.
+ *   Nothing of the engine's state moves: queues, pwr, repeats_done, statistics, the quantile row store and the cross scratch
+ *     stay as they are, and an engine that never calls these entries allocates nothing for them.
+ * rpf_stft_device puts every launch on `hip_stream` and returns without synchronising; the stream follows
+ * rpf_accumulate_device's rules (address a multiple of b; 16-byte aligned streams take the LDS-DMA route, other alignments
+ * VGPR staging); d_out is 16-byte aligned.  rpf_stft is the same on a host stream into host rows: the stream moves through
+ * engine-owned device memory in pieces of whole frames, as many as keep BOTH the input span and the rows (8 N bytes per
+ * frame) within 64 MB and at least one (csrc/series_pieces.h, stft_pieces); it synchronises before it returns and
+ * *frames_done counts the rows that came back.
+ * RPF_ERR_INVALID_ARGUMENT, before any launch and with the output untouched: a NULL argument; N not a power of two
+ * (Bluestein's spectrum lacks the final chirp, which |.|^2 discards); an engine created with RPF_FLAG_BIN_STATS; a kernel
+ * variant other than 0; a running acquisition; max_frames < 0; nbytes or a stream address that is no multiple of b; d_out
+ * not 16-byte aligned. */
+int rpf_stft_device(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t max_frames,
+                    void* d_out /* F x N x (float re, float im) */, int64_t* frames_done, void* hip_stream);
+int rpf_stft(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t max_frames,
+             void* out /* host, F x N x 2 floats */, int64_t* frames_done);
 
 /* The two halves of rpf_accumulate_device as separate enqueues, so that a
  * benchmark can bracket the dominant kernel alone with events on `hip_stream`:

@@ -12,6 +12,7 @@
 #include "rpf_device_common.h"
 #include "rpf_kernels.h"
 #include "series_partition.h"
+#include "stft_core.h"
 
 namespace rpf {
 
@@ -236,12 +237,41 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_series_stats_kernel(const c
 #include "k1_scan_body.inc"
 }
 
+// ---- K1, the frames' spectra themselves (rpf_stft_device) ------------------------------------
+// The plain kernel's frame loop with the spectrum stored where the plain kernel squares it: row f of `out` = the N
+// float32 (re, im) of frame f in natural bin order (k1_stft_body.inc, stft_core.h).  The template arguments are the plain
+// kernels' without the accumulate ones; one exchange slab per frame slot.  Kernels of their own names, instantiated in
+// rpf_kernels_stft*.hip only: no other kernel moves.
+typedef float stft_pair_t __attribute__((ext_vector_type(4)));   // two neighbouring bins: one 16-byte LDS read and store
+
+template <class G, int WG, int OCC, bool WINDOW, bool DMA, int RAWD = 2, bool TWLDS = false, int FMT = kFmtCu8>
+__global__ __launch_bounds__(WG, OCC) void fft_stft_kernel(const uint8_t* __restrict__ stream, long nframes,
+                                                           const cf* __restrict__ twN,
+                                                           const float* __restrict__ window, cf* __restrict__ out)
+{
+    constexpr bool STRIDED = false;
+    constexpr long pitch = static_cast<long>(sample_bytes_of(FMT)) * G::N;     // (named by the discarded strided branches only)
+#include "k1_stft_body.inc"
+}
+
+template <class G, int WG, int OCC, bool WINDOW, bool DMA, int RAWD = 2, bool TWLDS = false, int FMT = kFmtCu8>
+__global__ __launch_bounds__(WG, OCC) void fft_stft_strided_kernel(const uint8_t* __restrict__ stream, long nframes,
+                                                                   long pitch, const cf* __restrict__ twN,
+                                                                   const float* __restrict__ window,
+                                                                   cf* __restrict__ out)
+{
+    constexpr bool STRIDED = true;
+#include "k1_stft_body.inc"
+}
+
 }  // namespace
 
 using SingleFn = void (*)(const uint8_t*, long, const cf*, const float*, double*);
 using ScanFn = void (*)(const cf*, const float*, double*, const HopArgs);
 using StridedFn = void (*)(const uint8_t*, long, long, const cf*, const float*, double*);
 using SeriesFn = void (*)(const cf*, const float*, double*, const SeriesArgs);
+using StftFn = void (*)(const uint8_t*, long, const cf*, const float*, cf*);
+using StftStridedFn = void (*)(const uint8_t*, long, long, const cf*, const float*, cf*);
 
 // One geometry of one size and the kernels instantiated for it, each as [window][dma]; a unit leaves the kernels it
 // does not instantiate null (K1Kernels).
@@ -253,6 +283,8 @@ struct Variant {
     ScanFn scan[2][2];       // several hops per launch
     StridedFn strided[2][2]; // one acquisition of overlapped frames (frame pitch a kernel argument)
     SeriesFn series[2][2];   // a uniform series of spectra per launch (kK1SeriesStats: of three-plane statistics)
+    StftFn stft[2][2];       // the frames' spectra themselves, frames side by side (kK1Stft only)
+    StftStridedFn stft_strided[2][2];   // ... of overlapped frames
 };
 
 // Variant 0 of every K1 size, one finder per translation unit so that the units compile side by side; each answers
@@ -270,6 +302,9 @@ struct Variant {
 //   k1_series_stats_variant      rpf_kernels_series_stats.hip      cu8, cs8, cs16, and cf32 by way of the next
 //                                                                             series with per-bin statistics
 //   k1_series_stats_cf32_variant rpf_kernels_series_stats_cf32.hip cf32       series with per-bin statistics
+//   k1_stft_variant              rpf_kernels_stft.hip              cu8        stft, stft_strided
+//   k1_stft_format_variant       rpf_kernels_stft_formats.hip      cs8, cs16  stft, stft_strided
+//   k1_stft_cf32_variant         rpf_kernels_stft_cf32.hip         cf32       stft, stft_strided
 const Variant* k1_variant(int N, int fmt);
 const Variant* k1_format_variant(int N, int fmt);
 const Variant* k1_cf32_variant(int N, int fmt);
@@ -279,6 +314,9 @@ const Variant* k1_stats_cf32_variant(int N, int fmt);
 const Variant* k1_series_variant(int N, int fmt);
 const Variant* k1_series_stats_variant(int N, int fmt);
 const Variant* k1_series_stats_cf32_variant(int N, int fmt);
+const Variant* k1_stft_variant(int N, int fmt);
+const Variant* k1_stft_format_variant(int N, int fmt);
+const Variant* k1_stft_cf32_variant(int N, int fmt);
 
 // The resident grid of kernels that share one launch geometry on `device`: for each kernel (null entries skipped) the
 // dynamic-LDS attribute is set and its occupancy asked; *grid = max(the smallest, 1) x CUs.  rpf_kernels.hip.
@@ -304,8 +342,9 @@ namespace {
 
 // The kernels a Variant names: kK1Plain single, scan and strided; kK1Stats single and strided with STATS (a scan of
 // a stats engine runs hop by hop); kK1Series the series kernel alone, with the geometry of the size's scan kernel;
-// kK1SeriesStats the series kernel with statistics alone, with the geometry of the size's statistics kernels.
-enum K1Kernels { kK1Plain, kK1Stats, kK1Series, kK1SeriesStats };
+// kK1SeriesStats the series kernel with statistics alone, with the geometry of the size's statistics kernels;
+// kK1Stft the two store kernels alone, with the geometry of the size's plain kernels.
+enum K1Kernels { kK1Plain, kK1Stats, kK1Series, kK1SeriesStats, kK1Stft };
 
 // the [window][dma] instantiations of one kernel template; the arguments are its template arguments after TWLDS
 #define RPF_K1_FORMS(KERNEL, ...)                                                             \
@@ -313,6 +352,13 @@ enum K1Kernels { kK1Plain, kK1Stats, kK1Series, kK1SeriesStats };
       KERNEL<G, WG, OCC, false, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, __VA_ARGS__>},       \
      {KERNEL<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, __VA_ARGS__>,      \
       KERNEL<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, __VA_ARGS__>}}
+
+// ... of a store kernel, whose template arguments are the plain kernels' without the accumulate ones
+#define RPF_K1_STFT_FORMS(KERNEL)                                                \
+    {{KERNEL<G, WG, OCC, false, false, RAWD, TWLDS, FMT>,                         \
+      KERNEL<G, WG, OCC, false, true, RAWD, TWLDS, FMT>},                         \
+     {KERNEL<G, WG, OCCW, true, false, RAWD, TWLDSW, FMT>,                        \
+      KERNEL<G, WG, OCCW, true, true, RAWD, TWLDSW, FMT>}}
 
 // The template arguments are K1Size's (k1_sizes.h) and the kernels' (above).  vid = tuning variant (0 = the default
 // for this N).
@@ -324,7 +370,10 @@ Variant make_variant(int vid)
     using G = Geom<N, P>;
     constexpr K1Geometry geo = k1_geometry<G>(WGO, DBUF ? 2 : 1, RAWD, FMT, TWLDS || TWLDSW);
     constexpr int WG = geo.WG;
-    if constexpr (KERNELS == kK1Series)
+    if constexpr (KERNELS == kK1Stft)
+        return Variant{N, vid, P, geo, PF32, {}, {}, {}, {}, RPF_K1_STFT_FORMS(fft_stft_kernel),
+                       RPF_K1_STFT_FORMS(fft_stft_strided_kernel)};
+    else if constexpr (KERNELS == kK1Series)
         return Variant{N, vid, P, geo, PF32, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_kernel, FMT)};
     else if constexpr (KERNELS == kK1SeriesStats)
         return Variant{N, vid, P, geo, PF32, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_stats_kernel, FMT)};
@@ -336,6 +385,7 @@ Variant make_variant(int vid)
                        RPF_K1_FORMS(fft_accum_scan_kernel, FMT), RPF_K1_FORMS(fft_accum_strided_kernel, FMT, false), {}};
 }
 #undef RPF_K1_FORMS
+#undef RPF_K1_STFT_FORMS
 
 // Variant 0 of every row of the size table for one sample format and one set of kernels, and its look-up by N.
 template <K1Kernels KERNELS, int FMT, int I>

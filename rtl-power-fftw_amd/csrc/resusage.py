@@ -23,4 +23,7 @@ for l in sys.stdin:
                 tag = 'cross_combine fmt=%s aligned_a=%s aligned_b=%s' % f.groups()
             elif 'cross_finish_kernel' in cur:
                 tag = 'cross_finish'
+            f = re.search(r'fft_stft(_strided)?_kernelINS_4GeomILi(\d+)ELi(\d+)EEELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELi(\d+)ELb(\d)ELi(\d+)E', cur)
+            if f:
+                tag = 'stft%s N=%s P=%s WG=%s OCC=%s win=%s dma=%s rawd=%s twlds=%s fmt=%s' % ((f.group(1) or '',) + f.groups()[1:])
             print(tag, {k: d.get(k) for k in ('VGPRs', 'AGPRs', 'ScratchSize', 'Occupancy', 'VGPRs Spill')})

@@ -186,6 +186,14 @@ struct rpf_engine {
     int64_t cross_chunk_frames = 0;       // ... frames a chunk holds (as many as span at most kGatherBytes, at least one)
     double* d_cross_planes = nullptr;     // Paa, Pbb, Puu, Pvv, then the host entry's four output planes: 8 N doubles
     bool last_was_cross = false;          // the last transform launched was a cross call's: rpf_last_launch_info reports cross_inner's
+    // the frames' spectra themselves (rpf_stft_device, rpf_stft); everything made at the first call that needs it
+    bool stft_planned = false;
+    rpf::LaunchInfo stft_plan;            // K1: the store kernels' resident grid
+    rpf_engine* stft_inner = nullptr;     // a family other than K1 and the catch-all: the catch-all engine of the same
+                                          // N, window, frame step, format, device and staging flag
+    float* d_stft_rows = nullptr;         // rpf_stft: the rows of one piece
+    size_t stft_rows = 0;                 // ... rows (of 2 N floats) it holds
+    bool last_was_stft = false;           // the last transform launched was an STFT call's on stft_inner
 
     mutable std::string last_error;
 };
@@ -525,6 +533,7 @@ int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes,
 {
     if (e->fused && !slot_verdict) note_device_path_aborts(e);
     e->last_was_cross = false;
+    e->last_was_stft = false;
     int nslots = 0;
     int rc = launch_transform(e, d_frames, nframes, stream, &nslots);
     if (rc != RPF_OK) return rc;
@@ -913,6 +922,12 @@ void release_device(rpf_engine* e)
         delete e->cross_inner;
     }
     e->cross_inner = nullptr;
+    (void)hipFree(e->d_stft_rows);
+    if (e->stft_inner) {
+        release_device(e->stft_inner);
+        delete e->stft_inner;
+        e->stft_inner = nullptr;
+    }
     for (auto& s : e->staging) {
         if (s.base) (void)hipFree(s.base);
         if (s.kernel_done) (void)hipEventDestroy(s.kernel_done);
@@ -1810,6 +1825,183 @@ int rpf_accumulate_cross(rpf_engine* e, const uint8_t* a, const uint8_t* b, size
     return RPF_OK;
 }
 
+// ---- the frames' spectra themselves: rpf_stft_device, rpf_stft (include/rpf_engine.h has the definition) -------------
+
+// Everything both entries refuse, before any launch.
+static int stft_check(rpf_engine* e, const char* who, const void* stream, size_t nbytes, int64_t max_frames, const void* out)
+{
+    const std::string me = who;
+    if (!e || !out || !stream) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+    if (e->N & (e->N - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": the number of bins must be a power of two (Bluestein's spectrum lacks its final chirp); got " +
+                        std::to_string(e->N));
+    if (e->stats) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not on an engine created with RPF_FLAG_BIN_STATS");
+    if (e->variant != 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not with a kernel variant other than 0");
+    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": acquisition running");
+    if (max_frames < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": max_frames must not be negative");
+    if (nbytes % e->sample_bytes)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": nbytes must be a multiple of the sample size (" + std::to_string(e->sample_bytes) + " bytes)");
+    return RPF_OK;
+}
+
+// K1's store kernels serve every K1 engine the checks let through.
+static bool stft_native(const rpf_engine* e) { return is_k1(e) && rpf::stft_supported(e->N, e->format); }
+
+// What the engine's route needs, made at the first call: the store kernels' grid, or the catch-all engine of a family
+// that is neither K1 nor the catch-all, or (PFB) the fold's scratch and what the inner engine's route needs.
+static int ensure_stft(rpf_engine* e)
+{
+    if (e->taps) {
+        if (!e->d_pfb_z) {
+            const size_t zframe = sizeof(float) * 2 * static_cast<size_t>(e->N);
+            e->pfb_chunk_frames = std::max<int64_t>(1, static_cast<int64_t>(rpf::kGatherBytes / zframe));
+            HIP_TRY(e, hipMalloc(&e->d_pfb_z, static_cast<size_t>(e->pfb_chunk_frames) * zframe));
+        }
+        const int rc = ensure_stft(e->inner);
+        return rc == RPF_OK ? rc : fail(e, rc, e->inner->last_error);
+    }
+    if (stft_native(e)) {
+        if (!e->stft_planned) {
+            HIP_TRY(e, rpf::plan_stft(e->N, e->has_window, e->device, &e->stft_plan, e->format));
+            e->stft_planned = true;
+        }
+        return RPF_OK;
+    }
+    if (e->family == rpf::Family::Generic || e->stft_inner) return RPF_OK;
+    rpf_config icfg;
+    icfg.struct_size = sizeof(icfg);
+    icfg.N = e->N;
+    icfg.window = e->window.empty() ? nullptr : e->window.data();
+    icfg.n_buffers = 1;
+    icfg.buffer_capacity = 8;
+    icfg.device = e->device;
+    icfg.flags = (e->flags & (RPF_FLAG_NO_LDS_DMA | RPF_FLAG_SAMPLE_FORMAT(0xf))) | RPF_FLAG_CATCH_ALL;
+    icfg.frame_step = e->step;
+    const int rc = create_engine(&icfg, nullptr, /*inner_of_pfb=*/true, &e->stft_inner);
+    return rc == RPF_OK ? rc : fail(e, rc, g_last_error);
+}
+
+// One launch of the plain or (frame step != N) the strided store kernel: rows [0, nframes) of d_out.
+static int transform_stft_k1(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, rpf::cf* d_out, hipStream_t s)
+{
+    const int64_t wanted = (nframes + e->stft_plan.fpw - 1) / e->stft_plan.fpw;
+    const int grid = static_cast<int>(std::min<int64_t>(e->stft_plan.grid, wanted));
+    const long pitch = static_cast<long>(e->sample_bytes) * e->step;
+    const bool dma = e->use_dma && (reinterpret_cast<uintptr_t>(d_frames) % 16) == 0 && pitch % 16 == 0;
+    HIP_TRY(e, rpf::launch_fft_stft(e->N, e->has_window, dma, d_frames, nframes, e->d_twiddles, e->d_window, d_out, grid, s,
+                                    &e->last, pitch, e->format));
+    return RPF_OK;
+}
+
+// The catch-all engine's Stockham transform with the rows as its last pass's destination (rpf_generic.hip), in batches
+// of generic_batch(N) frames; overlapped frames go through the frame gather first, a chunk of scratch at a time.
+static int transform_stft_generic(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, rpf::cf* d_out, hipStream_t s)
+{
+    const size_t frame = e->sample_bytes * static_cast<size_t>(e->N);
+    auto rows = [&](const uint8_t* side_by_side, int64_t n, rpf::cf* d_rows) {
+        HIP_TRY(e, rpf::launch_generic(e->N, side_by_side, n, e->d_window, e->d_chirp, e->d_bhat, e->d_tw_sub, e->d_tw_sub2,
+                                       e->gen_h, e->d_scratch, nullptr, false, s, e->format, false, d_rows));
+        e->last = e->plan;
+        return RPF_OK;
+    };
+    if (!overlapped(e)) return rows(d_frames, nframes, d_out);
+    if (!e->d_gather) {
+        e->gather_frames = std::max<int64_t>(1, static_cast<int64_t>(rpf::kGatherBytes / frame));
+        HIP_TRY(e, hipMalloc(&e->d_gather, static_cast<size_t>(e->gather_frames) * frame));
+    }
+    const long pitch = static_cast<long>(e->sample_bytes) * e->step;
+    for (int64_t f0 = 0; f0 < nframes; f0 += e->gather_frames) {
+        const int64_t n = std::min(e->gather_frames, nframes - f0);
+        HIP_TRY(e, rpf::launch_gather_frames(d_frames + f0 * pitch, n, pitch, static_cast<long>(frame), e->d_gather, s));
+        if (int rc = rows(e->d_gather, n, d_out + static_cast<size_t>(f0) * e->N)) return rc;
+    }
+    return RPF_OK;
+}
+
+static int stft_enqueue(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, rpf::cf* d_out, hipStream_t s);
+
+// A PFB engine, the channelizer: the existing fold per chunk of scratch, then the inner cf32 engine's STFT of the folded
+// frames into the chunk's rows.
+static int transform_stft_pfb(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, rpf::cf* d_out, hipStream_t s)
+{
+    const size_t row = e->sample_bytes * static_cast<size_t>(e->N);
+    for (int64_t f0 = 0; f0 < nframes; f0 += e->pfb_chunk_frames) {
+        const int64_t n = std::min(e->pfb_chunk_frames, nframes - f0);
+        HIP_TRY(e, rpf::launch_pfb_fold(d_frames + static_cast<size_t>(f0) * row, n, e->N, e->taps, e->format, e->d_pfb_coeffs,
+                                        e->d_pfb_z, s));
+        const int rc = stft_enqueue(e->inner, reinterpret_cast<const uint8_t*>(e->d_pfb_z), n, d_out + static_cast<size_t>(f0) * e->N, s);
+        if (rc != RPF_OK) return fail(e, rc, e->inner->last_error);
+    }
+    return RPF_OK;
+}
+
+// Rows [0, nframes) of d_out on `s` by the engine's route (ensure_stft has run).
+static int stft_enqueue(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, rpf::cf* d_out, hipStream_t s)
+{
+    e->last_was_cross = false;
+    e->last_was_stft = false;
+    if (e->taps) return transform_stft_pfb(e, d_frames, nframes, d_out, s);
+    if (stft_native(e)) return transform_stft_k1(e, d_frames, nframes, d_out, s);
+    if (e->family == rpf::Family::Generic) return transform_stft_generic(e, d_frames, nframes, d_out, s);
+    const int rc = transform_stft_generic(e->stft_inner, d_frames, nframes, d_out, s);
+    if (rc != RPF_OK) return fail(e, rc, e->stft_inner->last_error);
+    e->last_was_stft = true;
+    return RPF_OK;
+}
+
+int rpf_stft_device(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t max_frames, void* d_out, int64_t* frames_done,
+                    void* hip_stream)
+{
+    const std::string me = "rpf_stft_device";
+    int rc = stft_check(e, me.c_str(), d_stream, nbytes, max_frames, d_out);
+    if (rc != RPF_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_out must be 16-byte aligned");
+    const int64_t nframes = std::min(frames_in(e, nbytes), max_frames);
+    if (frames_done) *frames_done = 0;
+    if (nframes == 0) return RPF_OK;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    if ((rc = ensure_stft(e)) != RPF_OK) return rc;
+    rc = stft_enqueue(e, static_cast<const uint8_t*>(d_stream), nframes, static_cast<rpf::cf*>(d_out),
+                      static_cast<hipStream_t>(hip_stream));
+    if (rc == RPF_OK && frames_done) *frames_done = nframes;         // (rows that were enqueued, never rows that were not)
+    return rc;
+}
+
+int rpf_stft(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t max_frames, void* out, int64_t* frames_done)
+{
+    int rc = stft_check(e, "rpf_stft", stream, nbytes, max_frames, out);
+    if (rc != RPF_OK) return rc;
+    const int64_t nframes = std::min(frames_in(e, nbytes), max_frames);
+    if (frames_done) *frames_done = 0;
+    if (nframes == 0) return RPF_OK;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = e->compute_stream;
+    if ((rc = ensure_stft(e)) != RPF_OK) return rc;
+    // The series family's piece loop with one frame per integration and the rows as the second bound (series_pieces.h,
+    // stft_pieces: the cap is budget / row bytes): a piece's rows go to d_stft_rows and come back in ONE copy.
+    const size_t row_floats = 2 * static_cast<size_t>(e->N);
+    const int64_t row_cap = rpf::stft_pieces(frame_bytes(e), sizeof(float) * row_floats).per_piece;
+    float* const host_rows = static_cast<float*>(out);
+    return series_host_pieces(
+        e, stream, 1, nframes, row_cap,
+        [&](int64_t per_piece) {
+            return grow_scratch(e, &e->d_stft_rows, &e->stft_rows, static_cast<size_t>(per_piece), sizeof(float) * row_floats, s);
+        },
+        [&](int64_t k0, int64_t kc, hipStream_t ps) {
+            if (int prc = stft_enqueue(e, e->d_series_in, kc, reinterpret_cast<rpf::cf*>(e->d_stft_rows), ps)) return prc;
+            HIP_TRY(e, hipMemcpyAsync(host_rows + static_cast<size_t>(k0) * row_floats, e->d_stft_rows,
+                                      sizeof(float) * row_floats * static_cast<size_t>(kc), hipMemcpyDeviceToHost, ps));
+            return static_cast<int>(RPF_OK);
+        },
+        frames_done);
+}
+
 int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
                      void* hip_stream, int64_t* repeats_done)
 {
@@ -2473,6 +2665,7 @@ int rpf_last_launch_info(const rpf_engine* e, int* grid, int* block, int* frames
     if (!e) return RPF_ERR_INVALID_ARGUMENT;
     if (e->inner) e = e->inner;           // a PFB engine reports its transform launch
     if (e->last_was_cross && e->cross_inner) e = e->cross_inner;      // ... and a cross call the cf32 engine's
+    if (e->last_was_stft && e->stft_inner) e = e->stft_inner;         // ... and an STFT call on another family the catch-all engine's
     if (grid) *grid = e->last.grid ? e->last.grid : e->plan.grid;
     if (block) *block = e->plan.block;
     if (frames_per_wg) *frames_per_wg = e->plan.fpw;

@@ -240,8 +240,9 @@ void generic_twiddle_tables(int N, std::vector<cf>& t0, std::vector<cf>& t1, int
 }
 
 // One Stockham transform of `frames` frames of length M in d_a (ping-pong with d_b);
-// returns the buffer that holds the result.
-static cf* run_fft(cf* d_a, cf* d_b, long M, int frames, const cf* d_t0, const cf* d_t1, int h, hipStream_t stream)
+// returns the buffer that holds the result.  d_final (may be null): where the last pass writes instead.
+static cf* run_fft(cf* d_a, cf* d_b, long M, int frames, const cf* d_t0, const cf* d_t1, int h, hipStream_t stream,
+                   cf* d_final = nullptr)
 {
     const int logM = ilog2i(M);
     TwoLevel tw{d_t0, d_t1, h, (1u << h) - 1u};
@@ -250,6 +251,7 @@ static cf* run_fft(cf* d_a, cf* d_b, long M, int frames, const cf* d_t0, const c
     int ls = 0;
     if (logM & 1) {
         const long total = static_cast<long>(frames) * (M / 2);
+        if (d_final && logM == 1) dst = d_final;
         hipLaunchKernelGGL(gen_radix2_kernel, dim3(static_cast<unsigned>((total + kThreads - 1) / kThreads)), dim3(kThreads),
                            0, stream, src, dst, static_cast<int>(M), ls, total, tw);
         std::swap(src, dst);
@@ -257,6 +259,7 @@ static cf* run_fft(cf* d_a, cf* d_b, long M, int frames, const cf* d_t0, const c
     }
     for (; ls < logM; ls += 2) {
         const long total = static_cast<long>(frames) * (M / 4);
+        if (d_final && ls + 2 >= logM) dst = d_final;
         hipLaunchKernelGGL(gen_radix4_kernel, dim3(static_cast<unsigned>((total + kThreads - 1) / kThreads)), dim3(kThreads),
                            0, stream, src, dst, static_cast<int>(M), ls, total, tw);
         std::swap(src, dst);
@@ -269,11 +272,12 @@ static cf* run_fft(cf* d_a, cf* d_b, long M, int frames, const cf* d_t0, const c
 // d_g / d_bhat: bluestein_tables.h's tables (other N).  d_scratch: generic_scratch_bytes(N).
 hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const float* d_window, const cf* d_g,
                           const cf* d_bhat, const cf* d_t0, const cf* d_t1, int h, cf* d_scratch, double* d_pwr,
-                          bool accumulate, hipStream_t stream, int fmt, bool stats)
+                          bool accumulate, hipStream_t stream, int fmt, bool stats, cf* d_rows)
 {
     if (!generic_supported(N) || nframes < 1 || (fmt != kFmtCf32 && (fmt < kFmtCu8 || fmt > kFmtCs16))) return hipErrorInvalidValue;
     const long M = generic_length(N);
     const bool blu = M != N;
+    if (d_rows && blu) return hipErrorInvalidValue;      // (Bluestein's X lacks the final chirp: rpf_engine.h, rpf_stft_device)
     const int batch = generic_batch(N);
     cf* const d_a = d_scratch;
     cf* const d_b = d_scratch + static_cast<size_t>(M) * batch;
@@ -293,7 +297,12 @@ hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const fl
         const LoadFn loader = fmt == kFmtCf32 ? load_cf32[blu ? 1 : 0] : load_int[fmt][blu ? 1 : 0];
         hipLaunchKernelGGL(loader, dim3(blocks), dim3(kThreads), 0, stream, src, N, static_cast<int>(M), total, d_window,
                            d_g, d_a);
-        cf* res = run_fft(d_a, d_b, M, nb, d_t0, d_t1, h, stream);
+        cf* res = run_fft(d_a, d_b, M, nb, d_t0, d_t1, h, stream, d_rows ? d_rows + static_cast<size_t>(done) * N : nullptr);
+        if (d_rows) {
+            const hipError_t err = hipGetLastError();
+            if (err != hipSuccess) return err;
+            continue;
+        }
         if (blu) {
             hipLaunchKernelGGL(gen_mul_conj_kernel, dim3(blocks), dim3(kThreads), 0, stream, res, d_bhat, static_cast<int>(M),
                                total);

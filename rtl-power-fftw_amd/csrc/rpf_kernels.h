@@ -84,6 +84,18 @@ hipError_t launch_fft_accum_series_stats(int N, bool window, bool use_dma, const
                                          const float* d_window, double* d_partial, int grid, hipStream_t stream,
                                          LaunchInfo* li, int fmt = kFmtCu8);
 
+// ---- the frames' spectra themselves (rpf_kernels_stft*.hip; include/rpf_engine.h, rpf_stft_device) ----
+// Variant 0 of every K1 size, all four sample formats.
+bool stft_supported(int N, int fmt = kFmtCu8);
+// The store kernels' resident grid (kernels of their own, their own register counts).
+hipError_t plan_stft(int N, bool window, int device, LaunchInfo* li, int fmt = kFmtCu8);
+// d_out[f N .. f N + N) = the float32 transform of frame f = bytes [pitch f, pitch f + bN) of d_stream, f < nframes,
+// overwritten; nothing else is written.  pitch as launch_fft_accum's (0 = bN; any other runs the strided kernel, and
+// use_dma then also needs pitch % 16 == 0); d_out 16-byte aligned; `grid` <= the planned grid.
+hipError_t launch_fft_stft(int N, bool window, bool use_dma, const uint8_t* d_stream, long nframes, const cf* d_twiddles,
+                           const float* d_window, cf* d_out, int grid, hipStream_t stream, LaunchInfo* li, long pitch = 0,
+                           int fmt = kFmtCu8);
+
 // ---- the excised average over such rows (rpf_excise.hip, excise_core.h) ----
 // d_state: excise_state_doubles(N) doubles, one accumulator triple per (row group, bin), owned by one call at a time.
 size_t excise_state_doubles(int N);
@@ -198,9 +210,13 @@ void generic_twiddle_tables(int N, std::vector<cf>& t0, std::vector<cf>& t1, int
 // d_g (N) / d_bhat (M): bluestein_tables.h's tables (other N).
 hipError_t launch_generic(int N, const uint8_t* d_stream, long nframes, const float* d_window, const cf* d_g,
                           const cf* d_bhat, const cf* d_t0, const cf* d_t1, int h, cf* d_scratch, double* d_pwr,
-                          bool accumulate, hipStream_t stream, int fmt = kFmtCu8, bool stats = false);
+                          bool accumulate, hipStream_t stream, int fmt = kFmtCu8, bool stats = false, cf* d_rows = nullptr);
 // stats: d_pwr is three planes, d_pwr[plane * N + bin] = S1, S2, PK (launch_fft_accum), combined over the batches --
 // and with what d_pwr holds when `accumulate` -- by +, +, max.
+// d_rows (powers of two only; d_pwr, accumulate and stats are then not looked at): instead of squaring and summing, frame
+// f's transform X goes to d_rows[f N .. f N + N) in natural order -- the batch loop writes the rows [done, done + nb) --
+// by the Stockham transform's own last pass, which is given the rows as its destination: no kernel is added and none
+// changes.
 
 // ---- overlapped frames on the other kernel families (rpf_frames.hip) --------------------------------
 // d_dst[f * frame_bytes .. (f+1) * frame_bytes) = d_src[f * pitch .. f * pitch + frame_bytes) for f < nframes:

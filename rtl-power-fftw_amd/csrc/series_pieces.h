@@ -36,4 +36,12 @@ inline SeriesPieces series_pieces(const FrameBytes& fb, int64_t L, int64_t K = I
     return {per_piece, fb.span(per_piece * L), static_cast<size_t>(L) * fb.pitch};
 }
 
+// rpf_stft's pieces (one frame per "integration"): a frame leaves a row of row_bytes = 8 N bytes, usually more than it
+// brought, so a piece takes as many whole frames as keep BOTH its input span and its rows within the budget -- and at
+// least one.  With a frame step of one sample the rows, not the input, are the bound.
+inline SeriesPieces stft_pieces(const FrameBytes& fb, size_t row_bytes, int64_t F = INT64_MAX, size_t budget = kSeriesPieceBytes)
+{
+    return series_pieces(fb, 1, F, budget, static_cast<int64_t>(budget / row_bytes));
+}
+
 }  // namespace rpf

@@ -284,6 +284,30 @@ class Datastore:
             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(done)))
         return out, done.value
 
+    # -- the frames' spectra themselves (rpf_stft[_device]; include/rpf_engine.h has the definition) ------------------
+    def stft_device(self, d_stream_ptr, nbytes, max_frames, d_out_ptr, hip_stream=0):
+        """rpf_stft_device: row f of d_out (F x N device complex64, 16-byte aligned) = the float32 transform of frame f
+        of a stream resident in HBM; asynchronous.  Returns F."""
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_stft_device(
+            self._handle, ctypes.c_void_p(d_stream_ptr), nbytes, max_frames, ctypes.c_void_p(d_out_ptr),
+            ctypes.byref(done), ctypes.c_void_p(hip_stream)))
+        return done.value
+
+    def stft(self, stream, max_frames=None):
+        """rpf_stft: the same on a host byte stream.  Returns a complex64 array of shape (F, N); max_frames None = every
+        whole frame the stream holds."""
+        stream = _as_bytes(stream)
+        if max_frames is None:
+            max_frames = 1 << 62
+        rows = max(min(max_frames, self.frames_in(stream.size)), 0)
+        out = np.zeros((max(rows, 1), self.params.N), dtype=np.complex64)
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_stft(
+            self._handle, ctypes.c_void_p(stream.ctypes.data), stream.size, max_frames,
+            ctypes.c_void_p(out.ctypes.data), ctypes.byref(done)))
+        return out[:done.value]
+
     def accumulate_device_series(self, d_stream_ptr, nbytes, frames_per_spectrum, max_spectra, d_out_ptr, hip_stream=0):
         """rpf_accumulate_device_series: consecutive spectra of `frames_per_spectrum` frames of a stream resident in
         HBM, row k of d_out (K x N device doubles) = frames [k L, (k + 1) L); asynchronous.  Returns K."""

@@ -285,6 +285,24 @@ public:
                                         d_mask, hip_stream, &done));
     return done;
   }
+  // The frames' spectra themselves (rpf_stft; include/rpf_engine.h has the definition): row f of `rows` (resized to F x N
+  // x 2 floats, interleaved re, im) = the float32 transform of frame f of a host stream, F = min(max_frames, frames).  Not
+  // through the buffer queues: pwr and repeats_done stay.  Returns F.
+  int64_t stft(const uint8_t* stream, size_t nbytes, int64_t max_frames, std::vector<float>& rows) {
+    const int64_t fit = std::max<int64_t>(0, std::min(max_frames, static_cast<int64_t>(rpf_frames_in(engine_, nbytes))));
+    rows.assign(static_cast<size_t>(fit) * params.N * 2, 0.0f);
+    int64_t done = 0;
+    float none[2];
+    check(rpf_stft(engine_, stream, nbytes, max_frames, rows.empty() ? none : rows.data(), &done));
+    return done;
+  }
+  // The same on a stream resident in HBM (rpf_stft_device): d_out = F x N x 2 device floats, 16-byte aligned,
+  // asynchronous on hip_stream.
+  int64_t stft_device(const void* d_stream, size_t nbytes, int64_t max_frames, void* d_out, void* hip_stream = nullptr) {
+    int64_t done = 0;
+    check(rpf_stft_device(engine_, d_stream, nbytes, max_frames, d_out, &done, hip_stream));
+    return done;
+  }
   // Cross-spectrum of two host streams of nbytes each (rpf_accumulate_cross; include/rpf_engine.h has the definition):
   // `planes` (resized to 4 x N) = Saa, Sbb, Re Sab, Im Sab over the first min(repeats, frames) frames; coherence and
   // cross_phase above take one bin of them.  Not through the buffer queues: pwr and repeats_done stay.  Returns the frames.

@@ -286,6 +286,21 @@ long long rpf_host_accumulate_series(int N, int sample_format, int frame_step, c
     });
 }
 
+// rpf_host::Datastore's two STFT calls: the rows of a host stream through stft into out[cap_rows x N x 2 floats];
+// device_resident != 0: stream and out are device pointers and stft_device runs on the null stream.  Returns F, or
+// -(the reference's exit code) with the message in `msg`.
+long long rpf_host_stft(int N, int sample_format, int frame_step, const unsigned char* stream, size_t nbytes,
+                        long long max_frames, float* out, long long cap_rows, int device_resident, char* msg, size_t cap)
+{
+    return on_datastore(N, sample_format, frame_step, false, nullptr, msg, cap, [&](Datastore& data) -> long long {
+        if (device_resident) return data.stft_device(stream, nbytes, std::min(max_frames, cap_rows), out);
+        std::vector<float> rows;
+        const long long done = data.stft(stream, nbytes, std::min(max_frames, cap_rows), rows);
+        std::memcpy(out, rows.data(), sizeof(float) * rows.size());
+        return done;
+    });
+}
+
 // The same for the two series calls with statistics, on a Datastore with params.bin_stats: out[cap_rows x 3 x N].
 long long rpf_host_accumulate_series_stats(int N, int sample_format, int frame_step, const unsigned char* stream,
                                            size_t nbytes, long long L, long long max_spectra, double* out, long long cap_rows,

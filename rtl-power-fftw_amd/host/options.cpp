@@ -90,6 +90,11 @@ const Spec kSpecs[] = {
      "power of a, the power of b, the magnitude-squared coherence and the phase of the cross-spectrum [rad] over the whole "
      "frames of the shorter file (not with a frequency range, -n, -t, -c, -e, -m, --stats, --series, --series-stats, "
      "--excise, --quantile, --pfb or several --gpus)."},
+    {0, "stft", Kind::Text, "file",
+     "Short-time Fourier transform of --input: the complex spectrum of every FFT frame, bin N/2 = DC, written to <file> as "
+     "raw little-endian float32 pairs (re, im), frame after frame; nothing goes to stdout (power-of-two bins only; "
+     "combines with -w, --format, --frame-overlap and --pfb; not with a frequency range, -n, -t, -c, -e, -m, --stats, "
+     "--series, --series-stats, --excise, --quantile, --cross or several --gpus)."},
     {0, "reduce", Kind::Text, "rccl|host", "With --gpus: where a scan's per-device spectra are added (default: rccl if it loads, else host)."},
     {'h', "help", Kind::Flag, "", "Displays usage information and exits."},
     {0, "version", Kind::Flag, "", "Displays version information and exits."},
@@ -466,6 +471,25 @@ Options parse_command_line(int argc, const char* const* argv)
                          "): the integration length is its own argument and the replay is read once.");
         if (o.matrixMode) conflict("does not combine with -m (matrix mode): the quantiles are columns of one text block.");
         if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
+    }
+    if (p.has("stft")) {
+        o.stft_file = p.get("stft");
+        auto conflict = [](const std::string& what) {
+            throw RPFexception("Option --stft " + what + " Exiting.", ReturnValue::InvalidArgument);
+        };
+        if (!p.has("input")) conflict("needs --input: it transforms the frames of a replayed stream.");
+        for (const char* name : {"repeats", "time", "continue", "elapsed"})
+            if (p.has(name))
+                conflict(std::string("does not combine with --") + name + " (-" + find_spec(std::string("--") + name)->short_name +
+                         "): the replay is read once, to its end, and every frame leaves a row.");
+        if (o.freq_hopping_isSet) conflict("does not combine with a frequency range in -f: a replay is one stream.");
+        if (o.matrixMode) conflict("does not combine with -m (matrix mode): the rows go to the file given to --stft.");
+        if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
+        for (const char* name : {"stats", "series", "series-stats", "excise", "quantile", "cross"})
+            if (p.has(name))
+                conflict(std::string("does not combine with --") + name + ": those end in sums of |X|^2, this writes X itself.");
+        if (o.N & (o.N - 1))
+            conflict("needs a power-of-two number of bins (-b); got " + std::to_string(o.N) + ".");
     }
     if (p.has("cross")) {
         o.cross_file = p.get("cross");

@@ -1,6 +1,7 @@
 // piece_reader.h -- a file (or stdin) handed out in the pieces of csrc/series_pieces.h, whole integrations of L frames
 // in one buffer: fill(), the engine call on data() with per_piece() as its cap, consume(what it credited), until that
-// says false or the engine credits nothing.  --series, --series-stats, --excise and --quantile read their input so.
+// says false or the engine credits nothing.  --series, --series-stats, --excise, --quantile, --cross and --stft read their
+// input so.
 #ifndef RPF_HOST_PIECE_READER_H
 #define RPF_HOST_PIECE_READER_H
 
@@ -16,10 +17,11 @@ namespace rpf_host {
 class PieceReader {
 public:
   // path "-": stdin.  Frame f of the file is bytes [f pitch_bytes, f pitch_bytes + frame_bytes).
+  // row_cap: at most so many integrations in a piece (--stft: the rows a piece leaves are bounded too, stft_pieces).
   PieceReader(const std::string& path, int64_t frame_bytes, int64_t pitch_bytes, int64_t L,
-              int64_t budget = static_cast<int64_t>(rpf::kSeriesPieceBytes))
+              int64_t budget = static_cast<int64_t>(rpf::kSeriesPieceBytes), int64_t row_cap = INT64_MAX)
     : frames_{static_cast<size_t>(frame_bytes), static_cast<size_t>(pitch_bytes)}, L_(L),
-      pieces_(rpf::series_pieces(frames_, L, INT64_MAX, static_cast<size_t>(budget))),
+      pieces_(rpf::series_pieces(frames_, L, INT64_MAX, static_cast<size_t>(budget), row_cap)),
       file_(path == "-" ? stdin : std::fopen(path.c_str(), "rb")), bytes_(file_ ? pieces_.bytes : 0) {
     if (!file_) throw RPFexception("Could not open " + path + ".", ReturnValue::InvalidInput);
   }

@@ -534,6 +534,42 @@ int run_cross(const Options& options, AuxData& aux, int actual_samplerate, int64
     return 0;
 }
 
+// --input a --stft out: the complex spectrum of every frame of the replay (rpf_stft), raw little-endian float32 pairs,
+// frame after frame, into `out`; nothing on stdout.  The file is read in pieces of whole frames that keep the input AND the
+// rows a piece leaves within the budget (piece_reader.h with one frame per integration and the row cap of stft_pieces),
+// the bytes neighbouring pieces share carried over.
+int run_stft(const Options& options, AuxData& aux, int actual_samplerate)
+{
+    Datastore data(options, aux.window_values);
+    const int64_t b = options.sample_bytes();
+    // (the frames of a piece by the engine's own rule: csrc/series_pieces.h, stft_pieces)
+    const int64_t row_cap = rpf::stft_pieces(options.frame_bytes(), 8 * static_cast<size_t>(options.N)).per_piece;
+    PieceReader in(options.input_file, b * options.span_samples(), b * options.step(), 1,
+                   static_cast<int64_t>(rpf::kSeriesPieceBytes), row_cap);
+    std::ofstream out(options.stft_file, std::ios::out | std::ios::trunc | std::ios::binary);
+    if (!out) throw RPFexception("Could not open " + options.stft_file + " for writing.", ReturnValue::InvalidInput);
+    std::vector<float> rows;
+    int64_t frames = 0;
+    set_CtrlC_handler(true);
+    while (!checkInterrupt(InterruptState::FinishNow)) {
+        const size_t have = in.fill() / static_cast<size_t>(b) * static_cast<size_t>(b);
+        const int64_t done = data.stft(in.data(), have, in.per_piece(), rows);
+        if (done == 0) break;
+        out.write(reinterpret_cast<const char*>(rows.data()), static_cast<std::streamsize>(sizeof(float) * 2 * options.N * done));
+        if (!out) throw RPFexception("Could not write to " + options.stft_file + ".", ReturnValue::InvalidInput);
+        frames += done;
+        if (!in.consume(done)) break;
+    }
+    if (frames == 0)
+        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+    int lds = 0;
+    (void)rpf_last_launch_info(data.engine(), nullptr, nullptr, nullptr, &lds);
+    std::cerr << "STFT: " << frames << " frames of " << options.N << " bins, route: "
+              << (options.pfb_taps ? "PFB fold, then " : "") << (lds > 0 ? "K1 store kernels" : "catch-all transform") << std::endl;
+    if (chatty(options)) print_acquisition_summary(options.N, frames, 0, 0, actual_samplerate);
+    return 0;
+}
+
 int run(int argc, char** argv)
 {
     Options options = parse_command_line(argc, argv);
@@ -583,6 +619,7 @@ int run(int argc, char** argv)
     Plan plan(options, actual_samplerate);
     plan.print();
 
+    if (!options.stft_file.empty()) return run_stft(options, aux, actual_samplerate);
     if (!options.cross_file.empty()) return run_cross(options, aux, actual_samplerate, source->frequency());
     if (options.quantile_frames > 0) return run_quantile(options, aux, actual_samplerate, source->frequency());
     if (options.excise_frames > 0) return run_excise(options, aux, actual_samplerate, source->frequency());
