@@ -5,6 +5,7 @@
 #include <fstream>
 #include <iomanip>
 #include <iostream>
+#include <sstream>
 
 #include "interrupts.h"
 #include "scan_plan.h"
@@ -125,43 +126,18 @@ void Acquisition::print_summary() const
                               actual_samplerate_);
 }
 
-void write_text_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp)
-{
-    write_text_header(out, start_stamp, end_stamp, false);
-}
-
-void write_text_header_excised(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp)
-{
-    out << "# rtl-power-fftw output" << std::endl;
-    out << "# Acquisition start: " << start_stamp << std::endl;
-    out << "# Acquisition end: " << end_stamp << std::endl;
-    out << "#" << std::endl;
-    out << "# frequency [Hz] power spectral density [dB/Hz] kept fraction" << std::endl;
-}
-
-void write_text_header_quantiles(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp,
-                                 const std::vector<double>& q)
-{
-    out << "# rtl-power-fftw output" << std::endl;
-    out << "# Acquisition start: " << start_stamp << std::endl;
-    out << "# Acquisition end: " << end_stamp << std::endl;
-    out << "#" << std::endl;
-    out << "# frequency [Hz]";
-    for (double v : q) out << " quantile " << std::setprecision(6) << v << " [dB/Hz]";
-    out << std::endl;
-}
-
-void write_text_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, bool stats)
-{
-    out << "# rtl-power-fftw output" << std::endl;
-    out << "# Acquisition start: " << start_stamp << std::endl;
-    out << "# Acquisition end: " << end_stamp << std::endl;
-    out << "#" << std::endl;
-    out << "# frequency [Hz] power spectral density [dB/Hz]" << (stats ? " peak hold [dB/Hz] spectral kurtosis" : "")
-        << std::endl;
-}
-
 namespace {
+
+// The '#' lines that precede a text block; `titles` names the columns after the frequency.
+void write_titled_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp,
+                         const std::string& titles)
+{
+    out << "# rtl-power-fftw output" << std::endl;
+    out << "# Acquisition start: " << start_stamp << std::endl;
+    out << "# Acquisition end: " << end_stamp << std::endl;
+    out << "#" << std::endl;
+    out << "# frequency [Hz]" << titles << std::endl;
+}
 
 // value of bin i after normalisation (acquisition.cxx:392-399): successive
 // divisions in this order, then optional dB and baseline
@@ -178,22 +154,73 @@ inline void interpolate_dc(std::vector<double>& pwr, int N)
     pwr[N / 2] = (pwr[N / 2 - 1] + pwr[N / 2 + 1]) / 2;         // :377
 }
 
-}  // namespace
-
-void write_spectrum_text(std::ostream& out, std::vector<double>& pwr, int N, int64_t repeats_done,
-                         int64_t tuned_freq, int samplerate, bool linear, const std::vector<double>* baseline)
+// One line per bin: its frequency, then what columns(i) writes (" " and a value, per column), in six digits; the blank
+// line that ends a block (:428-432).
+template <class Columns>
+void write_rows(std::ostream& out, int N, int64_t tuned_freq, int samplerate, Columns columns)
 {
-    interpolate_dc(pwr, N);
     // digits needed to tell neighbouring bins apart, plus two (:380-383; samplerate/N is an int division)
     const int freq_digits = static_cast<int>(
         std::ceil(std::floor(std::log10(static_cast<double>(tuned_freq))) - std::log10(samplerate / N) + 1 + 2));
     for (int i = 0; i < N; ++i) {
         const double freq = tuned_freq + (i - N / 2.0) * samplerate / N;
-        out << std::setprecision(freq_digits) << freq << " " << std::setprecision(6)
-            << bin_value(pwr, i, N, repeats_done, samplerate, linear, baseline) << std::endl;
+        out << std::setprecision(freq_digits) << freq << std::setprecision(6);
+        columns(i);
+        out << std::endl;
     }
-    out << std::endl;                                           // :428-432
+    out << std::endl;
     out.flush();
+}
+
+// Plane c of planes[.. x N] on its own, its DC bin the mean of its neighbours.
+std::vector<std::vector<double>> split_planes(const std::vector<double>& planes, size_t count, int N)
+{
+    std::vector<std::vector<double>> plane(count);
+    for (size_t c = 0; c < count; ++c) {
+        plane[c].assign(planes.begin() + c * N, planes.begin() + (c + 1) * N);
+        interpolate_dc(plane[c], N);
+    }
+    return plane;
+}
+
+}  // namespace
+
+void write_text_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp)
+{
+    write_text_header(out, start_stamp, end_stamp, false);
+}
+
+void write_text_header(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, bool stats)
+{
+    write_titled_header(out, start_stamp, end_stamp, std::string(" power spectral density [dB/Hz]") +
+                                                         (stats ? " peak hold [dB/Hz] spectral kurtosis" : ""));
+}
+
+void write_text_header_excised(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp)
+{
+    write_titled_header(out, start_stamp, end_stamp, " power spectral density [dB/Hz] kept fraction");
+}
+
+void write_text_header_quantiles(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp,
+                                 const std::vector<double>& q)
+{
+    std::ostringstream titles;
+    for (double v : q) titles << " quantile " << std::setprecision(6) << v << " [dB/Hz]";
+    write_titled_header(out, start_stamp, end_stamp, titles.str());
+}
+
+void write_text_header_cross(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp)
+{
+    write_titled_header(out, start_stamp, end_stamp,
+                        " power spectral density a [dB/Hz] power spectral density b [dB/Hz] coherence phase [rad]");
+}
+
+void write_spectrum_text(std::ostream& out, std::vector<double>& pwr, int N, int64_t repeats_done,
+                         int64_t tuned_freq, int samplerate, bool linear, const std::vector<double>* baseline)
+{
+    interpolate_dc(pwr, N);
+    write_rows(out, N, tuned_freq, samplerate,
+               [&](int i) { out << " " << bin_value(pwr, i, N, repeats_done, samplerate, linear, baseline); });
 }
 
 void write_spectrum_text_stats(std::ostream& out, std::vector<double>& pwr, const std::vector<double>& sum_sq,
@@ -207,16 +234,10 @@ void write_spectrum_text_stats(std::ostream& out, std::vector<double>& pwr, cons
     interpolate_dc(sk, N);
     interpolate_dc(pwr, N);
     interpolate_dc(peak, N);
-    const int freq_digits = static_cast<int>(
-        std::ceil(std::floor(std::log10(static_cast<double>(tuned_freq))) - std::log10(samplerate / N) + 1 + 2));
-    for (int i = 0; i < N; ++i) {
-        const double freq = tuned_freq + (i - N / 2.0) * samplerate / N;
-        out << std::setprecision(freq_digits) << freq << " " << std::setprecision(6)
-            << bin_value(pwr, i, N, repeats_done, samplerate, linear, baseline) << " "
-            << bin_value(peak, i, N, 1, samplerate, linear, baseline) << " " << sk[i] << std::endl;
-    }
-    out << std::endl;
-    out.flush();
+    write_rows(out, N, tuned_freq, samplerate, [&](int i) {
+        out << " " << bin_value(pwr, i, N, repeats_done, samplerate, linear, baseline) << " "
+            << bin_value(peak, i, N, 1, samplerate, linear, baseline) << " " << sk[i];
+    });
 }
 
 void write_spectrum_text_excised(std::ostream& out, const std::vector<double>& clean, const std::vector<double>& kept,
@@ -230,69 +251,31 @@ void write_spectrum_text_excised(std::ostream& out, const std::vector<double>& c
     for (int i = 0; i < N; ++i)
         mean[i] = kept[i] > 0 ? clean[i] / (kept[i] * l) : total[i] / (static_cast<double>(K) * l);
     interpolate_dc(mean, N);
-    const int freq_digits = static_cast<int>(
-        std::ceil(std::floor(std::log10(static_cast<double>(tuned_freq))) - std::log10(samplerate / N) + 1 + 2));
-    for (int i = 0; i < N; ++i) {
-        const double freq = tuned_freq + (i - N / 2.0) * samplerate / N;
-        out << std::setprecision(freq_digits) << freq << " " << std::setprecision(6)
-            << bin_value(mean, i, N, 1, samplerate, linear, baseline) << " " << kept[i] / static_cast<double>(K) << std::endl;
-    }
-    out << std::endl;
-    out.flush();
+    write_rows(out, N, tuned_freq, samplerate, [&](int i) {
+        out << " " << bin_value(mean, i, N, 1, samplerate, linear, baseline) << " " << kept[i] / static_cast<double>(K);
+    });
 }
 
 void write_spectrum_text_quantiles(std::ostream& out, const std::vector<double>& planes, const std::vector<double>& q, int N,
                                    int64_t L, int64_t tuned_freq, int samplerate, bool linear,
                                    const std::vector<double>* baseline)
 {
-    std::vector<std::vector<double>> columns(q.size());
-    for (size_t c = 0; c < q.size(); ++c) {
-        columns[c].assign(planes.begin() + c * N, planes.begin() + (c + 1) * N);
-        interpolate_dc(columns[c], N);
-    }
-    const int freq_digits = static_cast<int>(
-        std::ceil(std::floor(std::log10(static_cast<double>(tuned_freq))) - std::log10(samplerate / N) + 1 + 2));
-    for (int i = 0; i < N; ++i) {
-        const double freq = tuned_freq + (i - N / 2.0) * samplerate / N;
-        out << std::setprecision(freq_digits) << freq << std::setprecision(6);
+    const std::vector<std::vector<double>> columns = split_planes(planes, q.size(), N);
+    write_rows(out, N, tuned_freq, samplerate, [&](int i) {
         for (const std::vector<double>& column : columns) out << " " << bin_value(column, i, N, L, samplerate, linear, baseline);
-        out << std::endl;
-    }
-    out << std::endl;
-    out.flush();
-}
-
-void write_text_header_cross(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp)
-{
-    out << "# rtl-power-fftw output" << std::endl;
-    out << "# Acquisition start: " << start_stamp << std::endl;
-    out << "# Acquisition end: " << end_stamp << std::endl;
-    out << "#" << std::endl;
-    out << "# frequency [Hz] power spectral density a [dB/Hz] power spectral density b [dB/Hz] coherence phase [rad]"
-        << std::endl;
+    });
 }
 
 void write_spectrum_text_cross(std::ostream& out, const std::vector<double>& planes, int N, int64_t frames, int64_t tuned_freq,
                                int samplerate, bool linear, const std::vector<double>* baseline)
 {
     // the DC bin of each of the four planes is the mean of its neighbours; coherence and phase come from those
-    std::vector<std::vector<double>> plane(4);
-    for (size_t c = 0; c < 4; ++c) {
-        plane[c].assign(planes.begin() + c * N, planes.begin() + (c + 1) * N);
-        interpolate_dc(plane[c], N);
-    }
-    const int freq_digits = static_cast<int>(
-        std::ceil(std::floor(std::log10(static_cast<double>(tuned_freq))) - std::log10(samplerate / N) + 1 + 2));
-    for (int i = 0; i < N; ++i) {
-        const double freq = tuned_freq + (i - N / 2.0) * samplerate / N;
-        out << std::setprecision(freq_digits) << freq << " " << std::setprecision(6)
-            << bin_value(plane[0], i, N, frames, samplerate, linear, baseline) << " "
+    const std::vector<std::vector<double>> plane = split_planes(planes, 4, N);
+    write_rows(out, N, tuned_freq, samplerate, [&](int i) {
+        out << " " << bin_value(plane[0], i, N, frames, samplerate, linear, baseline) << " "
             << bin_value(plane[1], i, N, frames, samplerate, linear, baseline) << " "
-            << coherence(plane[0][i], plane[1][i], plane[2][i], plane[3][i]) << " " << cross_phase(plane[2][i], plane[3][i])
-            << std::endl;
-    }
-    out << std::endl;
-    out.flush();
+            << coherence(plane[0][i], plane[1][i], plane[2][i], plane[3][i]) << " " << cross_phase(plane[2][i], plane[3][i]);
+    });
 }
 
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,

@@ -230,6 +230,15 @@ long rpf_host_format_header(const char* start_stamp, const char* end_stamp, int 
     return copy_out(os.str(), out, cap);
 }
 
+// The text header of the --excise block (cross == 0) or of the --cross block.
+long rpf_host_format_header_mode(const char* start_stamp, const char* end_stamp, int cross, char* out, size_t cap)
+{
+    std::ostringstream os;
+    if (cross) write_text_header_cross(os, start_stamp, end_stamp);
+    else write_text_header_excised(os, start_stamp, end_stamp);
+    return copy_out(os.str(), out, cap);
+}
+
 // datastore.h's spectral_kurtosis, element by element.
 void rpf_host_spectral_kurtosis(const double* s1, const double* s2, long long M, double* out, int n)
 {

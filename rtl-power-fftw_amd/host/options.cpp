@@ -175,6 +175,80 @@ void require_non_negative(const Parsed& p, const char* name)
                            ReturnValue::InvalidArgument);
 }
 
+// A replay mode is an option that reads --input once, to its end, outside the acquisition loop.  One row each, in the
+// order their refusals speak; replay_mode() below walks a row.
+struct Refused { const char* option; const char* why; };
+struct ReplayMode {
+    const char* name;
+    int64_t Options::*frames;       // where its <frames> goes, checked against min_frames; null: the argument is a file
+    int min_frames;
+    const char* min_why;            // (what follows "at least <min_frames>")
+    const char* input_why;          // "needs --input: <input_why>."
+    const char* repeat_why;         // "does not combine with --repeats (-n): <repeat_why>."; so -t, -c, -e
+    const char* matrix_why;         // "does not combine with -m (matrix mode): <matrix_why>."
+    bool bin_stats;                 // turns Options::bin_stats on
+    Refused refused[7];             // "does not combine with --<option>: <why>.", in this order; ends at the first null
+};
+
+const char kOwnLength[] = "the integration length is its own argument and the replay is read once";
+const char kAverage[] = "that writes every integration, this one their average";
+const char kOneProduct[] = "one product of the integrations per run";
+const char kSums[] = "those end in sums of |X|^2, this writes X itself";
+const char kNoCross[] = "cross-spectra of those are not built";
+
+const ReplayMode kReplayModes[] = {
+    {"series", &Options::series_frames, 1, "", "it cuts a replayed stream into consecutive integrations", kOwnLength,
+     "the spectra are text blocks", false, {{"stats", "time-resolved statistics are not built"}}},
+    {"series-stats", &Options::series_frames, 1, "", "it cuts a replayed stream into consecutive integrations", kOwnLength,
+     "the spectra are text blocks", true, {}},
+    {"excise", &Options::excise_frames, 2, " (the spectral kurtosis of one frame is undefined)",
+     "it averages a replayed stream", kOwnLength, "the average is one text block", true,
+     {{"series", kAverage}, {"series-stats", kAverage}}},
+    {"quantile", &Options::quantile_frames, 1, "", "it ranks the integrations of a replayed stream", kOwnLength,
+     "the quantiles are columns of one text block", false,
+     {{"series", kOneProduct}, {"series-stats", kOneProduct}, {"excise", kOneProduct},
+      {"stats", "the row store holds the plain series"}, {"pfb", "quantiles of PFB spectra are not built"}}},
+    {"stft", nullptr, 0, "", "it transforms the frames of a replayed stream",
+     "the replay is read once, to its end, and every frame leaves a row", "the rows go to the file given to --stft", false,
+     {{"stats", kSums}, {"series", kSums}, {"series-stats", kSums}, {"excise", kSums}, {"quantile", kSums}, {"cross", kSums}}},
+    {"cross", nullptr, 0, "", "that is stream a, and the file given here stream b",
+     "the two replays are read once, to the end of the shorter", "the cross-spectrum is one text block", false,
+     {{"stats", kNoCross}, {"series", kNoCross}, {"series-stats", kNoCross}, {"excise", kNoCross}, {"quantile", kNoCross},
+      {"pfb", kNoCross}}},
+};
+
+[[noreturn]] void refuse(const std::string& mode, const std::string& what)
+{
+    throw RPFexception("Option --" + mode + " " + what + " Exiting.", ReturnValue::InvalidArgument);
+}
+
+// False when the command line does not name the mode; else takes its frame count, throws the first of the row's
+// refusals that applies, and returns true.  `o` holds what parse_command_line has made of the other options by then.
+bool replay_mode(const std::string& name, const Parsed& p, Options& o)
+{
+    if (!p.has(name.c_str())) return false;
+    const ReplayMode* m = kReplayModes;
+    while (name != m->name) ++m;
+    if (m->frames) {
+        o.*m->frames = to_number<int64_t>(*find_spec("--" + name), p.get(name.c_str()));
+        if (o.*m->frames < m->min_frames)
+            refuse(name, "needs a number of frames of at least " + std::to_string(m->min_frames) + m->min_why + ", got " +
+                             p.get(name.c_str()) + ".");
+    }
+    if (!p.has("input")) refuse(name, std::string("needs --input: ") + m->input_why + ".");
+    for (const Refused* r = m->refused; r->option; ++r)
+        if (p.has(r->option)) refuse(name, std::string("does not combine with --") + r->option + ": " + r->why + ".");
+    if (o.freq_hopping_isSet) refuse(name, "does not combine with a frequency range in -f: a replay is one stream.");
+    for (const char* other : {"repeats", "time", "continue", "elapsed"})
+        if (p.has(other))
+            refuse(name, std::string("does not combine with --") + other + " (-" + find_spec(std::string("--") + other)->short_name +
+                             "): " + m->repeat_why + ".");
+    if (o.matrixMode) refuse(name, std::string("does not combine with -m (matrix mode): ") + m->matrix_why + ".");
+    if (o.devices.size() > 1) refuse(name, "does not combine with several devices in --gpus.");
+    if (m->bin_stats) o.bin_stats = true;
+    return true;
+}
+
 }  // namespace
 
 std::string usage_text()
@@ -379,68 +453,25 @@ Options parse_command_line(int argc, const char* const* argv)
     if (o.bin_stats && o.devices.size() > 1)
         throw RPFexception("Option --stats does not combine with several devices in --gpus. Exiting.",
                            ReturnValue::InvalidArgument);
-    // --series <frames>, or --series-stats <frames>: the same series with a stats engine (--stats beside it changes nothing)
+    // the replay modes (kReplayModes), in the table's order: with two of them given, the first one's refusals speak.
+    // Beside each walk, what is that mode's own.
     if (p.has("series") && p.has("series-stats"))
         throw RPFexception("Option --series-stats does not combine with --series: it is the series with the statistics "
                            "columns. Exiting.", ReturnValue::InvalidArgument);
-    if (p.has("series") || p.has("series-stats")) {
-        o.series_stats = p.has("series-stats");
-        const std::string opt = o.series_stats ? "series-stats" : "series";
-        o.series_frames = to_number<int64_t>(*find_spec("--" + opt), p.get(opt.c_str()));
-        auto conflict = [&opt](const std::string& what) {
-            throw RPFexception("Option --" + opt + " " + what + " Exiting.", ReturnValue::InvalidArgument);
-        };
-        if (o.series_frames < 1) conflict("needs a number of frames of at least 1, got " + p.get(opt.c_str()) + ".");
-        if (!p.has("input")) conflict("needs --input: it cuts a replayed stream into consecutive integrations.");
-        if (o.freq_hopping_isSet) conflict("does not combine with a frequency range in -f: a replay is one stream.");
-        for (const char* name : {"repeats", "time", "continue", "elapsed"})
-            if (p.has(name))
-                conflict(std::string("does not combine with --") + name + " (-" + find_spec(std::string("--") + name)->short_name +
-                         "): the integration length is its own argument and the replay is read once.");
-        if (o.matrixMode) conflict("does not combine with -m (matrix mode): the spectra are text blocks.");
-        if (o.bin_stats && !o.series_stats) conflict("does not combine with --stats: time-resolved statistics are not built.");
-        if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
-        if (o.series_stats) o.bin_stats = true;
-    }
+    replay_mode("series", p, o);
+    o.series_stats = replay_mode("series-stats", p, o);       // (--stats beside it changes nothing)
     if (p.has("excise-sigma") && !p.has("excise"))
         throw RPFexception("Option --excise-sigma needs --excise: it sets the width of its thresholds. Exiting.",
                            ReturnValue::InvalidArgument);
-    if (p.has("excise")) {
-        o.excise_frames = to_number<int64_t>(*find_spec("--excise"), p.get("excise"));
-        auto conflict = [](const std::string& what) {
-            throw RPFexception("Option --excise " + what + " Exiting.", ReturnValue::InvalidArgument);
-        };
-        if (o.excise_frames < 2)
-            conflict("needs a number of frames of at least 2 (the spectral kurtosis of one frame is undefined), got " +
-                     p.get("excise") + ".");
-        if (p.has("excise-sigma")) {
-            o.excise_sigma = to_number<double>(*find_spec("--excise-sigma"), p.get("excise-sigma"));
-            if (!(o.excise_sigma >= 0) || std::isinf(o.excise_sigma))
-                conflict("needs a finite, non-negative --excise-sigma, got " + p.get("excise-sigma") + ".");
-        }
-        if (!p.has("input")) conflict("needs --input: it averages a replayed stream.");
-        for (const char* name : {"series", "series-stats"})
-            if (p.has(name))
-                conflict(std::string("does not combine with --") + name + ": that writes every integration, this one their "
-                         "average.");
-        if (o.freq_hopping_isSet) conflict("does not combine with a frequency range in -f: a replay is one stream.");
-        for (const char* name : {"repeats", "time", "continue", "elapsed"})
-            if (p.has(name))
-                conflict(std::string("does not combine with --") + name + " (-" + find_spec(std::string("--") + name)->short_name +
-                         "): the integration length is its own argument and the replay is read once.");
-        if (o.matrixMode) conflict("does not combine with -m (matrix mode): the average is one text block.");
-        if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
-        o.bin_stats = true;
+    if (replay_mode("excise", p, o) && p.has("excise-sigma")) {
+        o.excise_sigma = to_number<double>(*find_spec("--excise-sigma"), p.get("excise-sigma"));
+        if (!(o.excise_sigma >= 0) || std::isinf(o.excise_sigma))
+            refuse("excise", "needs a finite, non-negative --excise-sigma, got " + p.get("excise-sigma") + ".");
     }
     if (p.has("quantiles") && !p.has("quantile"))
         throw RPFexception("Option --quantiles needs --quantile: it lists the quantiles that one writes. Exiting.",
                            ReturnValue::InvalidArgument);
-    if (p.has("quantile")) {
-        o.quantile_frames = to_number<int64_t>(*find_spec("--quantile"), p.get("quantile"));
-        auto conflict = [](const std::string& what) {
-            throw RPFexception("Option --quantile " + what + " Exiting.", ReturnValue::InvalidArgument);
-        };
-        if (o.quantile_frames < 1) conflict("needs a number of frames of at least 1, got " + p.get("quantile") + ".");
+    if (replay_mode("quantile", p, o)) {
         o.quantiles.assign(1, 0.5);
         if (p.has("quantiles")) {
             const std::string list = p.get("quantiles");
@@ -452,62 +483,22 @@ Options parse_command_line(int argc, const char* const* argv)
                 char* end = nullptr;
                 const double v = std::strtod(item.c_str(), &end);
                 if (item.empty() || *end != '\0' || !(v >= 0.0 && v <= 1.0))
-                    conflict("could not use the list given to --quantiles: " + list + ". Expecting comma-separated numbers in [0, 1].");
+                    refuse("quantile", "could not use the list given to --quantiles: " + list +
+                                       ". Expecting comma-separated numbers in [0, 1].");
                 o.quantiles.push_back(v);
                 pos = comma + 1;
             }
-            if (o.quantiles.size() > 8) conflict("takes at most 8 values in --quantiles, got " + std::to_string(o.quantiles.size()) + ".");
+            if (o.quantiles.size() > 8)
+                refuse("quantile", "takes at most 8 values in --quantiles, got " + std::to_string(o.quantiles.size()) + ".");
         }
-        if (!p.has("input")) conflict("needs --input: it ranks the integrations of a replayed stream.");
-        for (const char* name : {"series", "series-stats", "excise"})
-            if (p.has(name))
-                conflict(std::string("does not combine with --") + name + ": one product of the integrations per run.");
-        if (p.has("stats")) conflict("does not combine with --stats: the row store holds the plain series.");
-        if (p.has("pfb")) conflict("does not combine with --pfb: quantiles of PFB spectra are not built.");
-        if (o.freq_hopping_isSet) conflict("does not combine with a frequency range in -f: a replay is one stream.");
-        for (const char* name : {"repeats", "time", "continue", "elapsed"})
-            if (p.has(name))
-                conflict(std::string("does not combine with --") + name + " (-" + find_spec(std::string("--") + name)->short_name +
-                         "): the integration length is its own argument and the replay is read once.");
-        if (o.matrixMode) conflict("does not combine with -m (matrix mode): the quantiles are columns of one text block.");
-        if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
     }
-    if (p.has("stft")) {
+    if (replay_mode("stft", p, o)) {
         o.stft_file = p.get("stft");
-        auto conflict = [](const std::string& what) {
-            throw RPFexception("Option --stft " + what + " Exiting.", ReturnValue::InvalidArgument);
-        };
-        if (!p.has("input")) conflict("needs --input: it transforms the frames of a replayed stream.");
-        for (const char* name : {"repeats", "time", "continue", "elapsed"})
-            if (p.has(name))
-                conflict(std::string("does not combine with --") + name + " (-" + find_spec(std::string("--") + name)->short_name +
-                         "): the replay is read once, to its end, and every frame leaves a row.");
-        if (o.freq_hopping_isSet) conflict("does not combine with a frequency range in -f: a replay is one stream.");
-        if (o.matrixMode) conflict("does not combine with -m (matrix mode): the rows go to the file given to --stft.");
-        if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
-        for (const char* name : {"stats", "series", "series-stats", "excise", "quantile", "cross"})
-            if (p.has(name))
-                conflict(std::string("does not combine with --") + name + ": those end in sums of |X|^2, this writes X itself.");
-        if (o.N & (o.N - 1))
-            conflict("needs a power-of-two number of bins (-b); got " + std::to_string(o.N) + ".");
+        if (o.N & (o.N - 1)) refuse("stft", "needs a power-of-two number of bins (-b); got " + std::to_string(o.N) + ".");
     }
-    if (p.has("cross")) {
+    if (replay_mode("cross", p, o)) {
         o.cross_file = p.get("cross");
-        auto conflict = [](const std::string& what) {
-            throw RPFexception("Option --cross " + what + " Exiting.", ReturnValue::InvalidArgument);
-        };
-        if (!p.has("input")) conflict("needs --input: that is stream a, and the file given here stream b.");
-        if (o.cross_file == "-" && p.get("input") == "-") conflict("cannot read both streams from stdin.");
-        for (const char* name : {"repeats", "time", "continue", "elapsed"})
-            if (p.has(name))
-                conflict(std::string("does not combine with --") + name + " (-" + find_spec(std::string("--") + name)->short_name +
-                         "): the two replays are read once, to the end of the shorter.");
-        if (o.freq_hopping_isSet) conflict("does not combine with a frequency range in -f: a replay is one stream.");
-        if (o.matrixMode) conflict("does not combine with -m (matrix mode): the cross-spectrum is one text block.");
-        if (o.devices.size() > 1) conflict("does not combine with several devices in --gpus.");
-        for (const char* name : {"stats", "series", "series-stats", "excise", "quantile", "pfb"})
-            if (p.has(name))
-                conflict(std::string("does not combine with --") + name + ": cross-spectra of those are not built.");
+        if (o.cross_file == "-" && p.get("input") == "-") refuse("cross", "cannot read both streams from stdin.");
     }
     if (p.has("input")) o.input_file = p.get("input");
     o.synthetic = p.has("synthetic");

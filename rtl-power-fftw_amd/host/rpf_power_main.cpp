@@ -347,6 +347,45 @@ private:
     int64_t hops_written_ = 0;
 };
 
+// ---- the replay modes -------------------------------------------------------------------
+struct NoSpectrum : RPFexception {
+    NoSpectrum() : RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError) {}
+};
+
+// The loop of every replay mode over the pieces of its input (piece_reader.h; two readers: a piece of each at a time):
+// fill, step(the bytes the shorter holds) -> the integrations it credits, consume them on every reader; until a step
+// credits nothing, a reader has less than one integration left or Ctrl-C.  Returns the integrations credited in all and
+// throws NoSpectrum if that is none.  held (if given): what each reader held when last filled -- once more after the
+// last piece, so what is left of each input once the last common integration is taken.
+template <class Step>
+int64_t replay_pieces(const std::vector<PieceReader*>& in, Step step, size_t* held = nullptr)
+{
+    auto fill = [&]() {
+        size_t have = SIZE_MAX;
+        for (size_t r = 0; r < in.size(); ++r) {
+            const size_t got = in[r]->fill();
+            if (held) held[r] = got;
+            have = std::min(have, got);
+        }
+        return have;
+    };
+    int64_t total = 0;
+    set_CtrlC_handler(true);
+    while (!checkInterrupt(InterruptState::FinishNow)) {
+        const int64_t done = step(fill());
+        if (done == 0) break;
+        total += done;
+        bool more = true;
+        for (PieceReader* reader : in) more = reader->consume(done) && more;
+        if (!more) {
+            fill();
+            break;
+        }
+    }
+    if (total == 0) throw NoSpectrum();
+    return total;
+}
+
 // --series <frames>: the replay cut into consecutive integrations of <frames> frames (rpf_accumulate_series), one text
 // block per integration -- what `-c -n <frames> --input` writes, block for block, without an acquisition per block.
 // The file is read in pieces of whole spectra (64 MB, or one spectrum if that is larger) with the bytes two pieces share
@@ -367,38 +406,40 @@ int run_series(const Options& options, AuxData& aux, int actual_samplerate, int6
         peak.resize(options.N);
     }
     int64_t written = 0;
-    set_CtrlC_handler(true);
-    while (!checkInterrupt(InterruptState::FinishNow)) {
-        const std::string start_stamp = Acquisition::utc_now();
-        const size_t have = in.fill();
-        const int64_t done = stats ? data.accumulate_series_stats(in.data(), have, L, in.per_piece(), rows)
-                                   : data.accumulate_series(in.data(), have, L, in.per_piece(), rows);
-        if (done == 0) break;
-        const std::string end_stamp = Acquisition::utc_now();
-        for (int64_t k = 0; k < done; ++k) {
-            const auto at = rows.begin() + static_cast<size_t>(k) * row;
-            std::copy(at, at + options.N, pwr.begin());
-            write_text_header(std::cout, start_stamp, end_stamp, stats);
-            if (stats) {
-                std::copy(at + options.N, at + 2 * options.N, sum_sq.begin());
-                std::copy(at + 2 * options.N, at + 3 * options.N, peak.begin());
-                write_spectrum_text_stats(std::cout, pwr, sum_sq, peak, options.N, L, tuned_freq, actual_samplerate,
-                                          options.linear, baseline);
-            } else {
-                write_spectrum_text(std::cout, pwr, options.N, L, tuned_freq, actual_samplerate, options.linear, baseline);
-            }
-            std::cout << std::endl;          // (the blank line that closes a pass of -c)
-        }
-        written += done;
-        if (!in.consume(done)) break;
-    }
-    if (chatty(options)) {
+    auto report = [&]() {
+        if (!chatty(options)) return;
         std::cerr << "Spectra written: " << written << ", " << L << " frames each ("
                   << (data.series_launches() == 1 ? "one launch per piece" : "one launch per spectrum") << ")" << std::endl;
         print_acquisition_summary(options.N, written * L, 0, 0, actual_samplerate);
+    };
+    std::string start_stamp = Acquisition::utc_now();      // (of every piece: from before it is read)
+    try {
+        written = replay_pieces({&in}, [&](size_t have) {
+            const int64_t done = stats ? data.accumulate_series_stats(in.data(), have, L, in.per_piece(), rows)
+                                       : data.accumulate_series(in.data(), have, L, in.per_piece(), rows);
+            const std::string end_stamp = Acquisition::utc_now();
+            for (int64_t k = 0; k < done; ++k) {
+                const auto at = rows.begin() + static_cast<size_t>(k) * row;
+                std::copy(at, at + options.N, pwr.begin());
+                write_text_header(std::cout, start_stamp, end_stamp, stats);
+                if (stats) {
+                    std::copy(at + options.N, at + 2 * options.N, sum_sq.begin());
+                    std::copy(at + 2 * options.N, at + 3 * options.N, peak.begin());
+                    write_spectrum_text_stats(std::cout, pwr, sum_sq, peak, options.N, L, tuned_freq, actual_samplerate,
+                                              options.linear, baseline);
+                } else {
+                    write_spectrum_text(std::cout, pwr, options.N, L, tuned_freq, actual_samplerate, options.linear, baseline);
+                }
+                std::cout << std::endl;          // (the blank line that closes a pass of -c)
+            }
+            start_stamp = Acquisition::utc_now();
+            return done;
+        });
+    } catch (NoSpectrum&) {
+        report();                                // (said of an input too short as well, before the refusal)
+        throw;
     }
-    if (written == 0)
-        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+    report();
     return 0;
 }
 
@@ -415,23 +456,16 @@ int run_excise(const Options& options, AuxData& aux, int actual_samplerate, int6
     sk_limits(L, options.excise_sigma, sk_lo, sk_hi);
     const size_t N = static_cast<size_t>(options.N);
     std::vector<double> piece, clean(N, 0.0), kept(N, 0.0), total(N, 0.0);
-    int64_t K = 0;
-    set_CtrlC_handler(true);
     const std::string start_stamp = Acquisition::utc_now();
-    while (!checkInterrupt(InterruptState::FinishNow)) {
-        const size_t have = in.fill();
+    const int64_t K = replay_pieces({&in}, [&](size_t have) {
         const int64_t done = data.accumulate_excised(in.data(), have, L, in.per_piece(), sk_lo, sk_hi, piece);
-        if (done == 0) break;
-        for (size_t i = 0; i < N; ++i) {
+        for (size_t i = 0; done > 0 && i < N; ++i) {
             clean[i] += piece[i];
             kept[i] += piece[N + i];
             total[i] += piece[2 * N + i];
         }
-        K += done;
-        if (!in.consume(done)) break;
-    }
-    if (K == 0)
-        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+        return done;
+    });
     const std::string end_stamp = Acquisition::utc_now();
     write_text_header_excised(std::cout, start_stamp, end_stamp);
     write_spectrum_text_excised(std::cout, clean, kept, total, options.N, K, L, tuned_freq, actual_samplerate, options.linear,
@@ -455,27 +489,22 @@ int run_quantile(const Options& options, AuxData& aux, int actual_samplerate, in
     Datastore data(options, aux.window_values);
     const int64_t L = options.quantile_frames;
     PieceReader in(options.input_file, options.sample_bytes() * options.N, options.sample_bytes() * options.step(), L);
-    int64_t K = 0;
+    int64_t kept = 0;
     bool one_launch = true;
-    set_CtrlC_handler(true);
     const std::string start_stamp = Acquisition::utc_now();
     data.quantile_reset();
-    while (!checkInterrupt(InterruptState::FinishNow)) {
-        const size_t have = in.fill();
+    const int64_t K = replay_pieces({&in}, [&](size_t have) {
         const int64_t coming = std::min(in.per_piece(), options.frames_in(static_cast<int64_t>(have)) / L);
-        if (K + coming > data.quantile_max_rows())
+        if (kept + coming > data.quantile_max_rows())
             throw RPFexception("Option --quantile: the input holds more than " + std::to_string(data.quantile_max_rows()) +
                                " integrations of " + std::to_string(L) + " frames, which is what the device keeps of " +
                                std::to_string(options.N) + " bins (1 GiB of rows): raise <frames>. Exiting.",
                                ReturnValue::InvalidArgument);
         const int64_t done = data.quantile_append(in.data(), have, L, in.per_piece());
-        if (done == 0) break;
-        one_launch = one_launch && data.series_launches() == 1;
-        K += done;
-        if (!in.consume(done)) break;
-    }
-    if (K == 0)
-        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+        one_launch = one_launch && (done == 0 || data.series_launches() == 1);
+        kept += done;
+        return done;
+    });
     std::vector<double> planes;
     data.quantile_select(options.quantiles, planes);
     const std::string end_stamp = Acquisition::utc_now();
@@ -496,32 +525,18 @@ int run_quantile(const Options& options, AuxData& aux, int actual_samplerate, in
 int run_cross(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
 {
     Datastore data(options, aux.window_values);
-    const int64_t b = options.sample_bytes();
+    const size_t b = static_cast<size_t>(options.sample_bytes());
     PieceReader in_a(options.input_file, b * options.N, b * options.step(), 1);
     PieceReader in_b(options.cross_file, b * options.N, b * options.step(), 1);
     const size_t N = static_cast<size_t>(options.N);
     std::vector<double> piece, planes(4 * N, 0.0);
-    int64_t frames = 0;
-    size_t left_a = 0, left_b = 0;
-    set_CtrlC_handler(true);
+    size_t left[2] = {0, 0};
     const std::string start_stamp = Acquisition::utc_now();
-    while (!checkInterrupt(InterruptState::FinishNow)) {
-        left_a = in_a.fill();
-        left_b = in_b.fill();
-        const size_t have = std::min(left_a, left_b) / static_cast<size_t>(b) * static_cast<size_t>(b);
-        const int64_t done = data.accumulate_cross(in_a.data(), in_b.data(), have, in_a.per_piece(), piece);
-        if (done == 0) break;
-        for (size_t i = 0; i < 4 * N; ++i) planes[i] += piece[i];
-        frames += done;
-        const bool more_a = in_a.consume(done), more_b = in_b.consume(done);
-        if (!more_a || !more_b) {
-            left_a = in_a.fill();
-            left_b = in_b.fill();
-            break;
-        }
-    }
-    if (frames == 0)
-        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+    const int64_t frames = replay_pieces({&in_a, &in_b}, [&](size_t have) {
+        const int64_t done = data.accumulate_cross(in_a.data(), in_b.data(), have / b * b, in_a.per_piece(), piece);
+        for (size_t i = 0; done > 0 && i < 4 * N; ++i) planes[i] += piece[i];
+        return done;
+    }, left);
     const std::string end_stamp = Acquisition::utc_now();
     write_text_header_cross(std::cout, start_stamp, end_stamp);
     write_spectrum_text_cross(std::cout, planes, options.N, frames, tuned_freq, actual_samplerate, options.linear,
@@ -529,7 +544,7 @@ int run_cross(const Options& options, AuxData& aux, int actual_samplerate, int64
     std::cout << std::endl;          // (the blank line that closes a pass)
     // what is left of each file once the last common frame is taken: the same unless the lengths differ
     std::cerr << "Cross-spectrum: " << frames << " frames of " << options.N << " bins from each stream"
-              << (left_a != left_b ? " (the files differ in length: the whole frames of the shorter are used)" : "") << std::endl;
+              << (left[0] != left[1] ? " (the files differ in length: the whole frames of the shorter are used)" : "") << std::endl;
     if (chatty(options)) print_acquisition_summary(options.N, frames, 0, 0, actual_samplerate);
     return 0;
 }
@@ -541,7 +556,7 @@ int run_cross(const Options& options, AuxData& aux, int actual_samplerate, int64
 int run_stft(const Options& options, AuxData& aux, int actual_samplerate)
 {
     Datastore data(options, aux.window_values);
-    const int64_t b = options.sample_bytes();
+    const size_t b = static_cast<size_t>(options.sample_bytes());
     // (the frames of a piece by the engine's own rule: csrc/series_pieces.h, stft_pieces)
     const int64_t row_cap = rpf::stft_pieces(options.frame_bytes(), 8 * static_cast<size_t>(options.N)).per_piece;
     PieceReader in(options.input_file, b * options.span_samples(), b * options.step(), 1,
@@ -549,19 +564,13 @@ int run_stft(const Options& options, AuxData& aux, int actual_samplerate)
     std::ofstream out(options.stft_file, std::ios::out | std::ios::trunc | std::ios::binary);
     if (!out) throw RPFexception("Could not open " + options.stft_file + " for writing.", ReturnValue::InvalidInput);
     std::vector<float> rows;
-    int64_t frames = 0;
-    set_CtrlC_handler(true);
-    while (!checkInterrupt(InterruptState::FinishNow)) {
-        const size_t have = in.fill() / static_cast<size_t>(b) * static_cast<size_t>(b);
-        const int64_t done = data.stft(in.data(), have, in.per_piece(), rows);
-        if (done == 0) break;
+    const int64_t frames = replay_pieces({&in}, [&](size_t have) {
+        const int64_t done = data.stft(in.data(), have / b * b, in.per_piece(), rows);
+        if (done == 0) return done;
         out.write(reinterpret_cast<const char*>(rows.data()), static_cast<std::streamsize>(sizeof(float) * 2 * options.N * done));
         if (!out) throw RPFexception("Could not write to " + options.stft_file + ".", ReturnValue::InvalidInput);
-        frames += done;
-        if (!in.consume(done)) break;
-    }
-    if (frames == 0)
-        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+        return done;
+    });
     int lds = 0;
     (void)rpf_last_launch_info(data.engine(), nullptr, nullptr, nullptr, &lds);
     std::cerr << "STFT: " << frames << " frames of " << options.N << " bins, route: "
@@ -713,8 +722,7 @@ int run(int argc, char** argv)
     if (options.matrixMode) write_metadata(options, meta, last_repeats_done, actual_samplerate);
     if (plan.freqs_to_tune.empty())
         throw RPFexception("No valid frequencies left.", ReturnValue::AcquisitionError);
-    if (!wrote_anything)
-        throw RPFexception("No complete spectrum could be acquired (input too short?).", ReturnValue::AcquisitionError);
+    if (!wrote_anything) throw NoSpectrum();
     return 0;
 }
 
