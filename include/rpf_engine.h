@@ -332,7 +332,8 @@ int rpf_accumulate_cross(rpf_engine* e, const uint8_t* a, const uint8_t* b, size
  *     so one rounding) is bit for bit what rpf_accumulate_device of the same engine writes for that frame alone (repeats =
  *     1, the pointer at the frame), on either staging route and on both kernel routes: the power kernels add
  *     fma(im, im, re re) to zero and every later addition adds zeros.  (An engine whose power comes from another family
- *     -- mixed radix, four-step -- is tied to the power of the catch-all engine of its configuration, whose rows it gives.)
+ *     -- mixed radix, four-step, or the Bluestein kernels that serve cu8 below 64 bins -- is tied to the power of the
+ *     catch-all engine of its configuration, whose rows it gives.)
  *   Routes.  N = 64 .. 8192 (the K1 sizes), any format, window, frame step and staging: K1's store kernels
  *     (csrc/k1_stft_body.inc), one launch; rpf_last_launch_info reports it.  Every other power of two up to 2^26, and any
  *     size with RPF_FLAG_CATCH_ALL: the catch-all Stockham transform, whatever family serves the size for power, in
