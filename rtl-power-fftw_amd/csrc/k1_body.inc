@@ -37,7 +37,47 @@
     // cycles, an LDS-DMA instruction ~100-200).
     const long stride = static_cast<long>(gridDim.x) * FPW;
     long fb = static_cast<long>(blockIdx.x) * FPW;
-    if (fb < nframes) {
+    // LDW > 0: loader waves behind the WG / 64 compute waves stage every frame's bytes, and the compute waves issue no
+    // LDS-DMA and wait for none; the two roles meet at the workgroup's barriers only (k1_loader.h has the schedule).
+    static_assert(LDW == 0 || (DMA && TWLDS && BLOCK_SYNC && !DBUF && !STRIDED && !STATS && ABL == 0 && (WG / 64) % LDW == 0),
+                  "the loader takes the place of the LDS-DMA of a kernel with the barriers of k1_loader.h");
+    if constexpr (LDW > 0) {
+        if (wave >= WG / 64) {
+            constexpr int SERVED = k1_loader::waves_served(WG / 64, LDW);
+            constexpr int PPI = k1_loader::pieces_per_iteration(WG / 64, LDW, PIECES);
+            static_assert(k1_loader::prologue_wait(RAWD, PPI) <= k1_loader::kMaxCountedWait &&
+                          k1_loader::loop_wait(RAWD, PPI) <= k1_loader::kMaxCountedWait, "vmcnt is a 6-bit field");
+            const int w0 = (wave - WG / 64) * SERVED;      // the compute waves this loader stages for
+            if (fb < nframes) {
+#pragma unroll
+                for (int d = 0; d < RAWD; ++d)
+#pragma unroll
+                    for (int k = 0; k < SERVED; ++k)
+                        stage_raw<G, DMA, long, FMT>(stream, fb + d * stride, nframes,
+                                                     raw_base + (w0 + k) * (RAWD * RAW_SLOT) + d * RAW_SLOT, w0 + k, lane);
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(k1_loader::prologue_wait(RAWD, PPI)) : "memory");
+            }
+#pragma unroll
+            for (int b = 0; b < k1_loader::kPrologueBarriers; ++b) exchange_sync<true>();
+            for (int it = 0; fb < nframes; fb += stride, ++it) {
+                static_assert(k1_loader::kBarriersPerIteration == 2 && k1_loader::kRefillBarrier == 0 &&
+                              k1_loader::kLandedBarrier == 1, "the two barriers of the frame loop below");
+                exchange_sync<true>();                   // top of frame: every compute wave's unpack reads have returned
+                const int slot = k1_loader::slot_of(it, RAWD);
+#pragma unroll
+                for (int k = 0; k < SERVED; ++k)
+                    stage_raw<G, DMA, long, FMT>(stream, fb + (k1_loader::refill_iteration(it, RAWD) - it) * stride, nframes,
+                                                 raw_base + (w0 + k) * (RAWD * RAW_SLOT) + slot * RAW_SLOT, w0 + k, lane);
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(k1_loader::loop_wait(RAWD, PPI)) : "memory");
+                exchange_sync<true>();                   // pass-1 exchange: the next iteration's bytes have landed
+            }
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(k1_loader::kFlushWait) : "memory");   // nothing lands in the flush's LDS
+#pragma unroll
+            for (int b = 0; b < k1_loader::flush_barriers(STATS); ++b) exchange_sync<true>();
+            return;
+        }
+    }
+    if (LDW == 0 && fb < nframes) {
 #pragma unroll
         for (int d = 0; d < RAWD; ++d)
             if constexpr (STRIDED)
@@ -98,9 +138,10 @@
         {
             // this frame's bytes have landed: every iteration issues exactly PIECES DMA
             // instructions per wave, so all but the newest (RAWD-1) frames' worth are done
-            if constexpr (DMA && !(ABL & 8))
+            // (LDW > 0: they landed before the loader arrived at the barrier this wave passed last)
+            if constexpr (DMA && !(ABL & 8) && LDW == 0)
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RAWD - 1) * PIECES) : "memory");
-            exchange_sync<false>();
+            if constexpr (LDW == 0) exchange_sync<false>();
             RPF_STAMP(clk, 0);                   // waiting for the staged bytes
             if constexpr (WINDOW && !WREG) {
                 const float* wp = window + t;
@@ -113,13 +154,14 @@
             // that hits in L2/MALL can land before queued LDS reads execute -- seen as
             // sporadic 1e-3 errors), so wait for this wave's LDS reads, not just issue.
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            exchange_sync<false>();
+            if constexpr (LDW == 0) exchange_sync<false>();
             RPF_STAMP(clk, 1);                   // unpack
 #ifdef RPF_PHASE_TIMING
             if (it == 0) RPF_SEAM_MARK(1);
 #endif
-            // the slot has been consumed: refill it with the frame RAWD iterations ahead
-            if constexpr (!(ABL & 8)) {
+            // the slot has been consumed: refill it with the frame RAWD iterations ahead (LDW > 0: the loader does,
+            // behind the top-of-frame barrier below)
+            if constexpr (!(ABL & 8) && LDW == 0) {
                 if constexpr (STRIDED)
                     stage_raw_pitched<G, DMA, FMT, SBATCH>(stream, fb + RAWD * stride, nframes, pitch, ring_slot, wave, lane);
                 else
@@ -174,7 +216,7 @@
         RPF_STAMP(clk, 14);                      // accumulate
     }
     RPF_SEAM_MARK(2);
-    if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // trailing (clamped) prefetches
+    if constexpr (DMA && LDW == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // trailing (clamped) prefetches
     if constexpr (ACCP) {
 #pragma unroll
         for (int a = 0; a < P; ++a) acc[a] += static_cast<double>(acc32p[a].x) + static_cast<double>(acc32p[a].y);

@@ -8,6 +8,7 @@
 #include <initializer_list>
 #include <utility>
 
+#include "k1_loader.h"
 #include "k1_sizes.h"
 #include "rpf_device_common.h"
 #include "rpf_kernels.h"
@@ -89,13 +90,13 @@ __device__ __forceinline__ void stage_raw_pitched(const uint8_t* __restrict__ st
 // profiles/r03_k1_fixed_cost.txt -- so rpf_accumulate / rpf_accumulate_device keep it.)
 // STATS (RPF_FLAG_BIN_STATS, instantiated in rpf_kernels_stats*.hip only): two more double accumulators per bin, the
 // sum of the squared powers and the largest power, and three partial planes per workgroup (k1_body.inc).
+// LDW: loader waves (k1_loader.h).  The workgroup is launched with WG + 64 LDW threads; WG stays the threads that own
+// frames.  The waves per SIMD the register budget must admit follow from the launched size (nine or ten waves: three).
 template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
-          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8, bool STATS = false>
-__global__ __launch_bounds__(WG, OCC) void fft_accum_kernel(const uint8_t* __restrict__ stream,
-                                                            long nframes,
-                                                            const cf* __restrict__ twN,
-                                                            const float* __restrict__ window,
-                                                            double* __restrict__ partial)
+          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8, bool STATS = false, int LDW = 0>
+__global__ __launch_bounds__(WG + 64 * LDW, LDW ? (WG / 64 + LDW + 3) / 4 : OCC)
+void fft_accum_kernel(const uint8_t* __restrict__ stream, long nframes, const cf* __restrict__ twN,
+                      const float* __restrict__ window, double* __restrict__ partial)
 {
     constexpr bool STRIDED = false;
     constexpr long pitch = static_cast<long>(sample_bytes_of(FMT)) * G::N;     // (named by the discarded strided branches only)
@@ -115,6 +116,7 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_strided_kernel(const uint8_
                                                                     double* __restrict__ partial)
 {
     constexpr bool STRIDED = true;
+    constexpr int LDW = 0;
 #include "k1_body.inc"
 }
 
@@ -279,6 +281,7 @@ struct Variant {
     int N, vid, P;
     K1Geometry geo;
     bool partial_f32;
+    int single_ldw[2][2];    // loader waves of single[window][dma]: its launch is geo.with_loader(...); no other kernel has any
     SingleFn single[2][2];   // one acquisition per launch
     ScanFn scan[2][2];       // several hops per launch
     StridedFn strided[2][2]; // one acquisition of overlapped frames (frame pitch a kernel argument)
@@ -328,7 +331,7 @@ inline void fill_info(LaunchInfo* li, const K1Geometry& geo, int grid)
 {
     if (!li) return;
     li->grid = grid;
-    li->block = geo.WG;
+    li->block = geo.WG;               // the threads that own frames, loader waves not counted
     li->fpw = geo.fpw;
     li->lds_bytes = geo.lds_bytes;
 }
@@ -353,6 +356,14 @@ enum K1Kernels { kK1Plain, kK1Stats, kK1Series, kK1SeriesStats, kK1Stft };
      {KERNEL<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, __VA_ARGS__>,      \
       KERNEL<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, __VA_ARGS__>}}
 
+// ... of the single-acquisition kernel, whose LDS-DMA entry without a window alone takes the loader waves
+#define RPF_K1_SINGLE_FORMS(STATS)                                                                                  \
+    {{fft_accum_kernel<G, WG, OCC, false, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT, STATS, 0>,                 \
+      fft_accum_kernel<G, WG, OCC, false, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT, STATS, LDW>},               \
+     {fft_accum_kernel<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, FMT, STATS, 0>,                \
+      fft_accum_kernel<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, FMT, STATS, 0>}}
+#define RPF_K1_SINGLE_LDW {{0, LDW}, {0, 0}}
+
 // ... of a store kernel, whose template arguments are the plain kernels' without the accumulate ones
 #define RPF_K1_STFT_FORMS(KERNEL)                                                \
     {{KERNEL<G, WG, OCC, false, false, RAWD, TWLDS, FMT>,                         \
@@ -364,27 +375,29 @@ enum K1Kernels { kK1Plain, kK1Stats, kK1Series, kK1SeriesStats, kK1Stft };
 // for this N).
 template <int N, int P, int OCC, int OCCW = OCC, bool DBUF = false, int ACCB = 0, bool PF32 = false,
           int RAWD = 2, int ABL = 0, bool TWLDS = false, int WGO = 0, int FMT = kFmtCu8, bool TWLDSW = TWLDS,
-          K1Kernels KERNELS = kK1Plain>
+          K1Kernels KERNELS = kK1Plain, int LDW = 0>
 Variant make_variant(int vid)
 {
     using G = Geom<N, P>;
     constexpr K1Geometry geo = k1_geometry<G>(WGO, DBUF ? 2 : 1, RAWD, FMT, TWLDS || TWLDSW);
     constexpr int WG = geo.WG;
     if constexpr (KERNELS == kK1Stft)
-        return Variant{N, vid, P, geo, PF32, {}, {}, {}, {}, RPF_K1_STFT_FORMS(fft_stft_kernel),
+        return Variant{N, vid, P, geo, PF32, {}, {}, {}, {}, {}, RPF_K1_STFT_FORMS(fft_stft_kernel),
                        RPF_K1_STFT_FORMS(fft_stft_strided_kernel)};
     else if constexpr (KERNELS == kK1Series)
-        return Variant{N, vid, P, geo, PF32, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_kernel, FMT)};
+        return Variant{N, vid, P, geo, PF32, {}, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_kernel, FMT)};
     else if constexpr (KERNELS == kK1SeriesStats)
-        return Variant{N, vid, P, geo, PF32, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_stats_kernel, FMT)};
+        return Variant{N, vid, P, geo, PF32, {}, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_stats_kernel, FMT)};
     else if constexpr (KERNELS == kK1Stats)
-        return Variant{N, vid, P, geo, PF32, RPF_K1_FORMS(fft_accum_kernel, FMT, true), {},
+        return Variant{N, vid, P, geo, PF32, RPF_K1_SINGLE_LDW, RPF_K1_SINGLE_FORMS(true), {},
                        RPF_K1_FORMS(fft_accum_strided_kernel, FMT, true), {}};
     else
-        return Variant{N, vid, P, geo, PF32, RPF_K1_FORMS(fft_accum_kernel, FMT, false),
+        return Variant{N, vid, P, geo, PF32, RPF_K1_SINGLE_LDW, RPF_K1_SINGLE_FORMS(false),
                        RPF_K1_FORMS(fft_accum_scan_kernel, FMT), RPF_K1_FORMS(fft_accum_strided_kernel, FMT, false), {}};
 }
 #undef RPF_K1_FORMS
+#undef RPF_K1_SINGLE_FORMS
+#undef RPF_K1_SINGLE_LDW
 #undef RPF_K1_STFT_FORMS
 
 // Variant 0 of every row of the size table for one sample format and one set of kernels, and its look-up by N.
@@ -394,7 +407,8 @@ Variant default_variant()
     constexpr K1Size s = k1_size(I, FMT, KERNELS == kK1Stats || KERNELS == kK1SeriesStats);
     static_assert(k1_geometry<Geom<s.N, s.P>>(s.WGO, 1, s.RAWD, FMT, s.TWLDS || s.TWLDSW).lds_bytes <= kLdsPerCU,
                   "a workgroup's LDS fits the CU");
-    return make_variant<s.N, s.P, s.OCC, s.OCCW, false, 0, false, s.RAWD, 0, s.TWLDS, s.WGO, FMT, s.TWLDSW, KERNELS>(0);
+    return make_variant<s.N, s.P, s.OCC, s.OCCW, false, 0, false, s.RAWD, 0, s.TWLDS, s.WGO, FMT, s.TWLDSW, KERNELS,
+                        s.LDW>(0);
 }
 template <K1Kernels KERNELS, int FMT, int... I>
 const Variant* find_default_variant(int N, std::integer_sequence<int, I...>)

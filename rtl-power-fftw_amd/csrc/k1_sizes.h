@@ -15,11 +15,14 @@ namespace rpf {
 // TWLDS  the twiddles of the passes after the first in an LDS table instead of registers; TWLDSW: windowed kernels
 //        (k1_size sets it: TWLDS, but for one statistics kernel)
 // WGO    workgroup size; 0 = max(T, 256).  A larger one runs more frames side by side.
+// LDW    loader waves launched behind the WGO threads (k1_loader.h): the single-acquisition kernel that stages by
+//        LDS-DMA without a window takes them, every other kernel of the row has none (k1_size sets it)
 struct K1Size {
     int N, P, OCC, OCCW, RAWD;
     bool TWLDS;
     int WGO;
     bool TWLDSW = false;
+    int LDW = 0;
 };
 
 constexpr int kRingSmall = 0;
@@ -42,8 +45,12 @@ constexpr K1Size kK1Sizes[] = {
 constexpr int kK1SizeCount = sizeof(kK1Sizes) / sizeof(kK1Sizes[0]);
 
 // What the host needs to launch a K1-shaped kernel: workgroup size, frames side by side in it, dynamic LDS.
+// WG counts the threads that own frames; `launched` is what the launch asks for, WG + 64 per loader wave (with_loader:
+// the geometry of a variant's one entry that has them).
 struct K1Geometry {
     int WG, fpw, lds_bytes;
+    int launched;
+    constexpr K1Geometry with_loader(int ldw) const { return K1Geometry{WG, fpw, lds_bytes, WG + 64 * ldw}; }
 };
 
 // The workgroup size and the LDS of its frame slots (slabs and raw ring, all but the twiddle table) from plain values,
@@ -64,7 +71,8 @@ constexpr K1Geometry k1_geometry(int wgo, int slabs, int rawd, int fmt, bool twt
     const int wg = k1_workgroup(G::N, G::P, wgo);
     return K1Geometry{wg, wg / G::T,
                       k1_slots_lds(G::N, G::P, wgo, slabs, rawd, fmt) +
-                          (twtable ? twlds_entries<G>() * static_cast<int>(sizeof(cf)) : 0)};
+                          (twtable ? twlds_entries<G>() * static_cast<int>(sizeof(cf)) : 0),
+                      wg};
 }
 
 // kRingSmall, the tiny frames of N <= 256: four frames in flight with 2-byte samples, two with cs16's 4-byte samples,
@@ -77,6 +85,13 @@ constexpr int ring_depth(int rawd, int fmt)
 }
 
 constexpr int kLdsPerCU = 160 * 1024;
+// RPF_K1_LOADER_WAVES (A/B builds, `make kvariant KFLAGS=-DRPF_K1_LOADER_WAVES=1`): the loader waves of the 4096 row.
+// Two, one per frame slot: with one, its sixteen pieces per iteration were the new critical path and the gain stayed
+// inside the run-to-run range; none is the kernel before the loader (profiles/k1_loader.json).
+#ifndef RPF_K1_LOADER_WAVES
+#define RPF_K1_LOADER_WAVES 2
+#endif
+constexpr int kLoaderWaves4096 = RPF_K1_LOADER_WAVES;
 
 // Row i as the kernels of sample format `fmt` take it; stats: the kernels with per-bin statistics
 // (RPF_FLAG_BIN_STATS), which depart from the table where the registers run out.  Three double accumulators per bin
@@ -111,6 +126,9 @@ constexpr K1Size k1_size(int i, int fmt, bool stats)
     if (fmt == kFmtCf32 && (s.N == 128 || s.N == 256)) s.OCCW = 2;
     if (fmt == kFmtCf32 && s.N == 1024) s.OCC = 2;
     s.TWLDSW = s.TWLDS;
+    // The loader wave: measured at 4096 with cu8 alone (profiles/k1_loader.json); every other row, format and kernel
+    // keeps the LDS-DMA in its compute waves.
+    s.LDW = (s.N == 4096 && fmt == kFmtCu8 && !stats) ? kLoaderWaves4096 : 0;
     if (stats) {
         if (s.N == 128 || s.N == 256 || s.N == 1024) s.OCC = s.OCCW = 2;
         if (s.N == 512) s.OCCW = 3;

@@ -212,7 +212,8 @@ Variant make_mfma_variant(int vid)
     return v;
 }
 
-// Template arguments after <N, P>: OCC, OCCW, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, WGO (k1_kernels.h, make_variant)
+// Template arguments after <N, P>: OCC, OCCW, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, WGO, FMT, TWLDSW, KERNELS, LDW
+// (k1_kernels.h, make_variant)
 const Variant kTuningVariants[] = {
     // Lab equipment, compiled only into the -DRPF_TUNING build (make tuning ->
     // librpf_engine_tuning.so, used by tools/): in the shipped library every N has exactly
@@ -241,6 +242,11 @@ const Variant kTuningVariants[] = {
     make_variant<4096, 16, 2, 2, false, 0, false, 2, 0, false, 512>(53),
     make_variant<4096, 16, 2, 2, false, 0, false, 4, 0, false, 512>(54),
     make_variant<2048, 16, 2, 2, false, 0, false, 4, 0, true, 512>(51),
+    // loader waves behind the eight compute waves (k1_loader.h): one, and one per frame slot -- the size table's own
+    // kernel under a number of its own (profiles/k1_loader.json)
+    make_variant<4096, 16, 2, 2, false, 0, false, 2, 0, true, 512, kFmtCu8, true, kK1Plain, 1>(70),
+    make_variant<4096, 16, 2, 2, false, 0, false, 2, 0, true, 512, kFmtCu8, true, kK1Plain, 2>(71),
+    make_variant<4096, 16, 2, 2, false, 0, false, 2, 0, true, 512, kFmtCu8, true, kK1Plain, 0>(72),    // no loader: variant 0 before it
     make_mfma_variant<4096, 16, 2, 512, 2>(60),              // first pass on the matrix pipe (exact, slower: see the kernel)
     make_variant<512, 8, 4, 4, false, 0, false, 4>(1),  make_variant<512, 8, 4, 4, false, 0, false, 8>(2),
     make_variant<512, 16, 3, 3, false, 0, false, 2>(3),

@@ -88,9 +88,14 @@ __device__ __forceinline__ void store_partial2(double* p, partial2_t v)
 // wave's LDS operations only (lgkmcnt): __syncthreads() would also drain vmcnt
 // and with it the LDS-DMA prefetch of the coming frames, exposing the full HBM
 // latency once per frame (measured: 3/4 of the kernel time).  LDS-DMA data is
-// ordered by the issuing wave's own counted vmcnt wait, and a wave only ever
-// reads bytes it staged itself.  Exchanges inside one wavefront need only a
-// compiler fence (one wavefront's DS instructions execute in order).
+// ordered by the issuing wave's own counted vmcnt wait.  Without loader waves a
+// wave only ever reads bytes it staged itself, and that wait is all it needs.
+// With them (k1_loader.h) the bytes a compute wave unpacks were staged by a
+// loader wave: the loader's counted wait followed by an s_barrier of this
+// function that both waves arrive at orders them, and the lgkmcnt(0) here is
+// what lets the loader refill a slot once the readers have arrived.  Exchanges
+// inside one wavefront need only a compiler fence (one wavefront's DS
+// instructions execute in order).
 template <bool BLOCK>
 __device__ __forceinline__ void exchange_sync()
 {

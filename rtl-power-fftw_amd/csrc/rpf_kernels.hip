@@ -299,7 +299,7 @@ hipError_t plan_resident_grid(std::initializer_list<const void*> kernels, const 
         hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, geo.lds_bytes);
         if (err != hipSuccess) return err;
         int n = 0;
-        err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, geo.WG, geo.lds_bytes);
+        err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, geo.launched, geo.lds_bytes);
         if (err != hipSuccess) return err;
         per_cu = std::min(per_cu, n);
     }
@@ -315,13 +315,16 @@ hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, La
     const Variant* v = find_variant(N, vid, fmt, stats);
     if (!v) return hipErrorInvalidValue;
     const int w = window ? 1 : 0, d = use_dma ? 1 : 0;
-    int grid = 0;
-    // the single-acquisition, scan and strided instantiations share one grid (the statistics kernels have no scan form)
-    hipError_t err = plan_resident_grid({reinterpret_cast<const void*>(v->single[w][d]),
-                                         reinterpret_cast<const void*>(v->scan[w][d]),
-                                         reinterpret_cast<const void*>(v->strided[w][d])}, v->geo, device, &grid);
+    int grid = 0, grid1 = 0;
+    // the single-acquisition, scan and strided instantiations share one grid (the statistics kernels have no scan
+    // form): the smaller of what the single kernel admits at its launched size, loader waves included, and the others
+    hipError_t err = plan_resident_grid({reinterpret_cast<const void*>(v->single[w][d])},
+                                        v->geo.with_loader(v->single_ldw[w][d]), device, &grid1);
     if (err != hipSuccess) return err;
-    fill_info(li, *v, grid);
+    err = plan_resident_grid({reinterpret_cast<const void*>(v->scan[w][d]),
+                              reinterpret_cast<const void*>(v->strided[w][d])}, v->geo, device, &grid);
+    if (err != hipSuccess) return err;
+    fill_info(li, *v, std::min(grid, grid1));
     return hipSuccess;
 }
 
@@ -333,10 +336,11 @@ hipError_t launch_fft_accum(int N, int vid, bool window, bool use_dma, const uin
     const long sb = sample_bytes_of(fmt);
     if (!v || grid < 1 || pitch < 0 || pitch > sb * N || (pitch % sb)) return hipErrorInvalidValue;
     if (pitch == 0 || pitch == sb * N)
-        hipLaunchKernelGGL(v->single[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->geo.WG), v->geo.lds_bytes,
-                           stream, d_stream, nframes, d_twiddles, d_window, d_partial);
+        hipLaunchKernelGGL(v->single[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid),
+                           dim3(v->geo.with_loader(v->single_ldw[window ? 1 : 0][use_dma ? 1 : 0]).launched),
+                           v->geo.lds_bytes, stream, d_stream, nframes, d_twiddles, d_window, d_partial);
     else
-        hipLaunchKernelGGL(v->strided[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->geo.WG), v->geo.lds_bytes,
+        hipLaunchKernelGGL(v->strided[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->geo.launched), v->geo.lds_bytes,
                            stream, d_stream, nframes, pitch, d_twiddles, d_window, d_partial);
     fill_info(li, *v, grid);
     return hipGetLastError();
@@ -348,7 +352,7 @@ hipError_t launch_fft_accum_hops(int N, int vid, bool window, bool use_dma, cons
 {
     const Variant* v = find_variant(N, vid, fmt);
     if (!v || grid < 1 || hops.H < 1 || hops.H > kMaxHops || grid > hops.total) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(v->scan[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->geo.WG), v->geo.lds_bytes, stream,
+    hipLaunchKernelGGL(v->scan[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->geo.launched), v->geo.lds_bytes, stream,
                        d_twiddles, d_window, d_partial, hops);
     fill_info(li, *v, grid);
     return hipGetLastError();

@@ -8,7 +8,9 @@ between two builds:
 The library's .hip_fatbin section holds one offload bundle per translation unit; each is unbundled for gfx950 and
 disassembled (llvm-objdump -d, addresses and encodings dropped, so only mnemonics and operands count).  Kernels are
 matched by demangled name; the trailing `, false` a defaulted `bool STATS` adds to the two K1 kernel templates'
-argument lists is dropped before matching, so that a build with that parameter can be compared with one before it."""
+argument lists is dropped before matching, so that a build with that parameter can be compared with one before it;
+so is the `, 0` of the defaulted `int LDW` behind it (a kernel with loader waves keeps its `, 1` or `, 2`: it is a new
+kernel, and the one it replaced is reported as different or missing)."""
 import hashlib
 import json
 import os
@@ -52,6 +54,8 @@ def streams(lib):
     plain = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines()
     res = {}
     for mangled, name in zip(names, plain):
+        if "fft_accum_kernel<" in name:
+            name = re.sub(r", (false|true), 0>\(", r", \1>(", name)      # the defaulted `int LDW` behind STATS
         if "fft_accum_kernel<" in name or "fft_accum_strided_kernel<" in name:
             name = re.sub(r", false>\(", ">(", name)
         res[name] = (hashlib.sha256("\n".join(out[mangled]).encode()).hexdigest(), len(out[mangled]))
