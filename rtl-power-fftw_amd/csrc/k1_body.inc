@@ -1,20 +1,20 @@
 // k1_body.inc -- the body of K1 (rpf_kernels.hip), included by its two kernels: fft_accum_kernel (frame f at byte
 // 2N f) and fft_accum_strided_kernel (frame f at byte f * pitch, overlapped frames).  The includer declares
-// `constexpr bool STRIDED` and, when it is true, has the kernel argument `long pitch`.  An include rather than a
-// force-inlined device function: the plain kernels then compile to the instruction stream they had before the
-// strided form existed (an inlined body changed their schedules).  `STATS` (a template argument of both, false
-// everywhere but in rpf_kernels_stats*.hip) adds the per-bin statistics; with it false nothing below changes what the
-// plain kernels compile to (tools/kernel_streams.py compares the instruction streams of two builds).
+// `constexpr bool STRIDED` and `pitch`: a constexpr long in the plain kernel, the kernel argument `long pitch` in the
+// strided one.  An include rather than a force-inlined device function: the plain kernels then compile to the
+// instruction stream they had before the strided form existed (an inlined body changed their schedules).  `STATS` (a
+// template argument of both, false everywhere but in rpf_kernels_stats*.hip) adds the per-bin statistics; with it
+// false nothing below changes what the plain kernels compile to (tools/kernel_streams.py compares the instruction
+// streams of two builds).
     RPF_SEAM_MARK(0);                            // (timing builds only)
     constexpr int P = G::P, T = G::T, N = G::N, NPASS = G::NPASS;
     constexpr int FPW = WG / T;
-    constexpr int NSLAB = DBUF ? 2 : 1;
     constexpr bool BLOCK_SYNC = (T > 64);
     static_assert(WG % T == 0 && WG % 64 == 0, "");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    cf* const slab_base = reinterpret_cast<cf*>(smem);                        // [NSLAB][FPW][LDS_CPX]
-    uint8_t* const raw_base = smem + NSLAB * FPW * G::LDS_CPX * sizeof(cf);  // [WG/64][RAWD][RAW_SLOT] bytes
+    cf* const slab_base = reinterpret_cast<cf*>(smem);                        // [FPW][LDS_CPX]
+    uint8_t* const raw_base = smem + FPW * G::LDS_CPX * sizeof(cf);          // [WG/64][RAWD][RAW_SLOT] bytes
 
     const int tid = threadIdx.x;
     const int fs = tid / T, t = tid % T;
@@ -39,7 +39,7 @@
     long fb = static_cast<long>(blockIdx.x) * FPW;
     // LDW > 0: loader waves behind the WG / 64 compute waves stage every frame's bytes, and the compute waves issue no
     // LDS-DMA and wait for none; the two roles meet at the workgroup's barriers only (k1_loader.h has the schedule).
-    static_assert(LDW == 0 || (DMA && TWLDS && BLOCK_SYNC && !DBUF && !STRIDED && !STATS && ABL == 0 && (WG / 64) % LDW == 0),
+    static_assert(LDW == 0 || (DMA && TWLDS && BLOCK_SYNC && !STRIDED && !STATS && ABL == 0 && (WG / 64) % LDW == 0),
                   "the loader takes the place of the LDS-DMA of a kernel with the barriers of k1_loader.h");
     if constexpr (LDW > 0) {
         if (wave >= WG / 64) {
@@ -53,7 +53,7 @@
                 for (int d = 0; d < RAWD; ++d)
 #pragma unroll
                     for (int k = 0; k < SERVED; ++k)
-                        stage_raw<G, DMA, long, FMT>(stream, fb + d * stride, nframes,
+                        stage_raw<G, DMA, long, FMT>(stream, fb + d * stride, nframes, pitch,
                                                      raw_base + (w0 + k) * (RAWD * RAW_SLOT) + d * RAW_SLOT, w0 + k, lane);
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(k1_loader::prologue_wait(RAWD, PPI)) : "memory");
             }
@@ -67,7 +67,7 @@
 #pragma unroll
                 for (int k = 0; k < SERVED; ++k)
                     stage_raw<G, DMA, long, FMT>(stream, fb + (k1_loader::refill_iteration(it, RAWD) - it) * stride, nframes,
-                                                 raw_base + (w0 + k) * (RAWD * RAW_SLOT) + slot * RAW_SLOT, w0 + k, lane);
+                                                 pitch, raw_base + (w0 + k) * (RAWD * RAW_SLOT) + slot * RAW_SLOT, w0 + k, lane);
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(k1_loader::loop_wait(RAWD, PPI)) : "memory");
                 exchange_sync<true>();                   // pass-1 exchange: the next iteration's bytes have landed
             }
@@ -80,10 +80,7 @@
     if (LDW == 0 && fb < nframes) {
 #pragma unroll
         for (int d = 0; d < RAWD; ++d)
-            if constexpr (STRIDED)
-                stage_raw_pitched<G, DMA, FMT, SBATCH>(stream, fb + d * stride, nframes, pitch, wave_raw + d * RAW_SLOT, wave, lane);
-            else
-                stage_raw<G, DMA, long, FMT, SBATCH>(stream, fb + d * stride, nframes, wave_raw + d * RAW_SLOT, wave, lane);
+            stage_raw<G, DMA, long, FMT, SBATCH>(stream, fb + d * stride, nframes, pitch, wave_raw + d * RAW_SLOT, wave, lane);
     }
 
     // Loop-invariant per-thread constants: twiddles, sign, window.
@@ -100,38 +97,23 @@
 #pragma unroll
         for (int a = 0; a < P; ++a) wsgn[a] = window[t + T * a] * sgn;
     }
-    // ACCB (tuning variants only): |X|^2 is first summed over ACCB frames in float32, then added to the double
-    // accumulators.  1 .. 99: one float per bin (two v_fma_f32; round 3's variant 22); 100 + n (round 6, VERDICT r05 item
-    // 4 i): PACKED, (re^2, im^2) kept apart in one register pair per bin -- ONE v_pk_fma_f32 per bin and frame -- over n
-    // frames.  Both depart from the reference's "square and sum in double" (datastore.cxx:83-85); neither is shipped.
-    constexpr bool ACCP = ACCB >= 100;
-    constexpr int ACCN = ACCP ? ACCB - 100 : ACCB;
     double acc[P];
-    float acc32[ACCB > 0 && !ACCP ? P : 1];
-    cf acc32p[ACCP ? P : 1];
 #pragma unroll
     for (int a = 0; a < P; ++a) acc[a] = 0.0;
     // STATS: the sum of the squared powers and the peak power of every bin beside acc (fft_core.h,
     // phase_accumulate_stats); the peak starts from 0, which no power is below.
-    static_assert(!STATS || (ACCB == 0 && !PF32 && ABL == 0), "the tuning paths do not combine with the statistics");
+    static_assert(!STATS || ABL == 0, "the ablations do not combine with the statistics");
     double acc_s2[STATS ? P : 1], acc_pk[STATS ? P : 1];
     if constexpr (STATS) {
 #pragma unroll
         for (int a = 0; a < P; ++a) acc_s2[a] = acc_pk[a] = 0.0;
-    }
-    if constexpr (ACCP) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) acc32p[a] = cf{0.0f, 0.0f};
-    } else if constexpr (ACCB > 0) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) acc32[a] = 0.0f;
     }
 
     PhaseClock clk;
     clk.start();
     for (int it = 0; fb < nframes; fb += stride, ++it) {
         const bool active = (fb + fs) < nframes;
-        cf* const slab = slab_base + ((DBUF ? (it & 1) : 0) * FPW + fs) * G::LDS_CPX;
+        cf* const slab = slab_base + fs * G::LDS_CPX;
         uint8_t* const ring_slot = wave_raw + (it % RAWD) * RAW_SLOT;
         cf x[P];
 
@@ -161,17 +143,13 @@
 #endif
             // the slot has been consumed: refill it with the frame RAWD iterations ahead (LDW > 0: the loader does,
             // behind the top-of-frame barrier below)
-            if constexpr (!(ABL & 8) && LDW == 0) {
-                if constexpr (STRIDED)
-                    stage_raw_pitched<G, DMA, FMT, SBATCH>(stream, fb + RAWD * stride, nframes, pitch, ring_slot, wave, lane);
-                else
-                    stage_raw<G, DMA, long, FMT, SBATCH>(stream, fb + RAWD * stride, nframes, ring_slot, wave, lane);
-            }
+            if constexpr (!(ABL & 8) && LDW == 0)
+                stage_raw<G, DMA, long, FMT, SBATCH>(stream, fb + RAWD * stride, nframes, pitch, ring_slot, wave, lane);
             RPF_STAMP(clk, 3);                   // DMA issue
         }
 
-        // single slab: every wave must be done with the previous frame's slab
-        if constexpr (!DBUF) exchange_sync<BLOCK_SYNC>();
+        // one slab: every wave must be done with the previous frame's slab
+        exchange_sync<BLOCK_SYNC>();
         RPF_STAMP(clk, 2);                       // top-of-frame barrier
         middle_passes<G, 1, ABL, TWLDS>(t, x, tw, slab, clk, twtable);   // stamps 4J..4J+3
         if constexpr (!(ABL & 4)) phase_fetch<G, NPASS>(t, x, slab);
@@ -179,33 +157,7 @@
         RPF_STAMP(clk, 12);                      // last fetch
         if constexpr (!(ABL & 2)) phase_last<G>(x);
         RPF_STAMP(clk, 13);                      // last butterfly
-        if constexpr (ACCP) {
-            if (active) {
-#pragma unroll
-                for (int a = 0; a < P; ++a)
-                    asm("v_pk_fma_f32 %0, %1, %1, %0" : "+v"(acc32p[a]) : "v"(x[a]));
-            }
-            if ((it % ACCN) == ACCN - 1) {
-#pragma unroll
-                for (int a = 0; a < P; ++a) {
-                    acc[a] += static_cast<double>(acc32p[a].x) + static_cast<double>(acc32p[a].y);
-                    acc32p[a] = cf{0.0f, 0.0f};
-                }
-            }
-        } else if constexpr (ACCB > 0) {
-            if (active) {
-#pragma unroll
-                for (int a = 0; a < P; ++a)
-                    acc32[a] = __builtin_fmaf(x[a].x, x[a].x, __builtin_fmaf(x[a].y, x[a].y, acc32[a]));
-            }
-            if ((it % ACCB) == ACCB - 1) {
-#pragma unroll
-                for (int a = 0; a < P; ++a) {
-                    acc[a] += static_cast<double>(acc32[a]);
-                    acc32[a] = 0.0f;
-                }
-            }
-        } else if constexpr (ABL & 1) {
+        if constexpr (ABL & 1) {
 #pragma unroll
             for (int a = 0; a < P; ++a) asm volatile("" ::"v"(x[a]));
         } else if constexpr (STATS) {
@@ -217,13 +169,6 @@
     }
     RPF_SEAM_MARK(2);
     if constexpr (DMA && LDW == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // trailing (clamped) prefetches
-    if constexpr (ACCP) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) acc[a] += static_cast<double>(acc32p[a].x) + static_cast<double>(acc32p[a].y);
-    } else if constexpr (ACCB > 0) {
-#pragma unroll
-        for (int a = 0; a < P; ++a) acc[a] += static_cast<double>(acc32[a]);
-    }
 
     // One partial spectrum per workgroup (the FPW frame slots are summed here);
     // every workgroup writes its partial, zeros included.  The accumulators go
@@ -265,26 +210,17 @@
             stage[fs * SN + bin + (bin >> 4)] = acc[a];
         }
         exchange_sync<true>();
-        if constexpr (PF32) {
-            for (int bin = tid; bin < N; bin += WG) {
-                double v = 0.0;
+        // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
+        // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
+        // Written through (store_partial2): 32 KB per workgroup that K3 reads from another XCD.
+        for (int bin = 2 * tid; bin < N; bin += 2 * WG) {
+            partial2_t v = {0.0, 0.0};
 #pragma unroll
-                for (int k = 0; k < FPW; ++k) v += stage[k * SN + bin + (bin >> 4)];
-                reinterpret_cast<float*>(partial)[static_cast<size_t>(blockIdx.x) * N + bin] = static_cast<float>(v);
+            for (int k = 0; k < FPW; ++k) {
+                v.x += stage[k * SN + bin + (bin >> 4)];
+                v.y += stage[k * SN + bin + 1 + (bin >> 4)];
             }
-        } else {
-            // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
-            // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
-            // Written through (store_partial2): 32 KB per workgroup that K3 reads from another XCD.
-            for (int bin = 2 * tid; bin < N; bin += 2 * WG) {
-                partial2_t v = {0.0, 0.0};
-#pragma unroll
-                for (int k = 0; k < FPW; ++k) {
-                    v.x += stage[k * SN + bin + (bin >> 4)];
-                    v.y += stage[k * SN + bin + 1 + (bin >> 4)];
-                }
-                store_partial2(partial + static_cast<size_t>(blockIdx.x) * N + bin, v);
-            }
+            store_partial2(partial + static_cast<size_t>(blockIdx.x) * N + bin, v);
         }
     }
     RPF_SEAM_DRAIN();

@@ -27,16 +27,17 @@ namespace {
 // s_waitcnt vmcnt(N) at the top of the frame loop stays exact.
 // IDX: the frame index type -- long in the single-acquisition kernel, int in the
 // scan kernel (a hop's frames; one 64-bit multiply less per DMA instruction).
+// pitch: bytes from one frame's start to the next -- a compile-time b N in every kernel but the strided ones, whose
+// frames of a stream with frame step S < N (rpf_config::frame_step) lie b S apart (a kernel argument).
 // FMT: the sample format (fft_core.h); 4-byte samples double the pieces and the frame, cf32's 8-byte samples double
 // them again (P / 2 pieces: 8 at P = 16, under the 6-bit vmcnt field at every ring depth in use).
 // BATCH > 0 (VGPR staging of the windowed cf32 kernels with statistics only, k1_body.inc): no more than BATCH 16-byte
 // loads in flight, the pieces go to LDS batch by batch; 0, everywhere else: the compiler's own order, all at once.
 template <class G, bool DMA, typename IDX, int FMT = kFmtCu8, int BATCH = 0>
-__device__ __forceinline__ void stage_raw(const uint8_t* __restrict__ stream, IDX fb, IDX nframes,
+__device__ __forceinline__ void stage_raw(const uint8_t* __restrict__ stream, IDX fb, IDX nframes, long pitch,
                                           uint8_t* wave_raw, int wave, int lane)
 {
     constexpr int PIECES = G::P / 8 * (sample_bytes_of(FMT) / 2);
-    constexpr int FRAME_BYTES = sample_bytes_of(FMT) * G::N;
 #pragma unroll
     for (int i = 0; i < PIECES; ++i) {
         const int j = i * 1024 + lane * 16;
@@ -44,35 +45,9 @@ __device__ __forceinline__ void stage_raw(const uint8_t* __restrict__ stream, ID
         raw_source<G, FMT>(wave, j, &slot, &off);
         IDX f = fb + slot;
         f = f < nframes ? f : nframes - 1;
-        const uint8_t* src = stream + static_cast<long>(f) * FRAME_BYTES + off;
+        const uint8_t* src = stream + static_cast<long>(f) * pitch + off;
         if constexpr (DMA) {
             // LDS address = wave-uniform base + 16 * lane (added by the hardware)
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(wave_raw + i * 1024), 16, 0, 0);
-        } else {
-            *reinterpret_cast<uint4*>(wave_raw + j) = *reinterpret_cast<const uint4*>(src);
-            if constexpr (BATCH > 0) {
-                if ((i + 1) % BATCH == 0) asm volatile("" ::: "memory");
-            }
-        }
-    }
-}
-
-// The same at a run-time frame pitch (bytes from one frame's start to the next): the frames of a stream with frame
-// step S < N (rpf_config::frame_step) lie 2S apart.  Only the strided K1 uses it.
-template <class G, bool DMA, int FMT = kFmtCu8, int BATCH = 0>
-__device__ __forceinline__ void stage_raw_pitched(const uint8_t* __restrict__ stream, long fb, long nframes, long pitch,
-                                                  uint8_t* wave_raw, int wave, int lane)
-{
-    constexpr int PIECES = G::P / 8 * (sample_bytes_of(FMT) / 2);
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-        const int j = i * 1024 + lane * 16;
-        int slot, off;
-        raw_source<G, FMT>(wave, j, &slot, &off);
-        long f = fb + slot;
-        f = f < nframes ? f : nframes - 1;
-        const uint8_t* src = stream + f * pitch + off;
-        if constexpr (DMA) {
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(wave_raw + i * 1024), 16, 0, 0);
         } else {
             *reinterpret_cast<uint4*>(wave_raw + j) = *reinterpret_cast<const uint4*>(src);
@@ -92,14 +67,14 @@ __device__ __forceinline__ void stage_raw_pitched(const uint8_t* __restrict__ st
 // sum of the squared powers and the largest power, and three partial planes per workgroup (k1_body.inc).
 // LDW: loader waves (k1_loader.h).  The workgroup is launched with WG + 64 LDW threads; WG stays the threads that own
 // frames.  The waves per SIMD the register budget must admit follow from the launched size (nine or ten waves: three).
-template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
-          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8, bool STATS = false, int LDW = 0>
+template <class G, int WG, int OCC, bool WINDOW, bool DMA, int RAWD = 2, int ABL = 0, bool TWLDS = false,
+          int FMT = kFmtCu8, bool STATS = false, int LDW = 0>
 __global__ __launch_bounds__(WG + 64 * LDW, LDW ? (WG / 64 + LDW + 3) / 4 : OCC)
 void fft_accum_kernel(const uint8_t* __restrict__ stream, long nframes, const cf* __restrict__ twN,
                       const float* __restrict__ window, double* __restrict__ partial)
 {
     constexpr bool STRIDED = false;
-    constexpr long pitch = static_cast<long>(sample_bytes_of(FMT)) * G::N;     // (named by the discarded strided branches only)
+    constexpr long pitch = static_cast<long>(sample_bytes_of(FMT)) * G::N;     // frames side by side (stage_raw)
 #include "k1_body.inc"
 }
 
@@ -107,8 +82,8 @@ void fft_accum_kernel(const uint8_t* __restrict__ stream, long nframes, const cf
 // to workgroup (f / FPW) mod grid, so neighbouring frames -- which share most of their bytes -- are staged by the
 // same workgroup a few iterations apart and the shared bytes come back from L2.  A separate instantiation: the
 // plain kernel keeps its compile-time 2N.
-template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
-          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8, bool STATS = false>
+template <class G, int WG, int OCC, bool WINDOW, bool DMA, int RAWD = 2, int ABL = 0, bool TWLDS = false,
+          int FMT = kFmtCu8, bool STATS = false>
 __global__ __launch_bounds__(WG, OCC) void fft_accum_strided_kernel(const uint8_t* __restrict__ stream,
                                                                     long nframes, long pitch,
                                                                     const cf* __restrict__ twN,
@@ -173,29 +148,20 @@ struct HopLanes {
 __device__ __forceinline__ double* series_rows(const HopArgs&) { return nullptr; }
 __device__ __forceinline__ double* series_rows(const SeriesArgs& a) { return a.out; }
 
-// DBUF: two slabs used alternately.  With one slab the pass-1 store of frame f+1
-// must wait (workgroup barrier at the top of the loop) until every wave has
-// finished reading frame f's slab; with two, the single barrier after the pass-1
-// store orders both hazards and a frame costs one s_barrier instead of two, at
-// the price of LDS (fewer resident workgroups).
+// One exchange slab per frame slot: the pass-1 store of frame f+1 waits (workgroup
+// barrier at the top of the loop) until every wave has finished reading frame f's slab.
 //
 // RAWD: depth of the raw-byte ring = iterations staged ahead by LDS-DMA.  The HBM
 // latency seen by a DMA under load is several frame times (measured ~3 us vs
 // ~1 us of butterflies per frame), so one frame ahead leaves the workgroup idle
 // most of the time; RAWD iterations ahead keep RAWD x 2N bytes per frame slot in flight.
-// ACCB > 0 (tuning variants): |X|^2 is first summed over ACCB frames in packed
-// float32 (one v_pk_fma_f32 per bin instead of four half-rate f64 instructions)
-// and only then folded into the f64 accumulators -- adds <= ~1e-7 relative error
-// per batch, averaged down over the batches.  PF32: partial spectra leave as
-// float32 (half the flush and K3 traffic; each partial is a sum over ~13 frames
-// and there are hundreds of them, so the rounding averages out to ~1e-9).
 //
 // One launch walks the hops of `hops` (a single acquisition is H = 1): workgroup w owns the
 // iterations [w I / G, (w + 1) I / G) of the launch's sequence and writes one partial spectrum
 // per hop it touched (slot = slot_bias[h] + w), zeroing its register accumulators in between
 // -- the reference's per-hop reset (acquisition.cxx:252-254) without a kernel boundary.
-template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
-          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8>
+template <class G, int WG, int OCC, bool WINDOW, bool DMA, int RAWD = 2, int ABL = 0, bool TWLDS = false,
+          int FMT = kFmtCu8>
 __global__ __launch_bounds__(WG, OCC) void fft_accum_scan_kernel(const cf* __restrict__ twN,
                                                             const float* __restrict__ window,
                                                             double* __restrict__ partial,
@@ -211,8 +177,8 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_scan_kernel(const cf* __res
 // from frame k L of one stream, as many spectra as the launch's 2^31 iterations hold.  A spectrum that lies inside one
 // workgroup's range goes straight to its row of hops.out; one that is cut leaves its segments in the partial slots
 // 2w / 2w + 1 for series_fixup_kernel.  Instantiated in rpf_kernels_series.hip only.
-template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
-          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8>
+template <class G, int WG, int OCC, bool WINDOW, bool DMA, int RAWD = 2, int ABL = 0, bool TWLDS = false,
+          int FMT = kFmtCu8>
 __global__ __launch_bounds__(WG, OCC) void fft_accum_series_kernel(const cf* __restrict__ twN,
                                                               const float* __restrict__ window,
                                                               double* __restrict__ partial,
@@ -227,8 +193,8 @@ __global__ __launch_bounds__(WG, OCC) void fft_accum_series_kernel(const cf* __r
 // power as in fft_accum_kernel's STATS form, zeroed at every spectrum; row k of hops.out and every partial slot are
 // three planes of N, S1, S2, PK, handed over one after the other.  A kernel of its own name, so that the plain series
 // kernels keep theirs.  Instantiated in rpf_kernels_series_stats.hip only.
-template <class G, int WG, int OCC, bool WINDOW, bool DMA, bool DBUF, int ACCB = 0, bool PF32 = false,
-          int RAWD = 2, int ABL = 0, bool TWLDS = false, int FMT = kFmtCu8>
+template <class G, int WG, int OCC, bool WINDOW, bool DMA, int RAWD = 2, int ABL = 0, bool TWLDS = false,
+          int FMT = kFmtCu8>
 __global__ __launch_bounds__(WG, OCC) void fft_accum_series_stats_kernel(const cf* __restrict__ twN,
                                                                     const float* __restrict__ window,
                                                                     double* __restrict__ partial,
@@ -251,8 +217,7 @@ __global__ __launch_bounds__(WG, OCC) void fft_stft_kernel(const uint8_t* __rest
                                                            const cf* __restrict__ twN,
                                                            const float* __restrict__ window, cf* __restrict__ out)
 {
-    constexpr bool STRIDED = false;
-    constexpr long pitch = static_cast<long>(sample_bytes_of(FMT)) * G::N;     // (named by the discarded strided branches only)
+    constexpr long pitch = static_cast<long>(sample_bytes_of(FMT)) * G::N;     // frames side by side (stage_raw)
 #include "k1_stft_body.inc"
 }
 
@@ -262,7 +227,6 @@ __global__ __launch_bounds__(WG, OCC) void fft_stft_strided_kernel(const uint8_t
                                                                    const float* __restrict__ window,
                                                                    cf* __restrict__ out)
 {
-    constexpr bool STRIDED = true;
 #include "k1_stft_body.inc"
 }
 
@@ -280,7 +244,6 @@ using StftStridedFn = void (*)(const uint8_t*, long, long, const cf*, const floa
 struct Variant {
     int N, vid, P;
     K1Geometry geo;
-    bool partial_f32;
     int single_ldw[2][2];    // loader waves of single[window][dma]: its launch is geo.with_loader(...); no other kernel has any
     SingleFn single[2][2];   // one acquisition per launch
     ScanFn scan[2][2];       // several hops per launch
@@ -325,8 +288,7 @@ const Variant* k1_stft_cf32_variant(int N, int fmt);
 // dynamic-LDS attribute is set and its occupancy asked; *grid = max(the smallest, 1) x CUs.  rpf_kernels.hip.
 hipError_t plan_resident_grid(std::initializer_list<const void*> kernels, const K1Geometry& geo, int device, int* grid);
 
-// What a plan or a launch reports (li may be null).  `slots` is not K1's to set; the Bluestein record has no
-// partial_f32 and leaves it alone.
+// What a plan or a launch reports (li may be null).  `slots` is not K1's to set.
 inline void fill_info(LaunchInfo* li, const K1Geometry& geo, int grid)
 {
     if (!li) return;
@@ -334,11 +296,6 @@ inline void fill_info(LaunchInfo* li, const K1Geometry& geo, int grid)
     li->block = geo.WG;               // the threads that own frames, loader waves not counted
     li->fpw = geo.fpw;
     li->lds_bytes = geo.lds_bytes;
-}
-inline void fill_info(LaunchInfo* li, const Variant& v, int grid)
-{
-    fill_info(li, v.geo, grid);
-    if (li) li->partial_f32 = v.partial_f32;
 }
 
 namespace {
@@ -350,18 +307,18 @@ namespace {
 enum K1Kernels { kK1Plain, kK1Stats, kK1Series, kK1SeriesStats, kK1Stft };
 
 // the [window][dma] instantiations of one kernel template; the arguments are its template arguments after TWLDS
-#define RPF_K1_FORMS(KERNEL, ...)                                                             \
-    {{KERNEL<G, WG, OCC, false, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, __VA_ARGS__>,       \
-      KERNEL<G, WG, OCC, false, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, __VA_ARGS__>},       \
-     {KERNEL<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, __VA_ARGS__>,      \
-      KERNEL<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, __VA_ARGS__>}}
+#define RPF_K1_FORMS(KERNEL, ...)                                           \
+    {{KERNEL<G, WG, OCC, false, false, RAWD, ABL, TWLDS, __VA_ARGS__>,       \
+      KERNEL<G, WG, OCC, false, true, RAWD, ABL, TWLDS, __VA_ARGS__>},       \
+     {KERNEL<G, WG, OCCW, true, false, RAWD, ABL, TWLDSW, __VA_ARGS__>,      \
+      KERNEL<G, WG, OCCW, true, true, RAWD, ABL, TWLDSW, __VA_ARGS__>}}
 
 // ... of the single-acquisition kernel, whose LDS-DMA entry without a window alone takes the loader waves
-#define RPF_K1_SINGLE_FORMS(STATS)                                                                                  \
-    {{fft_accum_kernel<G, WG, OCC, false, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT, STATS, 0>,                 \
-      fft_accum_kernel<G, WG, OCC, false, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDS, FMT, STATS, LDW>},               \
-     {fft_accum_kernel<G, WG, OCCW, true, false, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, FMT, STATS, 0>,                \
-      fft_accum_kernel<G, WG, OCCW, true, true, DBUF, ACCB, PF32, RAWD, ABL, TWLDSW, FMT, STATS, 0>}}
+#define RPF_K1_SINGLE_FORMS(STATS)                                                                \
+    {{fft_accum_kernel<G, WG, OCC, false, false, RAWD, ABL, TWLDS, FMT, STATS, 0>,                 \
+      fft_accum_kernel<G, WG, OCC, false, true, RAWD, ABL, TWLDS, FMT, STATS, LDW>},               \
+     {fft_accum_kernel<G, WG, OCCW, true, false, RAWD, ABL, TWLDSW, FMT, STATS, 0>,                \
+      fft_accum_kernel<G, WG, OCCW, true, true, RAWD, ABL, TWLDSW, FMT, STATS, 0>}}
 #define RPF_K1_SINGLE_LDW {{0, LDW}, {0, 0}}
 
 // ... of a store kernel, whose template arguments are the plain kernels' without the accumulate ones
@@ -373,26 +330,25 @@ enum K1Kernels { kK1Plain, kK1Stats, kK1Series, kK1SeriesStats, kK1Stft };
 
 // The template arguments are K1Size's (k1_sizes.h) and the kernels' (above).  vid = tuning variant (0 = the default
 // for this N).
-template <int N, int P, int OCC, int OCCW = OCC, bool DBUF = false, int ACCB = 0, bool PF32 = false,
-          int RAWD = 2, int ABL = 0, bool TWLDS = false, int WGO = 0, int FMT = kFmtCu8, bool TWLDSW = TWLDS,
-          K1Kernels KERNELS = kK1Plain, int LDW = 0>
+template <int N, int P, int OCC, int OCCW = OCC, int RAWD = 2, int ABL = 0, bool TWLDS = false, int WGO = 0,
+          int FMT = kFmtCu8, bool TWLDSW = TWLDS, K1Kernels KERNELS = kK1Plain, int LDW = 0>
 Variant make_variant(int vid)
 {
     using G = Geom<N, P>;
-    constexpr K1Geometry geo = k1_geometry<G>(WGO, DBUF ? 2 : 1, RAWD, FMT, TWLDS || TWLDSW);
+    constexpr K1Geometry geo = k1_geometry<G>(WGO, 1, RAWD, FMT, TWLDS || TWLDSW);
     constexpr int WG = geo.WG;
     if constexpr (KERNELS == kK1Stft)
-        return Variant{N, vid, P, geo, PF32, {}, {}, {}, {}, {}, RPF_K1_STFT_FORMS(fft_stft_kernel),
+        return Variant{N, vid, P, geo, {}, {}, {}, {}, {}, RPF_K1_STFT_FORMS(fft_stft_kernel),
                        RPF_K1_STFT_FORMS(fft_stft_strided_kernel)};
     else if constexpr (KERNELS == kK1Series)
-        return Variant{N, vid, P, geo, PF32, {}, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_kernel, FMT)};
+        return Variant{N, vid, P, geo, {}, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_kernel, FMT)};
     else if constexpr (KERNELS == kK1SeriesStats)
-        return Variant{N, vid, P, geo, PF32, {}, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_stats_kernel, FMT)};
+        return Variant{N, vid, P, geo, {}, {}, {}, {}, RPF_K1_FORMS(fft_accum_series_stats_kernel, FMT)};
     else if constexpr (KERNELS == kK1Stats)
-        return Variant{N, vid, P, geo, PF32, RPF_K1_SINGLE_LDW, RPF_K1_SINGLE_FORMS(true), {},
+        return Variant{N, vid, P, geo, RPF_K1_SINGLE_LDW, RPF_K1_SINGLE_FORMS(true), {},
                        RPF_K1_FORMS(fft_accum_strided_kernel, FMT, true), {}};
     else
-        return Variant{N, vid, P, geo, PF32, RPF_K1_SINGLE_LDW, RPF_K1_SINGLE_FORMS(false),
+        return Variant{N, vid, P, geo, RPF_K1_SINGLE_LDW, RPF_K1_SINGLE_FORMS(false),
                        RPF_K1_FORMS(fft_accum_scan_kernel, FMT), RPF_K1_FORMS(fft_accum_strided_kernel, FMT, false), {}};
 }
 #undef RPF_K1_FORMS
@@ -407,8 +363,7 @@ Variant default_variant()
     constexpr K1Size s = k1_size(I, FMT, KERNELS == kK1Stats || KERNELS == kK1SeriesStats);
     static_assert(k1_geometry<Geom<s.N, s.P>>(s.WGO, 1, s.RAWD, FMT, s.TWLDS || s.TWLDSW).lds_bytes <= kLdsPerCU,
                   "a workgroup's LDS fits the CU");
-    return make_variant<s.N, s.P, s.OCC, s.OCCW, false, 0, false, s.RAWD, 0, s.TWLDS, s.WGO, FMT, s.TWLDSW, KERNELS,
-                        s.LDW>(0);
+    return make_variant<s.N, s.P, s.OCC, s.OCCW, s.RAWD, 0, s.TWLDS, s.WGO, FMT, s.TWLDSW, KERNELS, s.LDW>(0);
 }
 template <K1Kernels KERNELS, int FMT, int... I>
 const Variant* find_default_variant(int N, std::integer_sequence<int, I...>)

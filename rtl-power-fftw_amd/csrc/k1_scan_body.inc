@@ -10,13 +10,12 @@
 // three planes each.  With it false nothing below changes what the two other kernels compile to.
     constexpr int P = G::P, T = G::T, N = G::N, NPASS = G::NPASS;
     constexpr int FPW = WG / T;
-    constexpr int NSLAB = DBUF ? 2 : 1;
     constexpr bool BLOCK_SYNC = (T > 64);
     static_assert(WG % T == 0 && WG % 64 == 0, "");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    cf* const slab_base = reinterpret_cast<cf*>(smem);                        // [NSLAB][FPW][LDS_CPX]
-    uint8_t* const raw_base = smem + NSLAB * FPW * G::LDS_CPX * sizeof(cf);  // [WG/64][RAWD][RAW_SLOT] bytes
+    cf* const slab_base = reinterpret_cast<cf*>(smem);                        // [FPW][LDS_CPX]
+    uint8_t* const raw_base = smem + FPW * G::LDS_CPX * sizeof(cf);          // [WG/64][RAWD][RAW_SLOT] bytes
 
     const int tid = threadIdx.x;
     const int fs = tid / T, t = tid % T;
@@ -77,7 +76,8 @@
         }
     };
     auto stage_next = [&](uint8_t* dst) {
-        stage_raw<G, DMA, int, FMT, SBATCH>(ahead.stream, ahead_fb, ahead.nframes, dst, wave, lane);
+        stage_raw<G, DMA, int, FMT, SBATCH>(ahead.stream, ahead_fb, ahead.nframes,
+                                            static_cast<long>(sample_bytes_of(FMT)) * G::N, dst, wave, lane);
         ahead_fb += ahead_fstep;
         if (--ahead_run == 0) ahead_turn();
     };
@@ -101,26 +101,21 @@
         for (int a = 0; a < P; ++a) wsgn[a] = window[t + T * a] * sgn;
     }
     double acc[P];
-    float acc32[ACCB > 0 ? P : 1];
     // STATS: the sum of the squared powers and the peak power of every bin beside acc (fft_core.h,
     // phase_accumulate_stats), zeroed with it at every spectrum; the peak starts from 0, which no power is below.
-    static_assert(!STATS || (SERIES && ACCB == 0 && !PF32 && ABL == 0), "the statistics: series kernels only, no tuning paths");
+    static_assert(!STATS || (SERIES && ABL == 0), "the statistics: series kernels only, no ablations");
     double acc_s2[STATS ? P : 1], acc_pk[STATS ? P : 1];
 
     PhaseClock clk;
     clk.start();
     HopCursor cur;
     cur.seek(tbl, first);
-    int it = 0;                                    // iterations done: ring slot and slab parity
+    int it = 0;                                    // iterations done: the ring slot
     while (true) {
         // ---- one segment: this workgroup's iterations inside hop cur.h ------------------------
         const int seg = run_length(cur, count - it);
 #pragma unroll
         for (int a = 0; a < P; ++a) acc[a] = 0.0;
-        if constexpr (ACCB > 0) {
-#pragma unroll
-            for (int a = 0; a < P; ++a) acc32[a] = 0.0f;
-        }
         if constexpr (STATS) {
 #pragma unroll
             for (int a = 0; a < P; ++a) acc_s2[a] = acc_pk[a] = 0.0;
@@ -128,7 +123,7 @@
         int fb = (cur.j - cur.begin) * FPW;        // slot-0 frame of the iteration, within the hop
         for (int n = seg; n > 0; --n, ++it, fb += fstep) {
             const bool active = (fb + fs) < cur.nframes;
-            cf* const slab = slab_base + ((DBUF ? (it & 1) : 0) * FPW + fs) * G::LDS_CPX;
+            cf* const slab = slab_base + fs * G::LDS_CPX;
             uint8_t* const ring_slot = wave_raw + (it % RAWD) * RAW_SLOT;
             cf x[P];
 
@@ -155,8 +150,8 @@
             if constexpr (!(ABL & 8)) stage_next(ring_slot);
             RPF_STAMP(clk, 3);                   // DMA issue
 
-            // single slab: every wave must be done with the previous frame's slab
-            if constexpr (!DBUF) exchange_sync<BLOCK_SYNC>();
+            // one slab: every wave must be done with the previous frame's slab
+            exchange_sync<BLOCK_SYNC>();
             RPF_STAMP(clk, 2);                       // top-of-frame barrier
             middle_passes<G, 1, ABL, TWLDS>(t, x, tw, slab, clk, twtable);   // stamps 4J..4J+3
             if constexpr (!(ABL & 4)) phase_fetch<G, NPASS>(t, x, slab);
@@ -164,20 +159,7 @@
             RPF_STAMP(clk, 12);                      // last fetch
             if constexpr (!(ABL & 2)) phase_last<G>(x);
             RPF_STAMP(clk, 13);                      // last butterfly
-            if constexpr (ACCB > 0) {
-                if (active) {
-#pragma unroll
-                    for (int a = 0; a < P; ++a)
-                        acc32[a] = __builtin_fmaf(x[a].x, x[a].x, __builtin_fmaf(x[a].y, x[a].y, acc32[a]));
-                }
-                if ((it % ACCB) == ACCB - 1) {
-#pragma unroll
-                    for (int a = 0; a < P; ++a) {
-                        acc[a] += static_cast<double>(acc32[a]);
-                        acc32[a] = 0.0f;
-                    }
-                }
-            } else if constexpr (ABL & 1) {
+            if constexpr (ABL & 1) {
 #pragma unroll
                 for (int a = 0; a < P; ++a) asm volatile("" ::"v"(x[a]));
             } else if constexpr (STATS) {
@@ -186,10 +168,6 @@
                 if (active) phase_accumulate(x, acc, P);
             }
             RPF_STAMP(clk, 14);                      // accumulate
-        }
-        if constexpr (ACCB > 0) {
-#pragma unroll
-            for (int a = 0; a < P; ++a) acc[a] += static_cast<double>(acc32[a]);
         }
 
         // ---- hand the segment over: one partial spectrum (the FPW frame slots summed) ----------
@@ -243,7 +221,6 @@
             double* row = nullptr;           // SERIES: where this segment goes
             if constexpr (SERIES) {
                 // (cur.j is still the segment's first iteration; first + it the one after its last)
-                static_assert(!PF32, "a series row is double");
                 const int w = static_cast<int>(blockIdx.x);
                 row = series_segment_complete(cur.j, first + it, cur.begin, cur.end)
                           ? series_rows(hops) + static_cast<size_t>(cur.h) * N
@@ -251,29 +228,20 @@
             } else {
                 slot = static_cast<size_t>(tbl.slot_bias(cur.h) + static_cast<int>(blockIdx.x));
             }
-            if constexpr (PF32) {
-                for (int bin = ftid; bin < N; bin += WG) {
-                    double v = 0.0;
+            // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
+            // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
+            // Written through (store_partial2), as K1's flush.
+            for (int bin = 2 * ftid; bin < N; bin += 2 * WG) {
+                partial2_t v = {0.0, 0.0};
 #pragma unroll
-                    for (int k = 0; k < FPW; ++k) v += stage[k * SN + bin + (bin >> 4)];
-                    reinterpret_cast<float*>(partial)[slot * N + bin] = static_cast<float>(v);
+                for (int k = 0; k < FPW; ++k) {
+                    v.x += stage[k * SN + bin + (bin >> 4)];
+                    v.y += stage[k * SN + bin + 1 + (bin >> 4)];
                 }
-            } else {
-                // two neighbouring bins per lane = one 16-byte store: an 8-byte-per-lane store tail is
-                // issue-bound at ~7 B/clk/CU (MI355X_MICROARCH.md), and every workgroup ends in one.
-                // Written through (store_partial2), as K1's flush.
-                for (int bin = 2 * ftid; bin < N; bin += 2 * WG) {
-                    partial2_t v = {0.0, 0.0};
-#pragma unroll
-                    for (int k = 0; k < FPW; ++k) {
-                        v.x += stage[k * SN + bin + (bin >> 4)];
-                        v.y += stage[k * SN + bin + 1 + (bin >> 4)];
-                    }
-                    if constexpr (SERIES)
-                        store_partial2(row + bin, v);
-                    else
-                        store_partial2(partial + slot * N + bin, v);
-                }
+                if constexpr (SERIES)
+                    store_partial2(row + bin, v);
+                else
+                    store_partial2(partial + slot * N + bin, v);
             }
         }
         if (it >= count) break;

@@ -61,9 +61,10 @@ constexpr int k1_slots_lds(int n, int p, int wgo, int slabs, int rawd, int fmt)
     return k1_workgroup(n, p, wgo) / (n / p) *
            (slabs * (n + n / p) * static_cast<int>(sizeof(cf)) + rawd * sample_bytes_of(fmt) * n);
 }
-// G: the frame's Geom; wgo: K1Size::WGO; per frame slot `slabs` exchange slabs (2: double-buffered) and a raw ring
-// of `rawd` frames of format `fmt` (0: no ring, the Bluestein kernel); twtable: the LDS twiddle table, one per
-// workgroup.  The kernels index LDS by the same compile-time quantities (k1_body.inc).
+// G: the frame's Geom; wgo: K1Size::WGO; per frame slot `slabs` exchange slabs (1 in every kernel; the host builds of
+// tests/emul state it too) and a raw ring of `rawd` frames of format `fmt` (0: no ring, the Bluestein kernel);
+// twtable: the LDS twiddle table, one per workgroup.  The kernels index LDS by the same compile-time quantities
+// (k1_body.inc).
 template <class G>
 constexpr K1Geometry k1_geometry(int wgo, int slabs, int rawd, int fmt, bool twtable)
 {

@@ -2,8 +2,8 @@
 // byte bN f) and fft_stft_strided_kernel (frame f at byte f * pitch): the plain kernel's frame loop (k1_body.inc) up to
 // and including the last pass, phase for phase, and then the frame's spectrum itself leaves -- row f of `out`, N
 // interleaved float32 (re, im) in natural bin order (include/rpf_engine.h, rpf_stft_device) -- where the plain kernel
-// squares it.  No double accumulators, no flush, no partial spectra.  The includer declares `constexpr bool STRIDED` and,
-// when it is true, has the kernel argument `long pitch`.
+// squares it.  No double accumulators, no flush, no partial spectra.  The includer has `pitch`: a constexpr long in
+// fft_stft_kernel, the kernel argument `long pitch` in fft_stft_strided_kernel.
     constexpr int P = G::P, T = G::T, N = G::N, NPASS = G::NPASS;
     constexpr int FPW = WG / T;
     constexpr bool BLOCK_SYNC = (T > 64);
@@ -27,10 +27,7 @@
     if (fb < nframes) {
 #pragma unroll
         for (int d = 0; d < RAWD; ++d)
-            if constexpr (STRIDED)
-                stage_raw_pitched<G, DMA, FMT>(stream, fb + d * stride, nframes, pitch, wave_raw + d * RAW_SLOT, wave, lane);
-            else
-                stage_raw<G, DMA, long, FMT>(stream, fb + d * stride, nframes, wave_raw + d * RAW_SLOT, wave, lane);
+            stage_raw<G, DMA, long, FMT>(stream, fb + d * stride, nframes, pitch, wave_raw + d * RAW_SLOT, wave, lane);
     }
 
     cf tw[NPASS - 1][P - 1];
@@ -64,10 +61,7 @@
         // the slot is refilled next: its LDS reads must have RETURNED first (k1_body.inc has the story)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         exchange_sync<false>();
-        if constexpr (STRIDED)
-            stage_raw_pitched<G, DMA, FMT>(stream, fb + RAWD * stride, nframes, pitch, ring_slot, wave, lane);
-        else
-            stage_raw<G, DMA, long, FMT>(stream, fb + RAWD * stride, nframes, ring_slot, wave, lane);
+        stage_raw<G, DMA, long, FMT>(stream, fb + RAWD * stride, nframes, pitch, ring_slot, wave, lane);
 
         // every wave is done with the slab: the read-back of the frame before this one
         exchange_sync<BLOCK_SYNC>();

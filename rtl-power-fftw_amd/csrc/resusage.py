@@ -13,8 +13,8 @@ for l in sys.stdin:
     if m and cur:
         d[m.group(1).strip()] = m.group(2)
         if 'LDS Size' in m.group(1):
-            g = re.search(r'GeomILi(\d+)ELi(\d+)EEELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)', cur)
-            tag = 'N=%s P=%s WG=%s OCC=%s win=%s dma=%s dbuf=%s' % g.groups() if g else cur[:48]
+            g = re.search(r'GeomILi(\d+)ELi(\d+)EEELi(\d+)ELi(\d+)ELb(\d)ELb(\d)', cur)
+            tag = 'N=%s P=%s WG=%s OCC=%s win=%s dma=%s' % g.groups() if g else cur[:48]
             f = re.search(r'pfb_fold_(sliding|reread)_kernelILi(\d+)E(?:Li(\d+)E)?Lb(\d)E', cur)
             if f:
                 tag = 'pfb_fold %s fmt=%s taps=%s aligned=%s' % (f.group(1), f.group(2), f.group(3) or 'any', f.group(4))

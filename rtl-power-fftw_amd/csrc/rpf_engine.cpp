@@ -517,8 +517,7 @@ int launch_transform(rpf_engine* e, const uint8_t* d_frames, int64_t nframes, hi
 int reduce_last(rpf_engine* e, double* d_out, bool accumulate, hipStream_t stream, unsigned* slot_verdict)
 {
     const bool fused = e->last_was_fused;
-    HIP_TRY(e, rpf::launch_reduce(e->d_partial, e->last_slots, e->N, d_out, accumulate, stream,
-                                  e->plan.partial_f32, e->partial_stride,
+    HIP_TRY(e, rpf::launch_reduce(e->d_partial, e->last_slots, e->N, d_out, accumulate, stream, e->partial_stride,
                                   fused && slot_verdict ? rpf::fourstep_fused_abort_word(e->d_fused_ctl) : nullptr));
     // a fused launch whose teams did not assemble must not leave something that looks like a spectrum
     if (fused)
@@ -544,7 +543,7 @@ int launch_side_by_side(rpf_engine* e, const uint8_t* d_frames, int64_t nframes,
         if (want_stats)
             HIP_TRY(e, rpf::launch_reduce_stats(e->d_partial, nslots, e->N, d_out, accumulate, stream));
         else
-            HIP_TRY(e, rpf::launch_reduce(e->d_partial, nslots, e->N, d_out, accumulate, stream, false,
+            HIP_TRY(e, rpf::launch_reduce(e->d_partial, nslots, e->N, d_out, accumulate, stream,
                                           static_cast<size_t>(rpf::kStatsPlanes) * e->N));
         return RPF_OK;
     }
@@ -2047,7 +2046,7 @@ int rpf_device_reduce(rpf_engine* e, double* d_pwr_out, void* hip_stream)
     HIP_TRY(e, on_device.status());
     if (e->last_hops > 0) {
         HIP_TRY(e, rpf::launch_reduce_hops(e->d_partial, e->last_ranges, e->last_hops, e->N, d_pwr_out,
-                                           /*accumulate=*/false, static_cast<hipStream_t>(hip_stream), e->plan.partial_f32));
+                                           /*accumulate=*/false, static_cast<hipStream_t>(hip_stream)));
         return RPF_OK;
     }
     return reduce_last(e, d_pwr_out, /*accumulate=*/false, static_cast<hipStream_t>(hip_stream), nullptr);
@@ -2122,8 +2121,7 @@ int rpf_accumulate_device_hops(rpf_engine* e, const void* const* d_streams, cons
         rc = launch_fused_hops(e, ptrs, frames.data() + h0, hc, s, &slots, &nslots);
         if (rc != RPF_OK) return rc;
         // (a hop without a whole frame has an empty slot range: the reduce writes zeros)
-        HIP_TRY(e, rpf::launch_reduce_hops(e->d_partial, slots, hc, e->N, d_pwr_out + h0 * N, /*accumulate=*/false, s,
-                                           e->plan.partial_f32));
+        HIP_TRY(e, rpf::launch_reduce_hops(e->d_partial, slots, hc, e->N, d_pwr_out + h0 * N, /*accumulate=*/false, s));
         e->last_slots = nslots;
         e->last_ranges = slots;
         e->last_hops = hc;

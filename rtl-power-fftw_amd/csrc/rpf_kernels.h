@@ -21,7 +21,6 @@ struct LaunchInfo {
     int block = 0;       // threads per workgroup
     int fpw = 0;         // frames processed concurrently by one workgroup
     int lds_bytes = 0;   // dynamic LDS per workgroup
-    bool partial_f32 = false;   // partial spectra are float32 (tuning variants), else f64
     int slots = 0;       // partial spectra written (0: one per workgroup)
 };
 
@@ -122,11 +121,10 @@ hipError_t launch_quantile_select(const double* d_rows, int64_t K, int N, const 
 // d_skip (may be null): a device word read when the kernel runs; non-zero = leave d_out untouched (the partial
 // spectra are not a result: fourstep_fused_abort_word).
 hipError_t launch_reduce(const double* d_partial, int nslots, int N, double* d_out,
-                         bool accumulate, hipStream_t stream, bool partial_f32 = false, size_t slot_stride = 0,
-                         const unsigned* d_skip = nullptr);
+                         bool accumulate, hipStream_t stream, size_t slot_stride = 0, const unsigned* d_skip = nullptr);
 // The same for H hops in one launch: d_out[h*N + bin] from the slots [slots.begin[h], slots.begin[h+1]).
 hipError_t launch_reduce_hops(const double* d_partial, const SlotRanges& slots, int H, int N, double* d_out,
-                              bool accumulate, hipStream_t stream, bool partial_f32 = false, size_t slot_stride = 0,
+                              bool accumulate, hipStream_t stream, size_t slot_stride = 0,
                               const unsigned* d_skip = nullptr);
 
 // ---- mixed-radix path (KM, rpf_mixed.hip): the planned kernel for the sizes of mixed_plans.inc, its split form

@@ -324,7 +324,7 @@ hipError_t plan_launch(int N, int vid, bool window, bool use_dma, int device, La
     err = plan_resident_grid({reinterpret_cast<const void*>(v->scan[w][d]),
                               reinterpret_cast<const void*>(v->strided[w][d])}, v->geo, device, &grid);
     if (err != hipSuccess) return err;
-    fill_info(li, *v, std::min(grid, grid1));
+    fill_info(li, v->geo, std::min(grid, grid1));
     return hipSuccess;
 }
 
@@ -342,7 +342,7 @@ hipError_t launch_fft_accum(int N, int vid, bool window, bool use_dma, const uin
     else
         hipLaunchKernelGGL(v->strided[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->geo.launched), v->geo.lds_bytes,
                            stream, d_stream, nframes, pitch, d_twiddles, d_window, d_partial);
-    fill_info(li, *v, grid);
+    fill_info(li, v->geo, grid);
     return hipGetLastError();
 }
 
@@ -354,7 +354,7 @@ hipError_t launch_fft_accum_hops(int N, int vid, bool window, bool use_dma, cons
     if (!v || grid < 1 || hops.H < 1 || hops.H > kMaxHops || grid > hops.total) return hipErrorInvalidValue;
     hipLaunchKernelGGL(v->scan[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->geo.launched), v->geo.lds_bytes, stream,
                        d_twiddles, d_window, d_partial, hops);
-    fill_info(li, *v, grid);
+    fill_info(li, v->geo, grid);
     return hipGetLastError();
 }
 
@@ -399,29 +399,22 @@ void launch_reduce_shape(const PT* d_partial, const SlotRanges& slots, int H, in
 }  // namespace
 
 hipError_t launch_reduce_hops(const double* d_partial, const SlotRanges& slots, int H, int N, double* d_out,
-                              bool accumulate, hipStream_t stream, bool partial_f32, size_t slot_stride,
-                              const unsigned* d_skip)
+                              bool accumulate, hipStream_t stream, size_t slot_stride, const unsigned* d_skip)
 {
     if (H < 1 || H > kMaxHops) return hipErrorInvalidValue;
     const size_t stride = slot_stride ? slot_stride : static_cast<size_t>(N);
-    if (partial_f32) {
-        launch_reduce_shape<float, 8, 32, 8>(reinterpret_cast<const float*>(d_partial), slots, H, N, d_out, accumulate,
-                                             stream, stride, d_skip);
-        return hipGetLastError();
-    }
     // one block shape: seven were measured in situ behind K1 within 0.3 us of each other (profiles/r03_k3_shapes.txt)
     launch_reduce_shape<double, 8, 16, 8>(d_partial, slots, H, N, d_out, accumulate, stream, stride, d_skip);
     return hipGetLastError();
 }
 
 hipError_t launch_reduce(const double* d_partial, int nslots, int N, double* d_out,
-                         bool accumulate, hipStream_t stream, bool partial_f32, size_t slot_stride,
-                         const unsigned* d_skip)
+                         bool accumulate, hipStream_t stream, size_t slot_stride, const unsigned* d_skip)
 {
     SlotRanges one;
     one.begin[0] = 0;
     for (int h = 1; h <= kMaxHops; ++h) one.begin[h] = nslots;
-    return launch_reduce_hops(d_partial, one, 1, N, d_out, accumulate, stream, partial_f32, slot_stride, d_skip);
+    return launch_reduce_hops(d_partial, one, 1, N, d_out, accumulate, stream, slot_stride, d_skip);
 }
 
 void make_twiddles(int N, std::vector<cf>& out)

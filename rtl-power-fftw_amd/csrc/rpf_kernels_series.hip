@@ -74,7 +74,7 @@ hipError_t plan_series(int N, bool window, int device, LaunchInfo* li, int fmt)
     hipError_t err = plan_resident_grid({reinterpret_cast<const void*>(v->series[w][0]),
                                          reinterpret_cast<const void*>(v->series[w][1])}, v->geo, device, &grid);
     if (err != hipSuccess) return err;
-    fill_info(li, *v, grid);
+    fill_info(li, v->geo, grid);
     return hipSuccess;
 }
 
@@ -86,7 +86,7 @@ hipError_t launch_fft_accum_series(int N, bool window, bool use_dma, const Serie
     if (!v || grid < 1 || grid > args.total || args.K < 1 || !args.stream || !args.out) return hipErrorInvalidValue;
     hipLaunchKernelGGL(v->series[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->geo.WG), v->geo.lds_bytes, stream,
                        d_twiddles, d_window, d_partial, args);
-    fill_info(li, *v, grid);
+    fill_info(li, v->geo, grid);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess || grid < 2) return err;       // one workgroup: every spectrum is complete
     constexpr int PAIRS = 8, GROUPS = 16;

@@ -34,7 +34,7 @@ hipError_t plan_stft(int N, bool window, int device, LaunchInfo* li, int fmt)
                                          reinterpret_cast<const void*>(v->stft_strided[w][0]),
                                          reinterpret_cast<const void*>(v->stft_strided[w][1])}, v->geo, device, &grid);
     if (err != hipSuccess) return err;
-    fill_info(li, *v, grid);
+    fill_info(li, v->geo, grid);
     return hipSuccess;
 }
 
@@ -51,7 +51,7 @@ hipError_t launch_fft_stft(int N, bool window, bool use_dma, const uint8_t* d_st
     else
         hipLaunchKernelGGL(v->stft_strided[window ? 1 : 0][use_dma ? 1 : 0], dim3(grid), dim3(v->geo.WG), v->geo.lds_bytes,
                            stream, d_stream, nframes, pitch, d_twiddles, d_window, d_out);
-    fill_info(li, *v, grid);
+    fill_info(li, v->geo, grid);
     return hipGetLastError();
 }
 

@@ -10,7 +10,10 @@ disassembled (llvm-objdump -d, addresses and encodings dropped, so only mnemonic
 matched by demangled name; the trailing `, false` a defaulted `bool STATS` adds to the two K1 kernel templates'
 argument lists is dropped before matching, so that a build with that parameter can be compared with one before it;
 so is the `, 0` of the defaulted `int LDW` behind it (a kernel with loader waves keeps its `, 1` or `, 2`: it is a new
-kernel, and the one it replaced is reported as different or missing)."""
+kernel, and the one it replaced is reported as different or missing); and so is the `, false, 0, false` that follows
+the sixth template argument (DMA, counting N and P of the Geom apart) of every K1 accumulate kernel (`fft_accum_*kernel<`)
+in a build that still has the three retired experiments' parameters ("Retired experiments"), so that such
+a build can be compared with one without them."""
 import hashlib
 import json
 import os
@@ -54,6 +57,9 @@ def streams(lib):
     plain = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines()
     res = {}
     for mangled, name in zip(names, plain):
+        # the three retired experiments' parameters behind <Geom<N, P>, WG, OCC, WINDOW, DMA
+        name = re.sub(r"(fft_accum_\w*kernel<rpf::Geom<\d+, \d+>, \d+, \d+, (?:false|true), (?:false|true))"
+                      r", false, 0, false", r"\1", name)
         if "fft_accum_kernel<" in name:
             name = re.sub(r", (false|true), 0>\(", r", \1>(", name)      # the defaulted `int LDW` behind STATS
         if "fft_accum_kernel<" in name or "fft_accum_strided_kernel<" in name:
