@@ -41,7 +41,8 @@ extern "C" {
                                rpf_quantile_reset, rpf_quantile_append_device, rpf_quantile_append,
                                rpf_quantile_select_device, rpf_quantile_select, rpf_quantile_rows, rpf_quantile_max_rows;
                                rpf_accumulate_device_cross, rpf_accumulate_cross;
-                               rpf_stft_device, rpf_stft */
+                               rpf_stft_device, rpf_stft;
+                               rpf_correlate_device, rpf_correlate */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -357,6 +358,52 @@ int rpf_stft_device(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t 
                     void* d_out /* F x N x (float re, float im) */, int64_t* frames_done, void* hip_stream);
 int rpf_stft(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t max_frames,
              void* out /* host, F x N x 2 floats */, int64_t* frames_done);
+
+/* Correlator of up to eight streams: the visibility matrix V_ij[k] = sum over the frames of X_i,f[k] conj(X_j,f[k]) of
+ * every pair at once, on the rows of rpf_stft_device.  Everything that computes or checks it refers to this definition.
+ *   Inputs.  M = n_streams streams, 2 <= M <= 8, in the engine's sample format, each of `nbytes` bytes.  Frames, frame step,
+ *     PFB folding, `repeats` and the dropped tail are those of rpf_stft_device on this engine: the frames used are [0, F),
+ *     F = min(repeats, rpf_frames_in(e, nbytes)).  *frames_done = F (may be NULL); 0 where the call returns an error.
+ *   Rows.  X_m,f is row f of rpf_stft_device of stream m on this engine: float32 (re, im), bin N/2 = DC.
+ *   Per-frame term.  For a = X_i,f[k] and b = X_j,f[k], converted to double (csrc/correlate_core.h):
+ *         t_re = fma(a.re, b.re, a.im b.im)        t_im = fma(a.im, b.re, -(a.re b.im))
+ *     Each float32 x float32 product is exact in double, so each term is correctly rounded and equals numpy's
+ *     ar br + ai bi and ai br - ar bi on float64 copies bit for bit, whatever contraction a compiler applies.  Swapping i
+ *     and j negates t_im exactly; for i = j, t_re = fma(im, im, re re), the power of that frame, and t_im = +0.
+ *   Sum.  V_ij[k] = sum over f of t, added in double, in an order fixed by N, M, F and the device, the same for every pair
+ *     and independent of which stream is which: per chunk of C frames (below) the frame groups of correlate_groups, each
+ *     summed from zero in frame order, then the groups added in their order, then the chunk added to the running sum of
+ *     the chunks before it.  No floating-point atomics.
+ *   Output.  d_out[M][M][2][N] doubles, 16-byte aligned, overwritten: ((i M + j) 2 + c) N + k, c = 0 re, 1 im.  For i > j the
+ *     entry is the conjugate of (j, i) (re equal, im negated); the diagonal im is 0; F = 0 zeroes d_out.  For M = 2, V_01
+ *     is Sab of rpf_accumulate_device_cross, A conj(B) with a = stream 0.
+ *   Derived quantities (stats.coherence_matrix; coherence_pair of host/datastore.h):
+ *         gamma^2_ij = (re^2 + im^2) / (V_ii V_jj)     NaN where the denominator is 0; NOT clamped
+ *         phase_ij   = atan2(im, re)                    radians
+ *     gamma^2 of F frames is biased as the cross entries' is: identically 1 for F = 1 and about 1/F for unrelated streams.
+ *     A NaN in a cf32 stream m makes row m and column m NaN and leaves the other entries finite.
+ * Per chunk of at most C = max(1, floor(64 MB / 8 N)) frames (2048 at 4096 bins, 1024 at 8192, 8 at 2^20): M launches of
+ * the STFT route (stream m from byte f0 b S into rows block m), then the X-engine (csrc/rpf_correlate.hip: a lane per bin,
+ * the pair sums in registers; with several frame groups one more launch adds their partial planes in order); after the
+ * last chunk one finishing launch writes the Hermitian layout.  rpf_last_launch_info reports the last transform launch.
+ * Made at the first call (and grown for a call with more streams than any before it): what rpf_stft_device makes; rows
+ * scratch of M C frames (M x at most 64 MB); the X-engine's partial planes, G M^2 N doubles where G > 1 (at most 64 MB);
+ * M^2 N running doubles (rpf_correlate: 3 M^2 N, the result included).  An engine that never correlates allocates
+ * nothing for it.  Nothing else moves: queues, pwr, repeats_done, statistics, the quantile row store, the cross and the
+ * STFT scratch stay as they are.
+ * rpf_correlate_device puts every launch on `hip_stream` and returns without synchronising; every stream follows
+ * rpf_stft_device's rules.  rpf_correlate is the same on M host streams: they move through engine-owned device memory
+ * side by side, one piece of each at a time, in the pieces csrc/series_pieces.h gives with one frame per integration;
+ * it synchronises before it returns.
+ * RPF_ERR_INVALID_ARGUMENT, before any launch and with the output untouched: a NULL argument (the array, any element,
+ * d_out); n_streams outside [2, 8]; N not a power of two (Bluestein's spectrum lacks the final chirp); an engine created
+ * with RPF_FLAG_BIN_STATS; a kernel variant other than 0; a running acquisition; repeats < 0; nbytes or (device entry) a
+ * stream address that is no multiple of b; d_out not 16-byte aligned (device entry).  PFB engines and overlapped frames
+ * are served: their rows come from the STFT route unchanged. */
+int rpf_correlate_device(rpf_engine* e, const void* const* d_streams, int n_streams, size_t nbytes, int64_t repeats,
+                         double* d_out /* M x M x 2 x N */, void* hip_stream, int64_t* frames_done);
+int rpf_correlate(rpf_engine* e, const uint8_t* const* streams, int n_streams, size_t nbytes, int64_t repeats,
+                  double* out /* host */, int64_t* frames_done);
 
 /* The two halves of rpf_accumulate_device as separate enqueues, so that a
  * benchmark can bracket the dominant kernel alone with events on `hip_stream`:

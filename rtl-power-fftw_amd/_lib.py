@@ -98,6 +98,10 @@ _SYMBOLS = [
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_stft_device", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P, ctypes.POINTER(ctypes.c_int64), _P]),
     ("rpf_stft", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P, ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_correlate_device", ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.c_int, ctypes.c_size_t, ctypes.c_int64, _P, _P,
+                                            ctypes.POINTER(ctypes.c_int64)]),
+    ("rpf_correlate", ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.c_int, ctypes.c_size_t, ctypes.c_int64,
+                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_has_bin_stats", ctypes.c_int, [_P]),
     ("rpf_get_bin_stats", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     ("rpf_accumulate_device_stats", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P, _P,

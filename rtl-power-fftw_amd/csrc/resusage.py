@@ -26,4 +26,9 @@ for l in sys.stdin:
             f = re.search(r'fft_stft(_strided)?_kernelINS_4GeomILi(\d+)ELi(\d+)EEELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELi(\d+)ELb(\d)ELi(\d+)E', cur)
             if f:
                 tag = 'stft%s N=%s P=%s WG=%s OCC=%s win=%s dma=%s rawd=%s twlds=%s fmt=%s' % ((f.group(1) or '',) + f.groups()[1:])
+            f = re.search(r'correlate_xengine_kernelILi(\d+)E', cur)
+            if f:
+                tag = 'correlate_xengine M=%s' % f.group(1)
+            elif 'correlate_reduce_kernel' in cur or 'correlate_finish_kernel' in cur:
+                tag = re.search(r'(correlate_\w+?)_kernel', cur).group(1)
             print(tag, {k: d.get(k) for k in ('VGPRs', 'AGPRs', 'ScratchSize', 'Occupancy', 'VGPRs Spill')})

@@ -37,6 +37,7 @@
 
 #include "bluestein_tables.h"
 #include "cross_core.h"
+#include "correlate_core.h"
 #include "engine_family.h"
 #include "rpf_kernels.h"
 #include "series_pieces.h"
@@ -194,6 +195,14 @@ struct rpf_engine {
     float* d_stft_rows = nullptr;         // rpf_stft: the rows of one piece
     size_t stft_rows = 0;                 // ... rows (of 2 N floats) it holds
     bool last_was_stft = false;           // the last transform launched was an STFT call's on stft_inner
+    // the correlator of up to eight streams (rpf_correlate_device, rpf_correlate); made at the first call, grown for a
+    // call with more streams than any before it
+    float* d_corr_rows = nullptr;         // M blocks of correlate_chunk_frames(N) rows of 2 N floats
+    size_t corr_rows = 0;                 // ... rows it holds
+    double* d_corr_partial = nullptr;     // the X-engine's partial planes: G M^2 N doubles where G > 1
+    size_t corr_partial = 0;              // ... doubles it holds
+    double* d_corr_planes = nullptr;      // the M^2 running planes, then the host entry's result: 3 M^2 N doubles
+    size_t corr_planes = 0;               // ... doubles it holds
 
     mutable std::string last_error;
 };
@@ -922,6 +931,9 @@ void release_device(rpf_engine* e)
     }
     e->cross_inner = nullptr;
     (void)hipFree(e->d_stft_rows);
+    (void)hipFree(e->d_corr_rows);
+    (void)hipFree(e->d_corr_partial);
+    (void)hipFree(e->d_corr_planes);
     if (e->stft_inner) {
         release_device(e->stft_inner);
         delete e->stft_inner;
@@ -1999,6 +2011,140 @@ int rpf_stft(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t max_fr
             return static_cast<int>(RPF_OK);
         },
         frames_done);
+}
+
+// ---- the correlator of up to eight streams: rpf_correlate_device, rpf_correlate (include/rpf_engine.h) ---------------
+
+// Everything both entries refuse, before any launch.
+static int correlate_check(rpf_engine* e, const char* who, const void* const* streams, int n_streams, size_t nbytes,
+                           int64_t repeats, const void* out)
+{
+    const std::string me = who;
+    bool null = !e || !streams || !out;
+    for (int m = 0; !null && m < n_streams && m < rpf::kCorrelateMaxStreams; ++m) null = !streams[m];
+    if (null) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+    if (n_streams < rpf::kCorrelateMinStreams || n_streams > rpf::kCorrelateMaxStreams)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": n_streams must be 2 to 8; got " + std::to_string(n_streams));
+    if (e->N & (e->N - 1))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": the number of bins must be a power of two (Bluestein's spectrum lacks its final chirp); got " +
+                        std::to_string(e->N));
+    if (e->stats) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not on an engine created with RPF_FLAG_BIN_STATS");
+    if (e->variant != 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not with a kernel variant other than 0");
+    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": acquisition running");
+    if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
+    if (nbytes % e->sample_bytes)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": nbytes must be a multiple of the sample size (" + std::to_string(e->sample_bytes) + " bytes)");
+    return RPF_OK;
+}
+
+// What the STFT route needs, the rows scratch of M streams, the X-engine's partial planes and the running planes (the
+// host entry: and its result), made at the first call and grown for a call with more streams.
+static int ensure_correlate(rpf_engine* e, int M, bool host, hipStream_t s)
+{
+    int rc = ensure_stft(e);
+    if (rc != RPF_OK) return rc;
+    const size_t N = static_cast<size_t>(e->N), MM = static_cast<size_t>(M) * static_cast<size_t>(M);
+    const int64_t C = rpf::correlate_chunk_frames(e->N);
+    if ((rc = grow_scratch(e, &e->d_corr_rows, &e->corr_rows, static_cast<size_t>(M) * static_cast<size_t>(C),
+                           sizeof(float) * 2 * N, s)) != RPF_OK)
+        return rc;
+    const int64_t G = rpf::correlate_groups(e->N, M, C);
+    if (G > 1 && (rc = grow_scratch(e, &e->d_corr_partial, &e->corr_partial, static_cast<size_t>(G) * MM * N, sizeof(double), s)) != RPF_OK)
+        return rc;
+    return grow_scratch(e, &e->d_corr_planes, &e->corr_planes, (host ? 3 : 1) * MM * N, sizeof(double), s);
+}
+
+// The M^2 running planes of `nframes` frames of the M device streams into (accumulate: added to) e->d_corr_planes, on
+// `s`: per chunk of correlate_chunk_frames(N) frames the M streams' rows by the STFT route (stream m from frame f0 at
+// byte f0 b S) into rows block m, then the X-engine over the chunk, the chunks after the first adding.
+static int correlate_enqueue(rpf_engine* e, const uint8_t* const* d_streams, int M, int64_t nframes, bool accumulate, hipStream_t s)
+{
+    const int64_t C = rpf::correlate_chunk_frames(e->N);
+    const size_t block = static_cast<size_t>(C) * static_cast<size_t>(e->N);          // complex values per rows block
+    const size_t pitch = frame_bytes(e).pitch;
+    rpf::cf* const rows = reinterpret_cast<rpf::cf*>(e->d_corr_rows);
+    for (int64_t f0 = 0; f0 < nframes; f0 += C) {
+        const int64_t n = std::min(C, nframes - f0);
+        for (int m = 0; m < M; ++m)
+            if (int rc = stft_enqueue(e, d_streams[m] + static_cast<size_t>(f0) * pitch, n, rows + m * block, s)) return rc;
+        HIP_TRY(e, rpf::launch_correlate_xengine(e->d_corr_rows, static_cast<long>(block), M, e->N, n,
+                                                 rpf::correlate_groups(e->N, M, n), e->d_corr_partial, e->d_corr_planes,
+                                                 accumulate || f0 > 0, s));
+    }
+    return RPF_OK;
+}
+
+int rpf_correlate_device(rpf_engine* e, const void* const* d_streams, int n_streams, size_t nbytes, int64_t repeats, double* d_out,
+                         void* hip_stream, int64_t* frames_done)
+{
+    const std::string me = "rpf_correlate_device";
+    if (frames_done) *frames_done = 0;
+    int rc = correlate_check(e, me.c_str(), d_streams, n_streams, nbytes, repeats, d_out);
+    if (rc != RPF_OK) return rc;
+    for (int m = 0; m < n_streams; ++m)
+        if (reinterpret_cast<uintptr_t>(d_streams[m]) & (e->sample_bytes - 1))
+            return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": every stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_out must be 16-byte aligned");
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const int64_t nframes = std::min(frames_in(e, nbytes), repeats);
+    const size_t out_doubles = 2 * static_cast<size_t>(n_streams) * static_cast<size_t>(n_streams) * static_cast<size_t>(e->N);
+    if (nframes == 0) {
+        HIP_TRY(e, hipMemsetAsync(d_out, 0, sizeof(double) * out_doubles, s));
+        return RPF_OK;
+    }
+    if ((rc = ensure_correlate(e, n_streams, /*host=*/false, s)) != RPF_OK) return rc;
+    const uint8_t* ptrs[rpf::kCorrelateMaxStreams];
+    for (int m = 0; m < n_streams; ++m) ptrs[m] = static_cast<const uint8_t*>(d_streams[m]);
+    if ((rc = correlate_enqueue(e, ptrs, n_streams, nframes, /*accumulate=*/false, s)) != RPF_OK) return rc;
+    HIP_TRY(e, rpf::launch_correlate_finish(e->d_corr_planes, n_streams, e->N, d_out, s));
+    if (frames_done) *frames_done = nframes;                          // (frames that were enqueued, never frames that were not)
+    return RPF_OK;
+}
+
+int rpf_correlate(rpf_engine* e, const uint8_t* const* streams, int n_streams, size_t nbytes, int64_t repeats, double* out,
+                  int64_t* frames_done)
+{
+    if (frames_done) *frames_done = 0;
+    int rc = correlate_check(e, "rpf_correlate", reinterpret_cast<const void* const*>(streams), n_streams, nbytes, repeats, out);
+    if (rc != RPF_OK) return rc;
+    const int64_t nframes = std::min(frames_in(e, nbytes), repeats);
+    const size_t MM = static_cast<size_t>(n_streams) * static_cast<size_t>(n_streams), N = static_cast<size_t>(e->N);
+    if (nframes == 0) {
+        std::fill(out, out + 2 * MM * N, 0.0);
+        return RPF_OK;
+    }
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = e->compute_stream;
+    if ((rc = ensure_correlate(e, n_streams, /*host=*/true, s)) != RPF_OK) return rc;
+    // pieces of whole frames, series_pieces.h's rule with L = 1 per stream: one piece of each stream at a time, side by side
+    const rpf::FrameBytes fb = frame_bytes(e);
+    const rpf::SeriesPieces p = rpf::series_pieces(fb, 1, nframes);
+    const size_t part = (p.bytes + 255) / 256 * 256;
+    if ((rc = grow_scratch(e, &e->d_series_in, &e->series_in_bytes, static_cast<size_t>(n_streams) * part, 1, s)) != RPF_OK) return rc;
+    const uint8_t* ptrs[rpf::kCorrelateMaxStreams];
+    for (int m = 0; m < n_streams; ++m) ptrs[m] = e->d_series_in + static_cast<size_t>(m) * part;
+    for (int64_t k0 = 0; k0 < nframes; k0 += p.per_piece) {
+        const int64_t kc = std::min(p.per_piece, nframes - k0);
+        const size_t at = static_cast<size_t>(k0) * p.hop, span = fb.span(kc);
+        for (int m = 0; m < n_streams; ++m)
+            HIP_TRY(e, hipMemcpyAsync(e->d_series_in + static_cast<size_t>(m) * part, streams[m] + at, span, hipMemcpyHostToDevice, s));
+        if ((rc = correlate_enqueue(e, ptrs, n_streams, kc, /*accumulate=*/k0 > 0, s)) != RPF_OK) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        HIP_TRY(e, hipStreamSynchronize(s));
+    }
+    double* const d_result = e->d_corr_planes + MM * N;
+    HIP_TRY(e, rpf::launch_correlate_finish(e->d_corr_planes, n_streams, e->N, d_result, s));
+    HIP_TRY(e, hipMemcpyAsync(out, d_result, sizeof(double) * 2 * MM * N, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (frames_done) *frames_done = nframes;                          // (only with the visibilities of all of them in `out`)
+    return RPF_OK;
 }
 
 int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,

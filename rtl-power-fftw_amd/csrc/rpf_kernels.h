@@ -243,6 +243,15 @@ hipError_t launch_cross_combine(const uint8_t* d_a, const uint8_t* d_b, long nsa
 // d_out[4 x N] = the finishing expression of include/rpf_engine.h over d_planes[4 x N] = Paa, Pbb, Puu, Pvv (not in place).
 hipError_t launch_cross_finish(const double* d_planes, int N, double* d_out, hipStream_t stream);
 
+// ---- correlator of up to eight streams (rpf_correlate.hip, correlate_core.h) ------------------------------------------
+// The X-engine over rows [0, F) of M cf32 row blocks (block m at d_rows + 2 m stride floats, stride >= F N complex
+// values): the M^2 running planes of correlate_plane at d_planes (accumulate: added to), through G frame groups
+// (correlate_groups; G > 1 needs d_partial of G M^2 N doubles and adds a reduce launch).
+hipError_t launch_correlate_xengine(const float* d_rows, long stride, int M, int N, long F, long G, double* d_partial,
+                                    double* d_planes, bool accumulate, hipStream_t stream);
+// d_out[M][M][2][N] (Hermitian; diagonal im 0) from the M^2 running planes (not in place).
+hipError_t launch_correlate_finish(const double* d_planes, int M, int N, double* d_out, hipStream_t stream);
+
 // Master twiddle table W_N^k = exp(-2 pi i k / N), k in [0,N), evaluated in
 // long double and rounded once to float.
 void make_twiddles(int N, std::vector<cf>& out);

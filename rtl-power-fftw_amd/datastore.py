@@ -308,6 +308,37 @@ class Datastore:
             ctypes.c_void_p(out.ctypes.data), ctypes.byref(done)))
         return out[:done.value]
 
+    # -- correlator of up to eight streams (rpf_correlate[_device]; include/rpf_engine.h has the definition) ----------
+    def correlate_device(self, d_ptrs, nbytes, repeats, d_out_ptr, hip_stream=0):
+        """rpf_correlate_device: M = len(d_ptrs) streams of nbytes each resident in HBM, d_out = M x M x 2 x N device
+        doubles (the visibilities V_ij, re and im); asynchronous.  Returns F, the number of frames that will be summed."""
+        ptrs = (ctypes.c_void_p * max(len(d_ptrs), 1))(*[ctypes.c_void_p(p) for p in d_ptrs])
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_correlate_device(
+            self._handle, ptrs, len(d_ptrs), nbytes, repeats, ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(hip_stream),
+            ctypes.byref(done)))
+        return done.value
+
+    def correlate(self, streams, repeats=None):
+        """rpf_correlate: the same on M host streams of equal length (not through the buffer queues).  Returns
+        (V complex128 of shape (M, M, N), F); stats.coherence_matrix takes V.  repeats None = every whole frame the
+        streams hold."""
+        streams = [_as_bytes(s) for s in streams]
+        sizes = sorted({s.size for s in streams})
+        if len(sizes) > 1:
+            raise RPFError("correlate: the streams must have the same length; got %s bytes."
+                           % ", ".join(str(s.size) for s in streams), ReturnValue.InvalidArgument)
+        M, N = len(streams), self.params.N
+        out = np.zeros((max(M, 1), max(M, 1), 2, N), dtype=np.float64)
+        ptrs = (ctypes.c_void_p * max(M, 1))(*[ctypes.c_void_p(s.ctypes.data) for s in streams])
+        done = ctypes.c_int64()
+        self._check(self._lib.rpf_correlate(
+            self._handle, ptrs, M, sizes[0] if sizes else 0, (1 << 62) if repeats is None else repeats,
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(done)))
+        v = np.empty((out.shape[0], out.shape[1], N), dtype=np.complex128)
+        v.real, v.imag = out[:, :, 0, :], out[:, :, 1, :]          # the doubles as they came, bit for bit
+        return v, done.value
+
     def accumulate_device_series(self, d_stream_ptr, nbytes, frames_per_spectrum, max_spectra, d_out_ptr, hip_stream=0):
         """rpf_accumulate_device_series: consecutive spectra of `frames_per_spectrum` frames of a stream resident in
         HBM, row k of d_out (K x N device doubles) = frames [k L, (k + 1) L); asynchronous.  Returns K."""

@@ -215,6 +215,15 @@ void write_text_header_cross(std::ostream& out, const std::string& start_stamp, 
                         " power spectral density a [dB/Hz] power spectral density b [dB/Hz] coherence phase [rad]");
 }
 
+void write_text_header_correlate(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, int M)
+{
+    std::ostringstream titles;
+    for (int m = 0; m < M; ++m) titles << " power spectral density " << m << " [dB/Hz]";
+    for (int i = 0; i < M; ++i)
+        for (int j = i + 1; j < M; ++j) titles << " coherence " << i << "-" << j << " phase " << i << "-" << j << " [rad]";
+    write_titled_header(out, start_stamp, end_stamp, titles.str());
+}
+
 void write_spectrum_text(std::ostream& out, std::vector<double>& pwr, int N, int64_t repeats_done,
                          int64_t tuned_freq, int samplerate, bool linear, const std::vector<double>* baseline)
 {
@@ -275,6 +284,22 @@ void write_spectrum_text_cross(std::ostream& out, const std::vector<double>& pla
         out << " " << bin_value(plane[0], i, N, frames, samplerate, linear, baseline) << " "
             << bin_value(plane[1], i, N, frames, samplerate, linear, baseline) << " "
             << coherence(plane[0][i], plane[1][i], plane[2][i], plane[3][i]) << " " << cross_phase(plane[2][i], plane[3][i]);
+    });
+}
+
+void write_spectrum_text_correlate(std::ostream& out, const std::vector<double>& vis, int M, int N, int64_t frames,
+                                   int64_t tuned_freq, int samplerate, bool linear, const std::vector<double>* baseline)
+{
+    // the DC bin of every plane is the mean of its neighbours; coherence and phase come from those
+    const std::vector<std::vector<double>> plane = split_planes(vis, static_cast<size_t>(2 * M * M), N);
+    auto re = [&](int i, int j) -> const std::vector<double>& { return plane[2 * (i * M + j)]; };
+    auto im = [&](int i, int j) -> const std::vector<double>& { return plane[2 * (i * M + j) + 1]; };
+    write_rows(out, N, tuned_freq, samplerate, [&](int k) {
+        for (int m = 0; m < M; ++m) out << " " << bin_value(re(m, m), k, N, frames, samplerate, linear, baseline);
+        for (int i = 0; i < M; ++i)
+            for (int j = i + 1; j < M; ++j)
+                out << " " << coherence_pair(re(i, i)[k], re(j, j)[k], re(i, j)[k], im(i, j)[k]) << " "
+                    << cross_phase(re(i, j)[k], im(i, j)[k]);
     });
 }
 

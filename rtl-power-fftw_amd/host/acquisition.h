@@ -128,6 +128,13 @@ void write_spectrum_text_quantiles(std::ostream& out, const std::vector<double>&
 // two power columns go / frames / N / samplerate, dB and baseline as always, and coherence (dimensionless: never dB, no
 // baseline, "nan" where undefined) and phase [rad] are derived from the four (datastore.h: coherence, cross_phase).
 void write_text_header_cross(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp);
+// --correlate: the header, whose last line names the columns (frequency, the power of every stream m, then coherence
+// i-j and phase i-j [rad] for i < j), and the block.  vis[M x M x 2 x N] = V_ij re, im over `frames` frames
+// (rpf_correlate); the DC bin of every plane is the mean of its neighbours, then the powers are written by the usual
+// rules and coherence and phase derived from the planes (datastore.h: coherence_pair, cross_phase).
+void write_text_header_correlate(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, int M);
+void write_spectrum_text_correlate(std::ostream& out, const std::vector<double>& vis, int M, int N, int64_t frames,
+                                   int64_t tuned_freq, int samplerate, bool linear, const std::vector<double>* baseline);
 void write_spectrum_text_cross(std::ostream& out, const std::vector<double>& planes, int N, int64_t frames, int64_t tuned_freq,
                                int samplerate, bool linear, const std::vector<double>* baseline);
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,

@@ -131,6 +131,9 @@ inline double coherence(double saa, double sbb, double re, double im) {
   return (re * re + im * im) / den;
 }
 inline double cross_phase(double re, double im) { return std::atan2(im, re); }
+// The same for the pair (i, j) of the correlator (rpf_correlate): (re^2 + im^2) / (V_ii V_jj) from one bin of V_ij and
+// of the two autos (stats.py's coherence_matrix does the same operations); NaN where V_ii V_jj = 0; not clamped.
+inline double coherence_pair(double vii, double vjj, double re, double im) { return coherence(vii, vjj, re, im); }
 
 // A filled/empty hand-off buffer: what `Buffer&` is in acquisition.cxx:283,302-304
 // (data()/size()/resize()), backed by engine-owned pinned memory.
@@ -318,6 +321,25 @@ public:
                                   void* hip_stream = nullptr) {
     int64_t done = 0;
     check(rpf_accumulate_device_cross(engine_, d_a, d_b, nbytes, repeats, d_out, hip_stream, &done));
+    return done;
+  }
+  // Visibilities of M host streams of nbytes each (rpf_correlate; include/rpf_engine.h has the definition): `out`
+  // (resized to M x M x 2 x N) = V_ij re and im over the first min(repeats, frames) frames; coherence_pair and
+  // cross_phase above take one bin of them.  Not through the buffer queues: pwr and repeats_done stay.  Returns the frames.
+  int64_t correlate(const std::vector<const uint8_t*>& streams, size_t nbytes, int64_t repeats, std::vector<double>& out) {
+    const size_t M = streams.size();
+    out.assign(2 * M * M * static_cast<size_t>(params.N), 0.0);
+    int64_t done = 0;
+    check(rpf_correlate(engine_, streams.data(), static_cast<int>(M), nbytes, repeats, out.data(), &done));
+    return done;
+  }
+  // The same on streams resident in HBM (rpf_correlate_device): d_out = M x M x 2 x N device doubles, asynchronous on
+  // hip_stream.
+  int64_t correlate_device(const std::vector<const void*>& d_streams, size_t nbytes, int64_t repeats, double* d_out,
+                           void* hip_stream = nullptr) {
+    int64_t done = 0;
+    check(rpf_correlate_device(engine_, d_streams.data(), static_cast<int>(d_streams.size()), nbytes, repeats, d_out,
+                               hip_stream, &done));
     return done;
   }
   // Per-bin quantiles of the integrations (rpf_quantile_*; include/rpf_engine.h has the definition): the engine keeps the

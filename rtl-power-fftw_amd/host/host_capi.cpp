@@ -267,6 +267,31 @@ long rpf_host_format_text_cross(const double* planes, int N, long long frames, l
     return copy_out(os.str(), out, cap);
 }
 
+// The --correlate header for M streams (write_text_header_correlate).
+long rpf_host_format_header_correlate(const char* start_stamp, const char* end_stamp, int M, char* out, size_t cap)
+{
+    std::ostringstream os;
+    write_text_header_correlate(os, start_stamp, end_stamp, M);
+    return copy_out(os.str(), out, cap);
+}
+
+// datastore.h's coherence_pair, element by element over n bins of the two autos and of V_ij.
+void rpf_host_coherence_pair(const double* vii, const double* vjj, const double* re, const double* im, int n, double* out)
+{
+    for (int i = 0; i < n; ++i) out[i] = coherence_pair(vii[i], vjj[i], re[i], im[i]);
+}
+
+// The --correlate writer (write_spectrum_text_correlate) over vis[M x M x 2 x N].
+long rpf_host_format_text_correlate(const double* vis, int M, int N, long long frames, long long tuned_freq, int samplerate,
+                                    int linear, const double* baseline, char* out, size_t cap)
+{
+    std::vector<double> v(vis, vis + 2 * static_cast<size_t>(M) * M * N), b;
+    if (baseline) b.assign(baseline, baseline + N);
+    std::ostringstream os;
+    write_spectrum_text_correlate(os, v, M, N, frames, tuned_freq, samplerate, linear != 0, baseline ? &b : nullptr);
+    return copy_out(os.str(), out, cap);
+}
+
 void rpf_host_format_matrix(double* pwr, int N, long long repeats_done, int samplerate, int linear,
                             const double* baseline, float* row_out)
 {

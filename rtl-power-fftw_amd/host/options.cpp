@@ -23,7 +23,8 @@ struct Spec {
     const char* long_name;
     Kind kind;
     const char* value_name;
-    const char* help;
+    const char* help;          // nullptr: parsed, but not in the --help text, which stays the text
+                               // tests/golden/cli_refusals.json pins (README.md documents such options)
 };
 
 // Same options, names and help texts as params.cxx:104-141 (alphabetical like the man page).
@@ -95,6 +96,12 @@ const Spec kSpecs[] = {
      "raw little-endian float32 pairs (re, im), frame after frame; nothing goes to stdout (power-of-two bins only; "
      "combines with -w, --format, --frame-overlap and --pfb; not with a frequency range, -n, -t, -c, -e, -m, --stats, "
      "--series, --series-stats, --excise, --quantile, --cross or several --gpus)."},
+    // Correlator of --input (stream 0) and the listed files (streams 1, 2, ..., at most 7; same format, sample rate and
+    // tuning): one block with the power of every stream, then the magnitude-squared coherence and the phase [rad] of every
+    // pair i < j, over the whole frames of the shortest file (power-of-two bins only; combines with -w, --format,
+    // --frame-overlap and --pfb; not with a frequency range, -n, -t, -c, -e, -m, --stats, --series, --series-stats,
+    // --excise, --quantile, --cross, --stft or several --gpus).
+    {0, "correlate", Kind::Text, "b,c,...", nullptr},
     {0, "reduce", Kind::Text, "rccl|host", "With --gpus: where a scan's per-device spectra are added (default: rccl if it loads, else host)."},
     {'h', "help", Kind::Flag, "", "Displays usage information and exits."},
     {0, "version", Kind::Flag, "", "Displays version information and exits."},
@@ -178,6 +185,7 @@ void require_non_negative(const Parsed& p, const char* name)
 // A replay mode is an option that reads --input once, to its end, outside the acquisition loop.  One row each, in the
 // order their refusals speak; replay_mode() below walks a row.
 struct Refused { const char* option; const char* why; };
+constexpr int kMaxRefused = 7;      // the most options one row refuses; the entry after them stays null (rows_end below)
 struct ReplayMode {
     const char* name;
     int64_t Options::*frames;       // where its <frames> goes, checked against min_frames; null: the argument is a file
@@ -187,7 +195,7 @@ struct ReplayMode {
     const char* repeat_why;         // "does not combine with --repeats (-n): <repeat_why>."; so -t, -c, -e
     const char* matrix_why;         // "does not combine with -m (matrix mode): <matrix_why>."
     bool bin_stats;                 // turns Options::bin_stats on
-    Refused refused[7];             // "does not combine with --<option>: <why>.", in this order; ends at the first null
+    Refused refused[kMaxRefused + 1];   // "does not combine with --<option>: <why>.", in this order; ends at the first null
 };
 
 const char kOwnLength[] = "the integration length is its own argument and the replay is read once";
@@ -195,8 +203,9 @@ const char kAverage[] = "that writes every integration, this one their average";
 const char kOneProduct[] = "one product of the integrations per run";
 const char kSums[] = "those end in sums of |X|^2, this writes X itself";
 const char kNoCross[] = "cross-spectra of those are not built";
+const char kNoCorrelate[] = "visibilities of those are not built";
 
-const ReplayMode kReplayModes[] = {
+constexpr ReplayMode kReplayModes[] = {
     {"series", &Options::series_frames, 1, "", "it cuts a replayed stream into consecutive integrations", kOwnLength,
      "the spectra are text blocks", false, {{"stats", "time-resolved statistics are not built"}}},
     {"series-stats", &Options::series_frames, 1, "", "it cuts a replayed stream into consecutive integrations", kOwnLength,
@@ -215,7 +224,20 @@ const ReplayMode kReplayModes[] = {
      "the two replays are read once, to the end of the shorter", "the cross-spectrum is one text block", false,
      {{"stats", kNoCross}, {"series", kNoCross}, {"series-stats", kNoCross}, {"excise", kNoCross}, {"quantile", kNoCross},
       {"pfb", kNoCross}}},
+    {"correlate", nullptr, 0, "", "that is stream 0, and the files listed here streams 1, 2, ...",
+     "the replays are read once, to the end of the shortest", "the visibilities are one text block", false,
+     {{"stats", kNoCorrelate}, {"series", kNoCorrelate}, {"series-stats", kNoCorrelate}, {"excise", kNoCorrelate},
+      {"quantile", kNoCorrelate}, {"cross", "--cross is the correlator's two-stream special case"},
+      {"stft", "that writes the frames' spectra themselves"}}},
 };
+
+// replay_mode() walks a row's refusals to the first null: every row keeps its last entry for it.
+constexpr int kReplayModeCount = sizeof(kReplayModes) / sizeof(kReplayModes[0]);
+constexpr bool rows_end(int row)
+{
+    return row == kReplayModeCount || (kReplayModes[row].refused[kMaxRefused].option == nullptr && rows_end(row + 1));
+}
+static_assert(rows_end(0), "a row of kReplayModes refuses more than kMaxRefused options: its list has no terminating null");
 
 [[noreturn]] void refuse(const std::string& mode, const std::string& what)
 {
@@ -257,6 +279,7 @@ std::string usage_text()
     o << "USAGE:\n   rpf_power [OPTION ...]\n\nObtain power spectrum from RTL device using FFTW library"
          " (MI355X engine build).\n\nWhere:\n";
     for (const Spec& s : kSpecs) {
+        if (!s.help) continue;
         o << "   ";
         if (s.short_name) o << "-" << s.short_name << ",  ";
         o << "--" << s.long_name;
@@ -499,6 +522,23 @@ Options parse_command_line(int argc, const char* const* argv)
     if (replay_mode("cross", p, o)) {
         o.cross_file = p.get("cross");
         if (o.cross_file == "-" && p.get("input") == "-") refuse("cross", "cannot read both streams from stdin.");
+    }
+    if (replay_mode("correlate", p, o)) {
+        const std::string list = p.get("correlate");
+        size_t pos = 0;
+        while (pos <= list.size()) {
+            const size_t comma = std::min(list.find(',', pos), list.size());
+            const std::string item = list.substr(pos, comma - pos);
+            if (item.empty()) refuse("correlate", "could not use the list given to --correlate: " + list + ". Expecting comma-separated files.");
+            o.correlate_files.push_back(item);
+            pos = comma + 1;
+        }
+        if (o.correlate_files.size() > 7)
+            refuse("correlate", "takes at most 7 files beside --input, got " + std::to_string(o.correlate_files.size()) + ".");
+        if (o.N & (o.N - 1)) refuse("correlate", "needs a power-of-two number of bins (-b); got " + std::to_string(o.N) + ".");
+        int from_stdin = p.get("input") == "-";
+        for (const std::string& f : o.correlate_files) from_stdin += f == "-";
+        if (from_stdin > 1) refuse("correlate", "cannot read more than one stream from stdin.");
     }
     if (p.has("input")) o.input_file = p.get("input");
     o.synthetic = p.has("synthetic");

@@ -60,6 +60,7 @@ struct Options : Params {
     int64_t quantile_frames = 0;     // --quantile <frames>: per-bin quantiles over the replay's integrations of <frames> frames (0 = off)
     std::vector<double> quantiles;   // --quantiles a,b,...: which (each in [0, 1], at most 8); default 0.5
     std::string cross_file;          // --cross <file>: stream b of the cross-spectrum with --input ("" = off)
+    std::vector<std::string> correlate_files;   // --correlate b,c,...: streams 1 .. M-1 of the correlator with --input (empty = off)
     std::string stft_file;           // --stft <file>: where the frames' complex spectra of --input go, raw float32 pairs ("" = off)
     // (--pfb <taps> sets Params::pfb_taps; the coefficients are the default prototype)
     bool show_help = false, show_version = false;

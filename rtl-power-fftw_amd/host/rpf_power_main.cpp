@@ -549,6 +549,47 @@ int run_cross(const Options& options, AuxData& aux, int actual_samplerate, int64
     return 0;
 }
 
+// --input a --correlate b,c,...: the visibilities of the M replays (rpf_correlate) over the whole frames of the shortest,
+// ONE block: the power of every stream, then coherence and phase of every pair i < j.  Every file is read in pieces of
+// whole frames (piece_reader.h with one frame per integration), a piece of each at a time; every set of pieces leaves
+// its visibilities -- sums over its frames, so the pieces' are added here in file order.
+int run_correlate(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
+{
+    Datastore data(options, aux.window_values);
+    const size_t b = static_cast<size_t>(options.sample_bytes());
+    std::vector<std::unique_ptr<PieceReader>> readers;
+    readers.emplace_back(new PieceReader(options.input_file, b * options.span_samples(), b * options.step(), 1));
+    for (const std::string& f : options.correlate_files)
+        readers.emplace_back(new PieceReader(f, b * options.span_samples(), b * options.step(), 1));
+    const size_t M = readers.size(), N = static_cast<size_t>(options.N);
+    std::vector<PieceReader*> in;
+    std::vector<const uint8_t*> streams;
+    for (auto& r : readers) {
+        in.push_back(r.get());
+        streams.push_back(r->data());
+    }
+    std::vector<double> piece, vis(2 * M * M * N, 0.0);
+    std::vector<size_t> left(M, 0);
+    const std::string start_stamp = Acquisition::utc_now();
+    const int64_t frames = replay_pieces(in, [&](size_t have) {
+        const int64_t done = data.correlate(streams, have / b * b, in[0]->per_piece(), piece);
+        for (size_t i = 0; done > 0 && i < vis.size(); ++i) vis[i] += piece[i];
+        return done;
+    }, left.data());
+    const std::string end_stamp = Acquisition::utc_now();
+    write_text_header_correlate(std::cout, start_stamp, end_stamp, static_cast<int>(M));
+    write_spectrum_text_correlate(std::cout, vis, static_cast<int>(M), options.N, frames, tuned_freq, actual_samplerate,
+                                  options.linear, options.baseline ? &aux.baseline_values : nullptr);
+    std::cout << std::endl;          // (the blank line that closes a pass)
+    // what is left of each file once the last common frame is taken: the same unless the lengths differ
+    bool differ = false;
+    for (size_t m = 1; m < M; ++m) differ = differ || left[m] != left[0];
+    std::cerr << "Correlator: " << frames << " frames of " << options.N << " bins from each of " << M << " streams"
+              << (differ ? " (the files differ in length: the whole frames of the shortest are used)" : "") << std::endl;
+    if (chatty(options)) print_acquisition_summary(options.N, frames, 0, 0, actual_samplerate);
+    return 0;
+}
+
 // --input a --stft out: the complex spectrum of every frame of the replay (rpf_stft), raw little-endian float32 pairs,
 // frame after frame, into `out`; nothing on stdout.  The file is read in pieces of whole frames that keep the input AND the
 // rows a piece leaves within the budget (piece_reader.h with one frame per integration and the row cap of stft_pieces),
@@ -629,6 +670,7 @@ int run(int argc, char** argv)
     plan.print();
 
     if (!options.stft_file.empty()) return run_stft(options, aux, actual_samplerate);
+    if (!options.correlate_files.empty()) return run_correlate(options, aux, actual_samplerate, source->frequency());
     if (!options.cross_file.empty()) return run_cross(options, aux, actual_samplerate, source->frequency());
     if (options.quantile_frames > 0) return run_quantile(options, aux, actual_samplerate, source->frequency());
     if (options.excise_frames > 0) return run_excise(options, aux, actual_samplerate, source->frequency());

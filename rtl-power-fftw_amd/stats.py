@@ -81,6 +81,26 @@ def cross_phase(planes):
     return np.arctan2(p[3], p[2])
 
 
+def coherence_matrix(V):
+    """The magnitude-squared coherence of every pair of include/rpf_engine.h (rpf_correlate_device) from the (M, M, N)
+    visibilities V:  gamma^2_ij = (re^2 + im^2) / (V_ii V_jj), with V_ii the real diagonal, in double in exactly this order
+    (the C++ host's coherence_pair, host/datastore.h, does the same operations).  NaN where V_ii V_jj == 0; not clamped.
+    The diagonal is 1 wherever the power is not 0.  Of F frames it is biased: identically 1 for F = 1, about 1/F for
+    unrelated streams."""
+    V = np.asarray(V)
+    if V.ndim != 3 or V.shape[0] != V.shape[1]:
+        raise ValueError("coherence_matrix: V must be (M, M, N)")
+    re, im = np.real(V).astype(np.float64), np.imag(V).astype(np.float64)
+    auto = np.real(np.diagonal(V, axis1=0, axis2=1)).T.astype(np.float64)       # (M, N)
+    den = auto[:, None, :] * auto[None, :, :]
+    num = re * re + im * im
+    out = np.full(num.shape, np.nan)
+    ok = den != 0.0
+    with np.errstate(invalid="ignore", over="ignore"):
+        out[ok] = num[ok] / den[ok]
+    return out
+
+
 def quantiles(rows, q):
     """The per-bin quantiles of include/rpf_engine.h (rpf_quantile_select_device) stated in numpy, on (K, N) rows: with
     v_(0) <= ... <= v_(K-1) the values of a bin in np.sort's order (a NaN last), h = q (K - 1), j = floor(h), g = h - j,
