@@ -42,7 +42,8 @@ extern "C" {
                                rpf_quantile_select_device, rpf_quantile_select, rpf_quantile_rows, rpf_quantile_max_rows;
                                rpf_accumulate_device_cross, rpf_accumulate_cross;
                                rpf_stft_device, rpf_stft;
-                               rpf_correlate_device, rpf_correlate */
+                               rpf_correlate_device, rpf_correlate;
+                               rpf_dedisperse_device, rpf_dedisperse, rpf_dedisperse_times */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -404,6 +405,57 @@ int rpf_correlate_device(rpf_engine* e, const void* const* d_streams, int n_stre
                          double* d_out /* M x M x 2 x N */, void* hip_stream, int64_t* frames_done);
 int rpf_correlate(rpf_engine* e, const uint8_t* const* streams, int n_streams, size_t nbytes, int64_t repeats,
                   double* out /* host */, int64_t* frames_done);
+
+/* Incoherent dedispersion of the stored integrations: the DM-time plane, a second reader of the quantile entries' row
+ * store.  Everything that computes or checks it refers to this definition.
+ *   Rows.  The store holds K = rpf_quantile_rows(e) rows r[k][b] of N doubles, bin N/2 = DC, bit for bit what
+ *     rpf_accumulate_device_series writes (rpf_quantile_append[_device] put them there).
+ *   Inputs, on the host.  delays: D x N int32, delays[d N + b] >= 0, counted in integrations (rows).  weights: N doubles,
+ *     or NULL for all ones.  D = n_trials, 1 <= D <= 4096.
+ *   Times.  Dmax = the largest entry of the whole table; T = max(0, K - Dmax) (rpf_dedisperse_times).
+ *   Output.  For every trial d < D and time t < T, in IEEE double with no contraction, every product and every sum
+ *     rounded on its own:
+ *         acc = +0.0
+ *         for b = 0 ... N-1, ascending:   if weights[b] != 0:   acc = acc + weights[b] r[t + delays[d][b]][b]
+ *         out[d T + t] = acc
+ *     With weights == NULL the term is the row value itself.  A bin of weight 0 is NOT READ: that is how the DC spike or a
+ *     flagged channel is left out.  A NaN in a row that some bin of non-zero weight reads makes exactly those outputs
+ *     NaN.  The order is ascending in b for every output; no atomics, no cross-lane sums: the bits do not depend on the
+ *     grid, the tiling or the route.  numpy gives the same bits with
+ *         for b: acc = acc + w[b] * rows[delays[d, b] : delays[d, b] + T, b]          (dedisperse.reference)
+ *   The store is read-only in this call: selecting quantiles before or after, appending more rows and dedispersing again,
+ *     and a second identical call are all defined.
+ *   The kernel knows no physics.  The delay table of a dispersion measure is built on the host, once in C++ (dm_delays of
+ *     host/datastore.h) and once in Python (dedisperse.dm_delays), both by exactly this double-precision sequence,
+ *     uncontracted, so the integers agree everywhere:
+ *         f_b   = (fc + (b - N/2) (rate / N)) / 1e6          [MHz; fc the tuned frequency in Hz, rate in samples/s]
+ *         inv_b = 1.0 / (f_b f_b);    ref = inv_(N-1);    t_row = (L S) / rate     [S the frame step, L frames per row]
+ *         delays[d][b] = (int32) floor(((4.148808e3 dm_d) (inv_b - ref)) / t_row + 0.5)
+ *     The highest bin is the reference, its delay 0.  Refused there: f_0 <= 0; a dm that is negative or not finite; a
+ *     delay that does not fit int32.
+ * How (csrc/rpf_dedisperse.hip over csrc/dedisperse_core.h): a workgroup owns 64 consecutive times x 16 trials and walks
+ * the bins in blocks of 32, ascending; per block it stages rows [t0 + lo, t0 + 64 + hi) x 32 bins into LDS, lo and hi the
+ * smallest and largest delay of the tile's trials over the block's bins of non-zero weight (computed here on the host
+ * when the table is uploaded); a lane keeps its (trial, time) sums in registers.  A (tile, block) whose span exceeds the
+ * LDS tile (hi - lo > 160) is read straight from the store: correct and slow.  One launch, no scratch.
+ * rpf_dedisperse_device uploads the weights, the spans and the table into engine-owned memory (pinned and device, made at
+ * the first call, grown for a larger table; an engine that never dedisperses allocates nothing), enqueues the copy and
+ * the launch on `hip_stream` and returns without synchronising; d_out holds `capacity` doubles, of which D T are
+ * written, and *times = T.  A call waits on the host for the launch of the call before it (the tables serve one call at
+ * a time).  rpf_dedisperse is the same on the engine's stream into engine scratch, copied to `out`; it synchronises.
+ * With T = 0 both return RPF_OK with *times = 0 and write nothing.  Nothing else of the engine moves: queues, pwr,
+ * repeats_done, the store, the selection state, the cross, STFT and correlator scratch.
+ * RPF_ERR_INVALID_ARGUMENT, before any device work, with the output untouched and *times = 0: a NULL e, delays,
+ * d_out / out or times; n_trials < 1 or > 4096; a negative delay; a weight that is not finite; D T > capacity; d_out not
+ * 16-byte aligned (device entry); a running acquisition; a PFB engine or an RPF_FLAG_BIN_STATS engine (the store's own
+ * refusals).  rpf_dedisperse_times: T for this table and the rows stored now; -1 for a NULL argument, n_trials < 1 or a
+ * negative delay. */
+int rpf_dedisperse_device(rpf_engine* e, const int32_t* delays /* host, D x N */, const double* weights /* host, N, or NULL */,
+                          int n_trials, double* d_out /* device, D x T, 16-byte aligned */, int64_t capacity /* doubles */,
+                          void* hip_stream, int64_t* times /* T */);
+int rpf_dedisperse(rpf_engine* e, const int32_t* delays, const double* weights, int n_trials, double* out /* host */,
+                   int64_t capacity, int64_t* times);
+int64_t rpf_dedisperse_times(const rpf_engine* e, const int32_t* delays, int n_trials);
 
 /* The two halves of rpf_accumulate_device as separate enqueues, so that a
  * benchmark can bracket the dominant kernel alone with events on `hip_stream`:

@@ -31,4 +31,6 @@ for l in sys.stdin:
                 tag = 'correlate_xengine M=%s' % f.group(1)
             elif 'correlate_reduce_kernel' in cur or 'correlate_finish_kernel' in cur:
                 tag = re.search(r'(correlate_\w+?)_kernel', cur).group(1)
+            if 'dedisperse_kernel' in cur:
+                tag = 'dedisperse LDS=%s' % m.group(2)
             print(tag, {k: d.get(k) for k in ('VGPRs', 'AGPRs', 'ScratchSize', 'Occupancy', 'VGPRs Spill')})

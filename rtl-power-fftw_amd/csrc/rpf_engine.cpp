@@ -38,6 +38,7 @@
 #include "bluestein_tables.h"
 #include "cross_core.h"
 #include "correlate_core.h"
+#include "dedisperse_core.h"
 #include "engine_family.h"
 #include "rpf_kernels.h"
 #include "series_pieces.h"
@@ -203,6 +204,13 @@ struct rpf_engine {
     size_t corr_partial = 0;              // ... doubles it holds
     double* d_corr_planes = nullptr;      // the M^2 running planes, then the host entry's result: 3 M^2 N doubles
     size_t corr_planes = 0;               // ... doubles it holds
+    // incoherent dedispersion of the stored integrations (rpf_dedisperse_device, rpf_dedisperse); made at the first call
+    uint8_t* h_dd_tables = nullptr;       // pinned: the weights, the spans and the delay table of one call, as uploaded
+    uint8_t* d_dd_tables = nullptr;       // ... and on the device
+    size_t dd_tables_bytes = 0;           // ... bytes each holds
+    hipEvent_t dd_done = nullptr;         // after the last call's launch: the tables may be overwritten once it has passed
+    double* d_dd_out = nullptr;           // rpf_dedisperse: the D x T result on the device
+    size_t dd_out = 0;                    // ... doubles it holds
 
     mutable std::string last_error;
 };
@@ -934,6 +942,10 @@ void release_device(rpf_engine* e)
     (void)hipFree(e->d_corr_rows);
     (void)hipFree(e->d_corr_partial);
     (void)hipFree(e->d_corr_planes);
+    (void)hipFree(e->d_dd_tables);
+    (void)hipFree(e->d_dd_out);
+    if (e->h_dd_tables) (void)hipHostFree(e->h_dd_tables);
+    if (e->dd_done) (void)hipEventDestroy(e->dd_done);
     if (e->stft_inner) {
         release_device(e->stft_inner);
         delete e->stft_inner;
@@ -2748,6 +2760,136 @@ int rpf_quantile_select(rpf_engine* e, const double* q, int nq, double* out)
     if ((rc = quantile_select_enqueue(e, ranks, e->d_quantile_out, s)) != RPF_OK) return rc;
     HIP_TRY(e, hipMemcpyAsync(out, e->d_quantile_out, sizeof(double) * static_cast<size_t>(nq) * e->N, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
+    return RPF_OK;
+}
+
+// ---- incoherent dedispersion of the stored integrations: rpf_dedisperse_device, rpf_dedisperse (include/rpf_engine.h) --
+
+// The largest entry of the D x N table, or -1 where one is negative (*at = its index).
+static int64_t dedisperse_dmax(const int32_t* delays, size_t cells, size_t* at)
+{
+    int32_t dmax = 0;
+    for (size_t i = 0; i < cells; ++i) {
+        if (delays[i] < 0) {
+            if (at) *at = i;
+            return -1;
+        }
+        dmax = std::max(dmax, delays[i]);
+    }
+    return dmax;
+}
+
+// Everything both entries refuse, before any device work; *T = the times of the call.
+static int dedisperse_check(rpf_engine* e, const char* who, const int32_t* delays, const double* weights, int n_trials,
+                            const void* out, int64_t capacity, int64_t* times, int64_t* T)
+{
+    if (times) *times = 0;
+    const int rc = quantile_check(e, who);
+    if (rc != RPF_OK) return rc;
+    const std::string me = who;
+    if (!delays || !out || !times) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+    if (n_trials < 1 || n_trials > rpf::kDedispMaxTrials)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": n_trials must be in 1 .. " + std::to_string(rpf::kDedispMaxTrials) + ", got " + std::to_string(n_trials));
+    const size_t N = static_cast<size_t>(e->N);
+    size_t at = 0;
+    const int64_t dmax = dedisperse_dmax(delays, static_cast<size_t>(n_trials) * N, &at);
+    if (dmax < 0)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": negative delay " + std::to_string(delays[at]) + " at trial " + std::to_string(at / N) + ", bin " +
+                        std::to_string(at % N));
+    for (size_t b = 0; weights && b < N; ++b)
+        if (!std::isfinite(weights[b]))
+            return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": weights[" + std::to_string(b) + "] is not finite");
+    *T = rpf::dedisperse_times(e->quantile_rows, dmax);
+    if (static_cast<int64_t>(n_trials) * *T > capacity)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": " + std::to_string(n_trials) + " trials of " + std::to_string(*T) + " times need " +
+                        std::to_string(static_cast<int64_t>(n_trials) * *T) + " doubles, the capacity is " + std::to_string(capacity));
+    return RPF_OK;
+}
+
+// Uploads the weights (NULL: ones), the spans of dedisperse_core.h and the table into the engine's tables, then the
+// launch, all on `s`.  The tables serve one call at a time: the call before this one has passed dd_done by then.
+static int dedisperse_enqueue(rpf_engine* e, const int32_t* delays, const double* weights, int D, int64_t T, double* d_out,
+                              hipStream_t s)
+{
+    const size_t N = static_cast<size_t>(e->N);
+    const int tiles = rpf::dedisperse_trial_tiles(D), nblocks = rpf::dedisperse_bin_blocks(e->N);
+    const size_t spans_at = sizeof(double) * N, delays_at = spans_at + sizeof(rpf::DedispSpan) * tiles * nblocks;
+    const size_t bytes = delays_at + sizeof(int32_t) * static_cast<size_t>(D) * N;
+    if (e->dd_done)
+        HIP_TRY(e, hipEventSynchronize(e->dd_done));
+    else
+        HIP_TRY(e, hipEventCreateWithFlags(&e->dd_done, hipEventDisableTiming));
+    if (bytes > e->dd_tables_bytes) {
+        if (e->h_dd_tables) (void)hipHostFree(e->h_dd_tables);
+        (void)hipFree(e->d_dd_tables);
+        e->h_dd_tables = e->d_dd_tables = nullptr;
+        e->dd_tables_bytes = 0;
+        HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_dd_tables), bytes, hipHostMallocDefault));
+        HIP_TRY(e, hipMalloc(&e->d_dd_tables, bytes));
+        e->dd_tables_bytes = bytes;
+    }
+    double* const w = reinterpret_cast<double*>(e->h_dd_tables);
+    if (weights)
+        std::copy(weights, weights + N, w);
+    else
+        std::fill(w, w + N, 1.0);
+    rpf::DedispSpan* const spans = reinterpret_cast<rpf::DedispSpan*>(e->h_dd_tables + spans_at);
+    for (int tile = 0; tile < tiles; ++tile)
+        for (int blk = 0; blk < nblocks; ++blk) spans[tile * nblocks + blk] = rpf::dedisperse_span(delays, w, e->N, D, tile, blk);
+    std::memcpy(e->h_dd_tables + delays_at, delays, bytes - delays_at);
+    HIP_TRY(e, hipMemcpyAsync(e->d_dd_tables, e->h_dd_tables, bytes, hipMemcpyHostToDevice, s));
+    const hipError_t launched = rpf::launch_dedisperse(e->d_quantile_rows, e->quantile_rows, e->N,
+                                                       reinterpret_cast<const int32_t*>(e->d_dd_tables + delays_at),
+                                                       reinterpret_cast<const double*>(e->d_dd_tables),
+                                                       e->d_dd_tables + spans_at, D, T, d_out, s);
+    // (recorded whether or not the launch went out: the copy above reads the pinned block until then)
+    HIP_TRY(e, hipEventRecord(e->dd_done, s));
+    HIP_TRY(e, launched);
+    return RPF_OK;
+}
+
+int64_t rpf_dedisperse_times(const rpf_engine* e, const int32_t* delays, int n_trials)
+{
+    if (!e || !delays || n_trials < 1) return -1;
+    const int64_t dmax = dedisperse_dmax(delays, static_cast<size_t>(n_trials) * static_cast<size_t>(e->N), nullptr);
+    return dmax < 0 ? -1 : rpf::dedisperse_times(e->quantile_rows, dmax);
+}
+
+int rpf_dedisperse_device(rpf_engine* e, const int32_t* delays, const double* weights, int n_trials, double* d_out,
+                          int64_t capacity, void* hip_stream, int64_t* times)
+{
+    const char* who = "rpf_dedisperse_device";
+    int64_t T = 0;
+    const int rc = dedisperse_check(e, who, delays, weights, n_trials, d_out, capacity, times, &T);
+    if (rc != RPF_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(d_out) & 15)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
+    if (T == 0) return RPF_OK;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    if (int err = dedisperse_enqueue(e, delays, weights, n_trials, T, d_out, static_cast<hipStream_t>(hip_stream))) return err;
+    *times = T;
+    return RPF_OK;
+}
+
+int rpf_dedisperse(rpf_engine* e, const int32_t* delays, const double* weights, int n_trials, double* out, int64_t capacity,
+                   int64_t* times)
+{
+    int64_t T = 0;
+    int rc = dedisperse_check(e, "rpf_dedisperse", delays, weights, n_trials, out, capacity, times, &T);
+    if (rc != RPF_OK || T == 0) return rc;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = e->compute_stream;
+    const size_t cells = static_cast<size_t>(n_trials) * static_cast<size_t>(T);
+    if ((rc = grow_scratch(e, &e->d_dd_out, &e->dd_out, cells, sizeof(double), s)) != RPF_OK) return rc;
+    if ((rc = dedisperse_enqueue(e, delays, weights, n_trials, T, e->d_dd_out, s)) != RPF_OK) return rc;
+    HIP_TRY(e, hipMemcpyAsync(out, e->d_dd_out, sizeof(double) * cells, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    *times = T;
     return RPF_OK;
 }
 

@@ -252,6 +252,13 @@ hipError_t launch_correlate_xengine(const float* d_rows, long stride, int M, int
 // d_out[M][M][2][N] (Hermitian; diagonal im 0) from the M^2 running planes (not in place).
 hipError_t launch_correlate_finish(const double* d_planes, int M, int N, double* d_out, hipStream_t stream);
 
+// ---- incoherent dedispersion of the stored integrations (rpf_dedisperse.hip, dedisperse_core.h) -----------------------
+// d_out[D x T] = the sums of include/rpf_engine.h (rpf_dedisperse_device) over rows [0, K) of N doubles: d_delays[D x N]
+// and d_weights[N] on the device, every delay in [0, K - T]; d_spans = DedispSpan[trial tiles x bin blocks], dedisperse_span
+// of that table and those weights.  T < 1 launches nothing.
+hipError_t launch_dedisperse(const double* d_rows, long K, int N, const int32_t* d_delays, const double* d_weights,
+                             const void* d_spans, int D, long T, double* d_out, hipStream_t stream);
+
 // Master twiddle table W_N^k = exp(-2 pi i k / N), k in [0,N), evaluated in
 // long double and rounded once to float.
 void make_twiddles(int N, std::vector<cf>& out);

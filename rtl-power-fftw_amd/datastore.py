@@ -470,6 +470,47 @@ class Datastore:
                                                   out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
         return out[:q.size]
 
+    # -- incoherent dedispersion of the stored rows (rpf_dedisperse[_device]; include/rpf_engine.h has the definition) --
+    def _dedisperse_args(self, delays, weights):
+        delays = np.ascontiguousarray(np.atleast_2d(np.asarray(delays)), dtype=np.int32)
+        if delays.ndim != 2 or delays.shape[1] != self.params.N:
+            raise RPFError("dedisperse: delays must be (D, N) with N = %d; got shape %s." % (self.params.N, delays.shape),
+                           ReturnValue.InvalidArgument)
+        wp = None
+        if weights is not None:
+            weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+            if weights.size != self.params.N:
+                raise RPFError("dedisperse: weights must hold N = %d values; got %d." % (self.params.N, weights.size),
+                               ReturnValue.InvalidArgument)
+            wp = weights.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        return delays, delays.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), weights, wp
+
+    def dedisperse_times(self, delays):
+        """rpf_dedisperse_times: T = max(0, rows stored - largest delay) for this table."""
+        delays, dp, _, _ = self._dedisperse_args(delays, None)
+        return self._lib.rpf_dedisperse_times(self._handle, dp, delays.shape[0])
+
+    def dedisperse_device(self, delays, weights, d_out_ptr, capacity, hip_stream=0):
+        """rpf_dedisperse_device: the DM-time plane of the stored rows for the host table delays (D, N) and the host
+        weights (N, or None for ones) into d_out = `capacity` device doubles, D x T of them written; asynchronous.
+        Returns T."""
+        delays, dp, weights, wp = self._dedisperse_args(delays, weights)
+        times = ctypes.c_int64()
+        self._check(self._lib.rpf_dedisperse_device(self._handle, dp, wp, delays.shape[0], ctypes.c_void_p(d_out_ptr),
+                                                    capacity, ctypes.c_void_p(hip_stream), ctypes.byref(times)))
+        return times.value
+
+    def dedisperse(self, delays, weights=None):
+        """rpf_dedisperse: the same into a (D, T) array; dedisperse.reference(rows, delays, weights) of the stored rows."""
+        delays, dp, weights, wp = self._dedisperse_args(delays, weights)
+        D = delays.shape[0]
+        T = max(self._lib.rpf_dedisperse_times(self._handle, dp, D), 0)
+        out = np.zeros(max(D * T, 1), dtype=np.float64)
+        times = ctypes.c_int64()
+        self._check(self._lib.rpf_dedisperse(self._handle, dp, wp, D, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                             D * T, ctypes.byref(times)))
+        return out[:D * times.value].reshape(D, times.value)
+
     def accumulate_quantiles(self, stream, frames_per_spectrum, q=(0.5,), max_spectra=None):
         """Reset, append, select: the per-bin quantiles q over the integrations of `frames_per_spectrum` frames of a
         host stream.  Returns ((len(q), N) array, K)."""

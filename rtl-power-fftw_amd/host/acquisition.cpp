@@ -303,6 +303,28 @@ void write_spectrum_text_correlate(std::ostream& out, const std::vector<double>&
     });
 }
 
+void write_text_header_dedisperse(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, double dm,
+                                  int64_t largest_delay)
+{
+    out << "# rtl-power-fftw output" << std::endl;
+    out << "# Acquisition start: " << start_stamp << std::endl;
+    out << "# Acquisition end: " << end_stamp << std::endl;
+    out << "# DM " << std::setprecision(6) << dm << " pc cm^-3, largest delay " << largest_delay << " integrations" << std::endl;
+    out << "#" << std::endl;
+    out << "# time [s] power [median units]" << std::endl;
+}
+
+void write_text_dedisperse(std::ostream& out, const double* trial, int64_t T, int64_t nb, int64_t L, int64_t step, int samplerate,
+                           bool linear)
+{
+    for (int64_t t = 0; t < T; ++t) {
+        const double time = static_cast<double>(t * L * step) / samplerate, p = trial[t] / static_cast<double>(nb);
+        out << std::setprecision(9) << time << std::setprecision(6) << " " << (linear ? p : 10 * std::log10(p)) << std::endl;
+    }
+    out << std::endl;
+    out.flush();
+}
+
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,
                          const std::vector<double>* baseline, std::vector<float>& row)
 {

@@ -137,6 +137,14 @@ void write_spectrum_text_correlate(std::ostream& out, const std::vector<double>&
                                    int64_t tuned_freq, int samplerate, bool linear, const std::vector<double>* baseline);
 void write_spectrum_text_cross(std::ostream& out, const std::vector<double>& planes, int N, int64_t frames, int64_t tuned_freq,
                                int samplerate, bool linear, const std::vector<double>* baseline);
+// --dedisperse: one block per trial.  The header carries one more line, "# DM <dm> pc cm^-3, largest delay <n>
+// integrations", and names the columns time [s] and power [median units]; the block is one line per time t < T:
+// t L S / samplerate in nine digits, then trial[t] / nb (nb = the bins of non-zero weight) in six, in dB unless
+// `linear`; a blank line ends it.
+void write_text_header_dedisperse(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, double dm,
+                                  int64_t largest_delay);
+void write_text_dedisperse(std::ostream& out, const double* trial, int64_t T, int64_t nb, int64_t L, int64_t step, int samplerate,
+                           bool linear);
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,
                          const std::vector<double>* baseline, std::vector<float>& row);
 // Matrix mode: append one float32 row to options.bin_file and keep the row/column

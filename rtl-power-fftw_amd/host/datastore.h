@@ -135,6 +135,40 @@ inline double cross_phase(double re, double im) { return std::atan2(im, re); }
 // of the two autos (stats.py's coherence_matrix does the same operations); NaN where V_ii V_jj = 0; not clamped.
 inline double coherence_pair(double vii, double vjj, double re, double im) { return coherence(vii, vjj, re, im); }
 
+// The delay table of the dispersion measures `dms` [pc cm^-3] for rpf_dedisperse (include/rpf_engine.h has the
+// sequence; dedisperse.py's dm_delays does the same operations, so the integers agree): D x N int32, in integrations of
+// L frames at step S, the highest bin the reference.  The one product that feeds a sum goes through a volatile, so no
+// compiler can fuse the two.
+inline std::vector<int32_t> dm_delays(const std::vector<double>& dms, double fc, double rate, int N, int64_t L, int64_t S) {
+  if (N < 1 || L < 1 || S < 1 || !(rate > 0))
+    throw RPFexception("dm_delays: N, L, the frame step and the rate must be positive.", ReturnValue::InvalidArgument);
+  std::vector<double> inv(N);
+  for (int b = 0; b < N; ++b) {
+    volatile double off = static_cast<double>(b - N / 2) * (rate / static_cast<double>(N));
+    const double f = (fc + off) / 1e6;
+    if (b == 0 && !(f > 0))
+      throw RPFexception("dm_delays: the lowest bin's frequency must be positive, got " + std::to_string(f) + " MHz.",
+                         ReturnValue::InvalidArgument);
+    inv[b] = 1.0 / (f * f);
+  }
+  const double ref = inv[N - 1], t_row = (static_cast<double>(L) * static_cast<double>(S)) / rate;
+  std::vector<int32_t> out(dms.size() * static_cast<size_t>(N));
+  for (size_t d = 0; d < dms.size(); ++d) {
+    if (!(dms[d] >= 0) || std::isinf(dms[d]))
+      throw RPFexception("dm_delays: a dispersion measure must be finite and not negative, got " + std::to_string(dms[d]) + ".",
+                         ReturnValue::InvalidArgument);
+    const double k = 4.148808e3 * dms[d];
+    for (int b = 0; b < N; ++b) {
+      const double v = std::floor((k * (inv[b] - ref)) / t_row + 0.5);
+      if (!(v < 2147483648.0))
+        throw RPFexception("dm_delays: the delay of DM " + std::to_string(dms[d]) + " at bin " + std::to_string(b) +
+                           " does not fit 32 bits.", ReturnValue::InvalidArgument);
+      out[d * N + b] = static_cast<int32_t>(v);
+    }
+  }
+  return out;
+}
+
 // A filled/empty hand-off buffer: what `Buffer&` is in acquisition.cxx:283,302-304
 // (data()/size()/resize()), backed by engine-owned pinned memory.
 class Buffer {
@@ -369,6 +403,27 @@ public:
   // the same into d_out = q.size() x N device doubles (rpf_quantile_select_device), asynchronous on hip_stream
   void quantile_select_device(const std::vector<double>& q, double* d_out, void* hip_stream = nullptr) {
     check(rpf_quantile_select_device(engine_, q.data(), static_cast<int>(q.size()), d_out, hip_stream));
+  }
+  // Incoherent dedispersion of the stored rows (rpf_dedisperse; include/rpf_engine.h has the definition): delays = D x N
+  // (dm_delays above makes a DM table), weights = N values or empty for all ones; `out` (resized to D x T) = the
+  // DM-time plane.  The store is only read.  Returns T.
+  int64_t dedisperse(const std::vector<int32_t>& delays, const std::vector<double>& weights, std::vector<double>& out) {
+    const int D = static_cast<int>(delays.size() / static_cast<size_t>(params.N));
+    const int64_t T = std::max<int64_t>(rpf_dedisperse_times(engine_, delays.data(), D), 0);
+    out.assign(std::max<size_t>(static_cast<size_t>(D) * static_cast<size_t>(T), 1), 0.0);
+    int64_t times = 0;
+    check(rpf_dedisperse(engine_, delays.data(), weights.empty() ? nullptr : weights.data(), D, out.data(),
+                         static_cast<int64_t>(D) * T, &times));
+    out.resize(static_cast<size_t>(D) * static_cast<size_t>(times));
+    return times;
+  }
+  // the same into d_out = `capacity` device doubles (rpf_dedisperse_device), asynchronous on hip_stream
+  int64_t dedisperse_device(const std::vector<int32_t>& delays, const std::vector<double>& weights, double* d_out,
+                            int64_t capacity, void* hip_stream = nullptr) {
+    int64_t times = 0;
+    check(rpf_dedisperse_device(engine_, delays.data(), weights.empty() ? nullptr : weights.data(),
+                                static_cast<int>(delays.size() / static_cast<size_t>(params.N)), d_out, capacity, hip_stream, &times));
+    return times;
   }
   // transform launches of the last series call: 1 = the one-launch path
   int series_launches() const { return rpf_series_launches(engine_); }

@@ -475,6 +475,41 @@ int rpf_host_parse_quantiles(int argc, const char* const* argv, long long* frame
     }));
 }
 
+// The --dedisperse options of a parsed command line: frames, and the trials of --dm into dms[cap_dms]; returns the number
+// of trials (0 without --dedisperse), or -(exit code) with the message in `msg`.
+int rpf_host_parse_dedisperse(int argc, const char* const* argv, long long* frames, double* dms, int cap_dms, char* msg, size_t cap)
+{
+    return static_cast<int>(or_exit_code(msg, cap, [&]() -> long long {
+        Options o = parse_command_line(argc, argv);
+        *frames = o.dedisperse_frames;
+        int n = 0;
+        for (double v : o.dms)
+            if (n < cap_dms) dms[n++] = v;
+        return n;
+    }));
+}
+
+// datastore.h's dm_delays into out[n_dms x N]; 0, or -(exit code) with the message in `msg`.
+int rpf_host_dm_delays(const double* dms, int n_dms, double fc, double rate, int N, long long L, long long step, int* out,
+                       char* msg, size_t cap)
+{
+    return static_cast<int>(or_exit_code(msg, cap, [&]() -> long long {
+        const std::vector<int32_t> d = dm_delays(std::vector<double>(dms, dms + n_dms), fc, rate, N, L, step);
+        std::copy(d.begin(), d.end(), out);
+        return 0;
+    }));
+}
+
+// The --dedisperse header and block of one trial (write_text_header_dedisperse, write_text_dedisperse).
+long rpf_host_format_text_dedisperse(const double* trial, long long T, long long nb, long long L, long long step, int samplerate,
+                                     int linear, double dm, long long largest_delay, char* out, size_t cap)
+{
+    std::ostringstream os;
+    write_text_header_dedisperse(os, "a", "b", dm, largest_delay);
+    write_text_dedisperse(os, trial, T, nb, L, step, samplerate, linear != 0);
+    return copy_out(os.str(), out, cap);
+}
+
 void rpf_host_synthetic(unsigned long long seed, unsigned long long first, unsigned long long n, unsigned char* out)
 {
     SyntheticSource::generate(seed, first, n, out);

@@ -102,6 +102,13 @@ const Spec kSpecs[] = {
     // --frame-overlap and --pfb; not with a frequency range, -n, -t, -c, -e, -m, --stats, --series, --series-stats,
     // --excise, --quantile, --cross, --stft or several --gpus).
     {0, "correlate", Kind::Text, "b,c,...", nullptr},
+    // Incoherent dedispersion of --input: the replay is cut into integrations of <frames> consecutive FFT frames, every bin
+    // is divided by its median over them, and for every dispersion measure of --dm (one value, or lo:hi:step; at most 4096
+    // trials; pc cm^-3) the bins are added along that DM's delay curve: one block of time and power per trial (combines
+    // with -w, --format, --frame-overlap and -l; not with a frequency range, -n, -t, -c, -e, -m, -B, --stats, --series,
+    // --series-stats, --excise, --quantile, --cross, --stft, --correlate, --pfb or several --gpus).
+    {0, "dedisperse", Kind::Int64, "frames", nullptr},
+    {0, "dm", Kind::Text, "lo:hi:step | value", nullptr},
     {0, "reduce", Kind::Text, "rccl|host", "With --gpus: where a scan's per-device spectra are added (default: rccl if it loads, else host)."},
     {'h', "help", Kind::Flag, "", "Displays usage information and exits."},
     {0, "version", Kind::Flag, "", "Displays version information and exits."},
@@ -185,7 +192,7 @@ void require_non_negative(const Parsed& p, const char* name)
 // A replay mode is an option that reads --input once, to its end, outside the acquisition loop.  One row each, in the
 // order their refusals speak; replay_mode() below walks a row.
 struct Refused { const char* option; const char* why; };
-constexpr int kMaxRefused = 7;      // the most options one row refuses; the entry after them stays null (rows_end below)
+constexpr int kMaxRefused = 9;      // the most options one row refuses; the entry after them stays null (rows_end below)
 struct ReplayMode {
     const char* name;
     int64_t Options::*frames;       // where its <frames> goes, checked against min_frames; null: the argument is a file
@@ -204,6 +211,7 @@ const char kOneProduct[] = "one product of the integrations per run";
 const char kSums[] = "those end in sums of |X|^2, this writes X itself";
 const char kNoCross[] = "cross-spectra of those are not built";
 const char kNoCorrelate[] = "visibilities of those are not built";
+const char kPlainRows[] = "it reads the row store, which holds the plain series of one stream";
 
 constexpr ReplayMode kReplayModes[] = {
     {"series", &Options::series_frames, 1, "", "it cuts a replayed stream into consecutive integrations", kOwnLength,
@@ -229,6 +237,11 @@ constexpr ReplayMode kReplayModes[] = {
      {{"stats", kNoCorrelate}, {"series", kNoCorrelate}, {"series-stats", kNoCorrelate}, {"excise", kNoCorrelate},
       {"quantile", kNoCorrelate}, {"cross", "--cross is the correlator's two-stream special case"},
       {"stft", "that writes the frames' spectra themselves"}}},
+    {"dedisperse", &Options::dedisperse_frames, 1, "", "it adds the integrations of a replayed stream along delay curves",
+     kOwnLength, "the DM-time plane is one text block per trial", false,
+     {{"stats", kPlainRows}, {"series", kOneProduct}, {"series-stats", kOneProduct}, {"excise", kOneProduct},
+      {"quantile", kOneProduct}, {"cross", kPlainRows}, {"stft", kPlainRows}, {"correlate", kPlainRows},
+      {"pfb", kPlainRows}}},
 };
 
 // replay_mode() walks a row's refusals to the first null: every row keeps its last entry for it.
@@ -242,6 +255,36 @@ static_assert(rows_end(0), "a row of kReplayModes refuses more than kMaxRefused 
 [[noreturn]] void refuse(const std::string& mode, const std::string& what)
 {
     throw RPFexception("Option --" + mode + " " + what + " Exiting.", ReturnValue::InvalidArgument);
+}
+
+// --dm <value> or <lo:hi:step>: the trials lo + i step for i = 0 ... floor((hi - lo) / step + 1e-9), at most 4096 of them,
+// none negative.
+std::vector<double> parse_dm_list(const std::string& text)
+{
+    std::vector<double> part;
+    size_t pos = 0;
+    bool good = true;
+    while (pos <= text.size()) {
+        const size_t colon = std::min(text.find(':', pos), text.size());
+        const std::string item = text.substr(pos, colon - pos);
+        char* end = nullptr;
+        const double v = std::strtod(item.c_str(), &end);
+        // (digits, a point and an exponent only: strtod alone would also take blanks, hexadecimal and "inf")
+        good = good && !item.empty() && item.find_first_not_of("0123456789.eE+-") == std::string::npos && *end == '\0' &&
+               std::isfinite(v) && v >= 0.0;
+        part.push_back(v);
+        pos = colon + 1;
+    }
+    good = good && (part.size() == 1 || (part.size() == 3 && part[1] >= part[0] && part[2] > 0.0));
+    if (!good)
+        refuse("dedisperse", "could not use the value given to --dm: " + text +
+                                 ". Expecting one dispersion measure or lo:hi:step, none negative, hi >= lo and step > 0.");
+    if (part.size() == 1) return part;
+    const double count = std::floor((part[1] - part[0]) / part[2] + 1e-9) + 1.0;
+    if (count > 4096.0) refuse("dedisperse", "takes at most 4096 trials in --dm, got " + std::to_string(static_cast<long long>(std::min(count, 1e18))) + ".");
+    std::vector<double> dms;
+    for (int i = 0; i < static_cast<int>(count); ++i) dms.push_back(part[0] + i * part[2]);
+    return dms;
 }
 
 // False when the command line does not name the mode; else takes its frame count, throws the first of the row's
@@ -539,6 +582,14 @@ Options parse_command_line(int argc, const char* const* argv)
         int from_stdin = p.get("input") == "-";
         for (const std::string& f : o.correlate_files) from_stdin += f == "-";
         if (from_stdin > 1) refuse("correlate", "cannot read more than one stream from stdin.");
+    }
+    if (p.has("dm") && !p.has("dedisperse"))
+        throw RPFexception("Option --dm needs --dedisperse: it lists the dispersion measures that one tries. Exiting.",
+                           ReturnValue::InvalidArgument);
+    if (replay_mode("dedisperse", p, o)) {
+        if (o.baseline) refuse("dedisperse", "does not combine with --baseline (-B): the power is in units of every bin's median.");
+        if (!p.has("dm")) refuse("dedisperse", "needs --dm: the dispersion measures to try, one value or lo:hi:step.");
+        o.dms = parse_dm_list(p.get("dm"));
     }
     if (p.has("input")) o.input_file = p.get("input");
     o.synthetic = p.has("synthetic");

@@ -481,6 +481,14 @@ int run_excise(const Options& options, AuxData& aux, int actual_samplerate, int6
     return 0;
 }
 
+// What --quantile and --dedisperse say when the replay holds more integrations than the engine's row store keeps.
+[[noreturn]] static void refuse_more_rows(int64_t max_rows, int64_t L, int N)
+{
+    throw RPFexception("Option --quantile: the input holds more than " + std::to_string(max_rows) + " integrations of " +
+                       std::to_string(L) + " frames, which is what the device keeps of " + std::to_string(N) +
+                       " bins (1 GiB of rows): raise <frames>. Exiting.", ReturnValue::InvalidArgument);
+}
+
 // --quantile <frames> [--quantiles a,b,...]: every bin's quantiles over the replay's integrations of <frames> frames
 // (rpf_quantile_append per piece, ONE rpf_quantile_select at the end), one block for the file.  The file is read in
 // pieces of whole integrations as run_series reads it; the rows stay in the engine's store on the device.
@@ -496,10 +504,7 @@ int run_quantile(const Options& options, AuxData& aux, int actual_samplerate, in
     const int64_t K = replay_pieces({&in}, [&](size_t have) {
         const int64_t coming = std::min(in.per_piece(), options.frames_in(static_cast<int64_t>(have)) / L);
         if (kept + coming > data.quantile_max_rows())
-            throw RPFexception("Option --quantile: the input holds more than " + std::to_string(data.quantile_max_rows()) +
-                               " integrations of " + std::to_string(L) + " frames, which is what the device keeps of " +
-                               std::to_string(options.N) + " bins (1 GiB of rows): raise <frames>. Exiting.",
-                               ReturnValue::InvalidArgument);
+            refuse_more_rows(data.quantile_max_rows(), L, options.N);
         const int64_t done = data.quantile_append(in.data(), have, L, in.per_piece());
         one_launch = one_launch && (done == 0 || data.series_launches() == 1);
         kept += done;
@@ -514,6 +519,84 @@ int run_quantile(const Options& options, AuxData& aux, int actual_samplerate, in
     std::cout << std::endl;          // (the blank line that closes a pass)
     std::cerr << "Quantiles: " << options.quantiles.size() << " of " << K << " integrations of " << L << " frames ("
               << (one_launch ? "one launch per piece" : "one launch per spectrum") << ")" << std::endl;
+    if (chatty(options)) print_acquisition_summary(options.N, K * L, 0, 0, actual_samplerate);
+    return 0;
+}
+
+// The median of v (the mean of the two middle values for an even count); v is reordered.
+static double median_of(std::vector<double>& v)
+{
+    const size_t n = v.size(), h = n / 2;
+    std::nth_element(v.begin(), v.begin() + h, v.end());
+    const double hi = v[h];
+    return n % 2 ? hi : (*std::max_element(v.begin(), v.begin() + h) + hi) / 2;
+}
+
+// --dedisperse <frames> --dm <lo:hi:step | value>: the DM-time plane of the replay's integrations of <frames> frames.  The
+// file is appended to the engine's row store piece by piece as run_quantile does; then ONE rpf_quantile_select(0.5) gives
+// every bin's median, the weights are w[b] = 1 / median[b] (0 for the DC bin and for a bin whose median is 0), and ONE
+// rpf_dedisperse adds the bins along every trial's delay curve (dm_delays).  One block per trial: time and the mean of the
+// summed bins in units of their medians.
+int run_dedisperse(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
+{
+    Datastore data(options, aux.window_values);
+    const int64_t L = options.dedisperse_frames;
+    const size_t N = static_cast<size_t>(options.N), D = options.dms.size();
+    const std::vector<int32_t> delays = dm_delays(options.dms, static_cast<double>(tuned_freq), static_cast<double>(actual_samplerate),
+                                                  options.N, L, options.step());
+    PieceReader in(options.input_file, options.sample_bytes() * options.N, options.sample_bytes() * options.step(), L);
+    int64_t kept = 0;
+    const std::string start_stamp = Acquisition::utc_now();
+    data.quantile_reset();
+    const int64_t K = replay_pieces({&in}, [&](size_t have) {
+        const int64_t coming = std::min(in.per_piece(), options.frames_in(static_cast<int64_t>(have)) / L);
+        if (kept + coming > data.quantile_max_rows())
+            refuse_more_rows(data.quantile_max_rows(), L, options.N);
+        const int64_t done = data.quantile_append(in.data(), have, L, in.per_piece());
+        kept += done;
+        return done;
+    });
+    std::vector<double> median, weights(N, 0.0), plane;
+    data.quantile_select(std::vector<double>(1, 0.5), median);
+    int64_t nb = 0;
+    for (size_t b = 0; b < N; ++b) {
+        if (b != N / 2 && median[b] != 0.0) weights[b] = 1.0 / median[b];
+        nb += weights[b] != 0.0;
+    }
+    if (nb == 0)
+        throw RPFexception("Option --dedisperse: every bin but DC has a median of 0, so no bin is left to add. Exiting.",
+                           ReturnValue::InvalidInput);
+    const int64_t T = data.dedisperse(delays, weights, plane);
+    const std::string end_stamp = Acquisition::utc_now();
+    // the strongest sample in robust sigmas of its own trial: (x - median) / (1.4826 MAD), dedisperse.py's snr
+    double best = -1;
+    size_t best_d = 0;
+    int64_t best_t = 0;
+    for (size_t d = 0; d < D; ++d) {
+        const double* trial = plane.data() + d * static_cast<size_t>(T);
+        write_text_header_dedisperse(std::cout, start_stamp, end_stamp, options.dms[d],
+                                     *std::max_element(delays.begin() + d * N, delays.begin() + (d + 1) * N));
+        write_text_dedisperse(std::cout, trial, T, nb, L, options.step(), actual_samplerate, options.linear);
+        if (T < 1) continue;
+        std::vector<double> v(trial, trial + T);
+        const double med = median_of(v);
+        for (double& x : v) x = std::fabs(x - med);
+        const double scale = 1.4826 * median_of(v);
+        for (int64_t t = 0; t < T; ++t) {
+            const double s = (trial[t] - med) / scale;
+            if (s > best) {
+                best = s;
+                best_d = d;
+                best_t = t;
+            }
+        }
+    }
+    std::cout << std::endl;          // (the blank line that closes a pass)
+    std::cerr << "Dedispersed: " << K << " integrations of " << L << " frames, " << T << " times of " << D << " trials";
+    if (T > 0 && best >= 0)
+        std::cerr << "; strongest sample: DM " << options.dms[best_d] << " (trial " << best_d << ") at "
+                  << static_cast<double>(best_t * L * options.step()) / actual_samplerate << " s, snr " << best;
+    std::cerr << std::endl;
     if (chatty(options)) print_acquisition_summary(options.N, K * L, 0, 0, actual_samplerate);
     return 0;
 }
@@ -672,6 +755,7 @@ int run(int argc, char** argv)
     if (!options.stft_file.empty()) return run_stft(options, aux, actual_samplerate);
     if (!options.correlate_files.empty()) return run_correlate(options, aux, actual_samplerate, source->frequency());
     if (!options.cross_file.empty()) return run_cross(options, aux, actual_samplerate, source->frequency());
+    if (options.dedisperse_frames > 0) return run_dedisperse(options, aux, actual_samplerate, source->frequency());
     if (options.quantile_frames > 0) return run_quantile(options, aux, actual_samplerate, source->frequency());
     if (options.excise_frames > 0) return run_excise(options, aux, actual_samplerate, source->frequency());
     if (options.series_frames > 0) return run_series(options, aux, actual_samplerate, source->frequency());
