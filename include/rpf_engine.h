@@ -43,7 +43,8 @@ extern "C" {
                                rpf_accumulate_device_cross, rpf_accumulate_cross;
                                rpf_stft_device, rpf_stft;
                                rpf_correlate_device, rpf_correlate;
-                               rpf_dedisperse_device, rpf_dedisperse, rpf_dedisperse_times */
+                               rpf_dedisperse_device, rpf_dedisperse, rpf_dedisperse_times;
+                               rpf_fold_device, rpf_dedisperse_fold */
 
 /* Return codes = ReturnValue of /root/reference/src/exceptions.h:25-34. */
 #define RPF_OK 0
@@ -456,6 +457,62 @@ int rpf_dedisperse_device(rpf_engine* e, const int32_t* delays /* host, D x N */
 int rpf_dedisperse(rpf_engine* e, const int32_t* delays, const double* weights, int n_trials, double* out /* host */,
                    int64_t capacity, int64_t* times);
 int64_t rpf_dedisperse_times(const rpf_engine* e, const int32_t* delays, int n_trials);
+
+/* Fold of a plane of time series at trial periods: profiles, hits and moments.  A reader of the D x T plane that
+ * rpf_dedisperse_device writes (or of any D x T doubles).  Everything that computes or checks it refers to this definition.
+ *   Input.  x[s][t]: D = n_series series of T doubles in device memory, pitch T.  steps[p]: P = n_periods unsigned 64-bit
+ *     values on the host.  NB = phase_bins.
+ *   Phase.  The kernel knows no physics: steps[p] is the phase advance per time in units of 2^-64 turn, and
+ *         bin(p, t) = (((uint64(t) steps[p]) mod 2^64) >> 32) NB >> 32                 all in uint64, in [0, NB)
+ *     Any steps[p] is legal; 0 puts every time into bin 0.
+ *   Segments.  The fixed order is RPF_FOLD_SEGMENTS = 16 segments, the same for every T.  G = ceil(T / 16); segment g
+ *     holds the times [min(T, g G), min(T, (g + 1) G)) and may be empty.
+ *   Output.  All sums are IEEE double with no contraction, every sum and every product rounded on its own:
+ *         part[g][s][p][b] = +0.0, then for t of segment g, ascending:   if bin(p, t) == b:  part += x[s][t]
+ *         prof[s][p][b]    = +0.0, then for g = 0 ... 15, ascending:     prof += part[g][s][p][b]
+ *         hits[p][b]       = the number of t < T with bin(p, t) == b                                        (int32)
+ *         mom[s][0], mom[s][1] = the same two-level sums of x[s][t] and of x[s][t] x[s][t] over all t      (no bins)
+ *     No atomics and no cross-lane sums of differently ordered terms: the bits depend on nothing but x, steps, NB and T.
+ *     A NaN at time t reaches exactly the cells prof[s][p][bin(p, t)] of every p, and mom[s].  numpy gives the same bits
+ *     with np.bincount(bins[lo:hi], weights=x[s, lo:hi], minlength=NB) per segment, the segments then added in order
+ *     (fold.reference).
+ *   Period to step, on the host, once in C++ (period_steps of host/datastore.h) and once in Python (fold.period_steps),
+ *     both by exactly this double sequence:
+ *         t_row = (L S) / rate;    pr = period_seconds / t_row           [S the frame step, L frames per row]
+ *         refused unless pr is finite and pr >= 2
+ *         steps = (uint64) ldexp(1.0 / pr, 64)                                 at most 2^63
+ *     (row_period_steps takes pr itself, periods given in rows.)
+ *   Statistic, on the host (fold.chi2 in Python, fold_chi2 of host/datastore.h), the reduced chi-square of a profile
+ *     against a flat one:
+ *         mu_s = mom[s][0] / T;    v_s = mom[s][1] / T - mu_s mu_s
+ *         chi2[s][p] = sum over the b with hits > 0 of hits (prof / hits - mu_s)^2 / v_s / (n_used - 1)
+ *     NaN where fewer than two bins have hits or v_s <= 0.
+ * How (csrc/rpf_fold.hip over csrc/fold_core.h): a wave owns (series, 64 consecutive periods, segment), lane = period;
+ * x[s][t] comes by scalar loads, every lane advances its 64-bit phase by steps[p] per time, and the wave's partial
+ * profiles live in LDS as part[b][lane] (NB x 64 doubles), the sum of a lane's current bin in a register while the bin
+ * stays.  The partials go to engine-owned scratch [g][s][p][b]; a second small launch adds the 16 segments in order.
+ * The scratch is made at the first call and never exceeds 256 MB: where the partials of all series need more, the series
+ * run in groups.  An engine that never folds allocates nothing.
+ * rpf_fold_device uploads steps into engine-owned memory, enqueues on `hip_stream` and returns without synchronising; a
+ * call waits on the host for the launches of the call before it (tables and scratch serve one call at a time).  d_prof
+ * holds `capacity` doubles, of which D P NB are written; d_hits (P NB int32) and d_mom (D x 2 doubles) may be NULL.  It
+ * touches nothing of the engine but its own tables and scratch, and works on any engine: it reads no store.
+ * rpf_dedisperse_fold runs rpf_dedisperse_device into the engine's plane scratch on the engine's stream, folds that plane
+ * where it lies (it never leaves the device), copies prof, hits and mom to the host and synchronises; *times = T of the
+ * dedispersion.  It inherits every refusal of rpf_dedisperse.
+ * With T = 0 both return RPF_OK and write nothing.
+ * RPF_ERR_INVALID_ARGUMENT, before any device work, with the outputs untouched: a NULL e, series, steps or profile
+ * pointer (rpf_dedisperse_fold: or times); D or P outside 1 ... 4096; NB outside 1 ... 128; T < 0 or T >= 2^31;
+ * D P NB > capacity or > 2^24; d_series not 8-byte aligned, d_prof or d_mom not 16-byte aligned; a running acquisition. */
+#define RPF_FOLD_SEGMENTS 16
+int rpf_fold_device(rpf_engine* e, const double* d_series /* device, D x T */, int n_series, int64_t T,
+                    const uint64_t* steps /* host, P */, int n_periods, int phase_bins,
+                    double* d_prof /* device, D x P x NB, 16-byte aligned */, int64_t capacity /* doubles */,
+                    int32_t* d_hits /* device, P x NB, or NULL */, double* d_mom /* device, D x 2, or NULL */, void* hip_stream);
+int rpf_dedisperse_fold(rpf_engine* e, const int32_t* delays, const double* weights, int n_trials,
+                        const uint64_t* steps, int n_periods, int phase_bins,
+                        double* prof /* host */, int64_t capacity, int32_t* hits /* host or NULL */, double* mom /* host or NULL */,
+                        int64_t* times);
 
 /* The two halves of rpf_accumulate_device as separate enqueues, so that a
  * benchmark can bracket the dominant kernel alone with events on `hip_stream`:

@@ -107,6 +107,12 @@ _SYMBOLS = [
     ("rpf_dedisperse", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                       ctypes.POINTER(ctypes.c_double), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_dedisperse_times", ctypes.c_int64, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
+    ("rpf_fold_device", ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int,
+                                       _P, ctypes.c_int64, _P, _P, _P]),
+    ("rpf_dedisperse_fold", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_double), ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
     ("rpf_has_bin_stats", ctypes.c_int, [_P]),
     ("rpf_get_bin_stats", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     ("rpf_accumulate_device_stats", ctypes.c_int, [_P, _P, ctypes.c_size_t, ctypes.c_int64, _P, _P,

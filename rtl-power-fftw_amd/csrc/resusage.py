@@ -33,4 +33,7 @@ for l in sys.stdin:
                 tag = re.search(r'(correlate_\w+?)_kernel', cur).group(1)
             if 'dedisperse_kernel' in cur:
                 tag = 'dedisperse LDS=%s' % m.group(2)
+            f = re.search(r'\d\dfold_(reduce_)?kernel(?:ILb(\d)E)?', cur)
+            if f:
+                tag = 'fold_reduce' if f.group(1) else ('fold series' if f.group(2) == '1' else 'fold hits') + ' (LDS is dynamic)'
             print(tag, {k: d.get(k) for k in ('VGPRs', 'AGPRs', 'ScratchSize', 'Occupancy', 'VGPRs Spill')})

@@ -39,6 +39,7 @@
 #include "cross_core.h"
 #include "correlate_core.h"
 #include "dedisperse_core.h"
+#include "fold_core.h"
 #include "engine_family.h"
 #include "rpf_kernels.h"
 #include "series_pieces.h"
@@ -211,6 +212,15 @@ struct rpf_engine {
     hipEvent_t dd_done = nullptr;         // after the last call's launch: the tables may be overwritten once it has passed
     double* d_dd_out = nullptr;           // rpf_dedisperse: the D x T result on the device
     size_t dd_out = 0;                    // ... doubles it holds
+    // fold of a plane at trial periods (rpf_fold_device, rpf_dedisperse_fold); made at the first call
+    uint64_t* h_fold_steps = nullptr;     // pinned: the steps of one call, as uploaded
+    uint64_t* d_fold_steps = nullptr;     // ... and on the device
+    size_t fold_steps = 0;                // ... values each holds
+    hipEvent_t fold_done = nullptr;       // after the last call's launches: steps and scratch may be overwritten once it has passed
+    uint8_t* d_fold_scratch = nullptr;    // the partials of one group of series (fold_core.h), at most 256 MB
+    size_t fold_scratch_bytes = 0;        // ... bytes it holds
+    uint8_t* d_fold_out = nullptr;        // rpf_dedisperse_fold: prof, mom and hits on the device
+    size_t fold_out_bytes = 0;            // ... bytes it holds
 
     mutable std::string last_error;
 };
@@ -946,6 +956,11 @@ void release_device(rpf_engine* e)
     (void)hipFree(e->d_dd_out);
     if (e->h_dd_tables) (void)hipHostFree(e->h_dd_tables);
     if (e->dd_done) (void)hipEventDestroy(e->dd_done);
+    (void)hipFree(e->d_fold_steps);
+    (void)hipFree(e->d_fold_scratch);
+    (void)hipFree(e->d_fold_out);
+    if (e->h_fold_steps) (void)hipHostFree(e->h_fold_steps);
+    if (e->fold_done) (void)hipEventDestroy(e->fold_done);
     if (e->stft_inner) {
         release_device(e->stft_inner);
         delete e->stft_inner;
@@ -2888,6 +2903,128 @@ int rpf_dedisperse(rpf_engine* e, const int32_t* delays, const double* weights, 
     if ((rc = grow_scratch(e, &e->d_dd_out, &e->dd_out, cells, sizeof(double), s)) != RPF_OK) return rc;
     if ((rc = dedisperse_enqueue(e, delays, weights, n_trials, T, e->d_dd_out, s)) != RPF_OK) return rc;
     HIP_TRY(e, hipMemcpyAsync(out, e->d_dd_out, sizeof(double) * cells, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    *times = T;
+    return RPF_OK;
+}
+
+// ---- fold of a plane at trial periods: rpf_fold_device, rpf_dedisperse_fold (include/rpf_engine.h) ---------------------
+
+// What both entries refuse of the fold's own arguments, before any device work (`e` is not NULL here).
+static int fold_check(rpf_engine* e, const char* who, int D, int64_t T, const uint64_t* steps, int P, int NB, const void* prof,
+                      int64_t capacity)
+{
+    const std::string me = who;
+    if (!steps || !prof) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+    if (D < 1 || D > rpf::kFoldMaxSeries)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": n_series must be in 1 .. " + std::to_string(rpf::kFoldMaxSeries) + ", got " + std::to_string(D));
+    if (P < 1 || P > rpf::kFoldMaxPeriods)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": n_periods must be in 1 .. " + std::to_string(rpf::kFoldMaxPeriods) + ", got " + std::to_string(P));
+    if (NB < 1 || NB > rpf::kFoldMaxBins)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": phase_bins must be in 1 .. " + std::to_string(rpf::kFoldMaxBins) + ", got " + std::to_string(NB));
+    if (T < 0 || T >= (static_cast<int64_t>(1) << 31))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": T must be in 0 .. 2^31 - 1, got " + std::to_string(T));
+    const int64_t cells = static_cast<int64_t>(D) * P * NB;
+    if (cells > capacity || cells > rpf::kFoldMaxCells)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT,
+                    me + ": " + std::to_string(D) + " series x " + std::to_string(P) + " periods x " + std::to_string(NB) +
+                        " phase bins are " + std::to_string(cells) + " cells, the capacity is " + std::to_string(capacity) +
+                        " and a call folds at most " + std::to_string(rpf::kFoldMaxCells));
+    return RPF_OK;
+}
+
+// Uploads the steps into the engine's table and enqueues the launches of every group of series, all on `s`.  The table
+// and the scratch serve one call at a time: the call before this one has passed fold_done by then.
+static int fold_enqueue(rpf_engine* e, const double* d_x, int D, int64_t T, const uint64_t* steps, int P, int NB, double* d_prof,
+                        int32_t* d_hits, double* d_mom, hipStream_t s)
+{
+    if (e->fold_done)
+        HIP_TRY(e, hipEventSynchronize(e->fold_done));
+    else
+        HIP_TRY(e, hipEventCreateWithFlags(&e->fold_done, hipEventDisableTiming));
+    if (static_cast<size_t>(P) > e->fold_steps) {
+        if (e->h_fold_steps) (void)hipHostFree(e->h_fold_steps);
+        (void)hipFree(e->d_fold_steps);
+        e->h_fold_steps = e->d_fold_steps = nullptr;
+        e->fold_steps = 0;
+        HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_fold_steps), sizeof(uint64_t) * P, hipHostMallocDefault));
+        HIP_TRY(e, hipMalloc(&e->d_fold_steps, sizeof(uint64_t) * P));
+        e->fold_steps = static_cast<size_t>(P);
+    }
+    const int per_group = rpf::fold_group_series(D, P, NB);
+    const size_t need = rpf::fold_scratch(per_group, P, NB).bytes;
+    if (need > e->fold_scratch_bytes) {          // (nothing of this engine reads the scratch now: fold_done has passed)
+        (void)hipFree(e->d_fold_scratch);
+        e->d_fold_scratch = nullptr;
+        e->fold_scratch_bytes = 0;
+        HIP_TRY(e, hipMalloc(&e->d_fold_scratch, need));
+        e->fold_scratch_bytes = need;
+    }
+    std::copy(steps, steps + P, e->h_fold_steps);
+    HIP_TRY(e, hipMemcpyAsync(e->d_fold_steps, e->h_fold_steps, sizeof(uint64_t) * P, hipMemcpyHostToDevice, s));
+    hipError_t launched = hipSuccess;
+    const size_t cells = static_cast<size_t>(P) * NB;
+    for (int s0 = 0; s0 < D && launched == hipSuccess; s0 += per_group)
+        launched = rpf::launch_fold(d_x + static_cast<size_t>(s0) * T, std::min(per_group, D - s0), T, e->d_fold_steps, P, NB,
+                                    e->d_fold_scratch, d_prof + s0 * cells, s0 == 0 ? d_hits : nullptr,
+                                    d_mom ? d_mom + 2 * static_cast<size_t>(s0) : nullptr, s);
+    // (recorded whether or not the launches went out: the copy above reads the pinned block until then)
+    HIP_TRY(e, hipEventRecord(e->fold_done, s));
+    HIP_TRY(e, launched);
+    return RPF_OK;
+}
+
+int rpf_fold_device(rpf_engine* e, const double* d_series, int n_series, int64_t T, const uint64_t* steps, int n_periods,
+                    int phase_bins, double* d_prof, int64_t capacity, int32_t* d_hits, double* d_mom, void* hip_stream)
+{
+    const char* who = "rpf_fold_device";
+    if (!e || !d_series) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": acquisition running");
+    const int rc = fold_check(e, who, n_series, T, steps, n_periods, phase_bins, d_prof, capacity);
+    if (rc != RPF_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(d_series) & 7)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_series must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_prof) & 15) || (reinterpret_cast<uintptr_t>(d_mom) & 15))
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_prof and d_mom must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_hits) & 3)
+        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_hits must be 4-byte aligned");
+    if (T == 0) return RPF_OK;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    return fold_enqueue(e, d_series, n_series, T, steps, n_periods, phase_bins, d_prof, d_hits, d_mom,
+                        static_cast<hipStream_t>(hip_stream));
+}
+
+int rpf_dedisperse_fold(rpf_engine* e, const int32_t* delays, const double* weights, int n_trials, const uint64_t* steps,
+                        int n_periods, int phase_bins, double* prof, int64_t capacity, int32_t* hits, double* mom, int64_t* times)
+{
+    const char* who = "rpf_dedisperse_fold";
+    int64_t T = 0;
+    // (the plane goes to engine scratch, grown to fit: its capacity is no refusal of this entry)
+    int rc = dedisperse_check(e, who, delays, weights, n_trials, prof, INT64_MAX, times, &T);
+    if (rc != RPF_OK) return rc;
+    if ((rc = fold_check(e, who, n_trials, T, steps, n_periods, phase_bins, prof, capacity)) != RPF_OK || T == 0) return rc;
+    DeviceScope on_device(e->device);
+    HIP_TRY(e, on_device.status());
+    hipStream_t s = e->compute_stream;
+    const size_t D = static_cast<size_t>(n_trials), cells = static_cast<size_t>(n_periods) * phase_bins;
+    // prof, then mom, then hits: every offset a multiple of 16 bytes
+    const size_t mom_at = sizeof(double) * D * cells, hits_at = mom_at + sizeof(double) * 2 * D;
+    if ((rc = grow_scratch(e, &e->d_dd_out, &e->dd_out, D * static_cast<size_t>(T), sizeof(double), s)) != RPF_OK) return rc;
+    if ((rc = grow_scratch(e, &e->d_fold_out, &e->fold_out_bytes, hits_at + sizeof(int32_t) * cells, 1, s)) != RPF_OK) return rc;
+    if ((rc = dedisperse_enqueue(e, delays, weights, n_trials, T, e->d_dd_out, s)) != RPF_OK) return rc;
+    double* const d_prof = reinterpret_cast<double*>(e->d_fold_out);
+    double* const d_mom = reinterpret_cast<double*>(e->d_fold_out + mom_at);
+    int32_t* const d_hits = reinterpret_cast<int32_t*>(e->d_fold_out + hits_at);
+    if ((rc = fold_enqueue(e, e->d_dd_out, n_trials, T, steps, n_periods, phase_bins, d_prof, hits ? d_hits : nullptr,
+                           mom ? d_mom : nullptr, s)) != RPF_OK)
+        return rc;
+    HIP_TRY(e, hipMemcpyAsync(prof, d_prof, mom_at, hipMemcpyDeviceToHost, s));
+    if (mom) HIP_TRY(e, hipMemcpyAsync(mom, d_mom, sizeof(double) * 2 * D, hipMemcpyDeviceToHost, s));
+    if (hits) HIP_TRY(e, hipMemcpyAsync(hits, d_hits, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     *times = T;
     return RPF_OK;

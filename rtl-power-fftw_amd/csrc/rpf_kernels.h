@@ -259,6 +259,13 @@ hipError_t launch_correlate_finish(const double* d_planes, int M, int N, double*
 hipError_t launch_dedisperse(const double* d_rows, long K, int N, const int32_t* d_delays, const double* d_weights,
                              const void* d_spans, int D, long T, double* d_out, hipStream_t stream);
 
+// ---- fold of a D x T plane at trial periods (rpf_fold.hip, fold_core.h) ------------------------------------------------
+// d_prof[series x P x NB] (and d_hits[P x NB], d_mom[series x 2] where not NULL) = the sums of include/rpf_engine.h
+// (rpf_fold_device) over d_x[series x T] for the steps d_steps[P] on the device.  d_scratch holds
+// fold_scratch(series, P, NB).bytes, at most kFoldScratchBytes.  T < 1 launches nothing.
+hipError_t launch_fold(const double* d_x, int series, long T, const uint64_t* d_steps, int P, int NB, void* d_scratch,
+                       double* d_prof, int32_t* d_hits, double* d_mom, hipStream_t stream);
+
 // Master twiddle table W_N^k = exp(-2 pi i k / N), k in [0,N), evaluated in
 // long double and rounded once to float.
 void make_twiddles(int N, std::vector<cf>& out);

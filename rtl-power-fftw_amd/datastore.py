@@ -511,6 +511,39 @@ class Datastore:
                                              D * T, ctypes.byref(times)))
         return out[:D * times.value].reshape(D, times.value)
 
+    # -- fold of a plane at trial periods (rpf_fold_device, rpf_dedisperse_fold; include/rpf_engine.h has the definition) --
+    @staticmethod
+    def _fold_steps(steps, phase_bins):
+        steps = np.ascontiguousarray(np.atleast_1d(steps), dtype=np.uint64)
+        if steps.ndim != 1:
+            raise RPFError("fold: steps must be a list of 64-bit values; got shape %s." % (steps.shape,), ReturnValue.InvalidArgument)
+        return steps, steps.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(phase_bins)
+
+    def fold_device(self, d_series_ptr, n_series, T, steps, phase_bins, d_prof_ptr, capacity, d_hits_ptr=None, d_mom_ptr=None,
+                    hip_stream=0):
+        """rpf_fold_device: folds the n_series x T device doubles at d_series at the host `steps` (fold.period_steps)
+        into phase_bins bins: d_prof = `capacity` device doubles, n_series x len(steps) x phase_bins written; d_hits
+        (len(steps) x phase_bins int32) and d_mom (n_series x 2 doubles) may be None.  Asynchronous on hip_stream."""
+        steps, sp, NB = self._fold_steps(steps, phase_bins)
+        self._check(self._lib.rpf_fold_device(self._handle, ctypes.c_void_p(d_series_ptr), n_series, T, sp, steps.size, NB,
+                                              ctypes.c_void_p(d_prof_ptr), capacity, ctypes.c_void_p(d_hits_ptr),
+                                              ctypes.c_void_p(d_mom_ptr), ctypes.c_void_p(hip_stream)))
+
+    def dedisperse_fold(self, delays, weights, steps, phase_bins):
+        """rpf_dedisperse_fold: dedisperses the stored rows (as `dedisperse`) and folds the plane on the device at
+        `steps`.  Returns prof (D, P, NB), hits (P, NB) int32, mom (D, 2) and T: fold.reference of that plane."""
+        delays, dp, weights, wp = self._dedisperse_args(delays, weights)
+        steps, sp, NB = self._fold_steps(steps, phase_bins)
+        D, P = delays.shape[0], steps.size
+        prof = np.zeros(max(D * P * NB, 1), dtype=np.float64)
+        hits = np.zeros(max(P * NB, 1), dtype=np.int32)
+        mom = np.zeros((D, 2), dtype=np.float64)
+        times = ctypes.c_int64()
+        self._check(self._lib.rpf_dedisperse_fold(self._handle, dp, wp, D, sp, P, NB, prof.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                  D * P * NB, hits.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                  mom.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(times)))
+        return prof[:D * P * max(NB, 0)].reshape(D, P, NB), hits[:P * NB].reshape(P, NB), mom, times.value
+
     def accumulate_quantiles(self, stream, frames_per_spectrum, q=(0.5,), max_spectra=None):
         """Reset, append, select: the per-bin quantiles q over the integrations of `frames_per_spectrum` frames of a
         host stream.  Returns ((len(q), N) array, K)."""

@@ -325,6 +325,49 @@ void write_text_dedisperse(std::ostream& out, const double* trial, int64_t T, in
     out.flush();
 }
 
+void write_text_fold_plane(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp,
+                           const std::vector<double>& dms, const std::vector<double>& periods, int NB, int64_t T,
+                           const std::vector<double>& chi2)
+{
+    out << "# rtl-power-fftw output" << std::endl;
+    out << "# Acquisition start: " << start_stamp << std::endl;
+    out << "# Acquisition end: " << end_stamp << std::endl;
+    out << "# fold: " << dms.size() << " DMs x " << periods.size() << " periods, " << NB << " phase bins, " << T << " times" << std::endl;
+    out << "#" << std::endl;
+    out << "# DM [pc cm^-3] period [s] reduced chi2" << std::endl;
+    for (size_t d = 0; d < dms.size(); ++d) {
+        for (size_t p = 0; p < periods.size(); ++p)
+            out << std::setprecision(6) << dms[d] << " " << std::setprecision(9) << periods[p] << " " << std::setprecision(6)
+                << chi2[d * periods.size() + p] << std::endl;
+        out << std::endl;
+    }
+    out << std::endl;
+    out.flush();
+}
+
+void write_text_fold_profile(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, double dm,
+                             double period, double chi2, const double* prof, const int32_t* hits, int NB, int64_t nb, bool linear)
+{
+    out << "# rtl-power-fftw output" << std::endl;
+    out << "# Acquisition start: " << start_stamp << std::endl;
+    out << "# Acquisition end: " << end_stamp << std::endl;
+    out << "# DM " << std::setprecision(6) << dm << " pc cm^-3, period " << std::setprecision(9) << period << " s, reduced chi2 "
+        << std::setprecision(6) << chi2 << std::endl;
+    out << "#" << std::endl;
+    out << "# phase [turns] power [median units] hits" << std::endl;
+    for (int b = 0; b < NB; ++b) {
+        const double p = prof[b] / (static_cast<double>(hits[b]) * static_cast<double>(nb));
+        out << std::setprecision(6) << (b + 0.5) / NB << " ";
+        if (hits[b] == 0)
+            out << "nan";
+        else
+            out << (linear ? p : 10 * std::log10(p));
+        out << " " << hits[b] << std::endl;
+    }
+    out << std::endl;
+    out.flush();
+}
+
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,
                          const std::vector<double>* baseline, std::vector<float>& row)
 {

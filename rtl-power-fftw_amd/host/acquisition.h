@@ -145,6 +145,17 @@ void write_text_header_dedisperse(std::ostream& out, const std::string& start_st
                                   int64_t largest_delay);
 void write_text_dedisperse(std::ostream& out, const double* trial, int64_t T, int64_t nb, int64_t L, int64_t step, int samplerate,
                            bool linear);
+// --dedisperse --fold, block 1, the search plane: the usual three header lines, "# fold: <D> DMs x <P> periods, <NB> phase
+// bins, <T> times", "#", the column names, then one line per (DM, period), DM-major with a blank line after every DM: the
+// DM in six digits, the period in nine, chi2[d P + p] in six; a blank line ends the block.
+void write_text_fold_plane(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp,
+                           const std::vector<double>& dms, const std::vector<double>& periods, int NB, int64_t T,
+                           const std::vector<double>& chi2);
+// ... block 2, the profile of one cell: "# DM <dm> pc cm^-3, period <p> s, reduced chi2 <v>", "#", the column names, then
+// one line per phase bin: (b + 0.5) / NB, prof[b] / (hits[b] nb) (nb = the bins of non-zero weight; in dB unless `linear`;
+// nan where hits[b] = 0) and hits[b]; a blank line ends it.
+void write_text_fold_profile(std::ostream& out, const std::string& start_stamp, const std::string& end_stamp, double dm,
+                             double period, double chi2, const double* prof, const int32_t* hits, int NB, int64_t nb, bool linear);
 void spectrum_matrix_row(std::vector<double>& pwr, int N, int64_t repeats_done, int samplerate, bool linear,
                          const std::vector<double>* baseline, std::vector<float>& row);
 // Matrix mode: append one float32 row to options.bin_file and keep the row/column

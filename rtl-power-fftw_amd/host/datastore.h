@@ -169,6 +169,53 @@ inline std::vector<int32_t> dm_delays(const std::vector<double>& dms, double fc,
   return out;
 }
 
+// The steps of rpf_fold_device (include/rpf_engine.h has the sequence; fold.py's row_period_steps and period_steps do the
+// same operations, so the integers agree): the phase advance per row, in units of 2^-64 turn, of periods given in rows ...
+inline std::vector<uint64_t> row_period_steps(const std::vector<double>& periods_rows) {
+  std::vector<uint64_t> out;
+  for (double pr : periods_rows) {
+    if (!std::isfinite(pr) || !(pr >= 2.0))
+      throw RPFexception("period_steps: a period must be finite and at least two rows; got " + std::to_string(pr) + " rows.",
+                         ReturnValue::InvalidArgument);
+    out.push_back(static_cast<uint64_t>(std::ldexp(1.0 / pr, 64)));       // at most 2^63
+  }
+  return out;
+}
+// ... and of periods in seconds, for rows of L frames at step S of a stream at `rate` samples/s.
+inline std::vector<uint64_t> period_steps(const std::vector<double>& periods_s, double rate, int N, int64_t L, int64_t S) {
+  if (N < 1 || L < 1 || S < 1 || !(rate > 0))
+    throw RPFexception("period_steps: N, L, the frame step and the rate must be positive.", ReturnValue::InvalidArgument);
+  const double t_row = (static_cast<double>(L) * static_cast<double>(S)) / rate;
+  std::vector<double> rows;
+  for (double v : periods_s) rows.push_back(v / t_row);
+  return row_period_steps(rows);
+}
+
+// The reduced chi-square of every folded profile against a flat one (include/rpf_engine.h; fold.py's chi2): prof D x P x NB,
+// hits P x NB, mom D x 2, T the times folded; D x P values, NaN where fewer than two bins have hits or the variance is
+// not positive.
+inline std::vector<double> fold_chi2(const std::vector<double>& prof, const std::vector<int32_t>& hits, const std::vector<double>& mom,
+                                     size_t D, size_t P, size_t NB, int64_t T) {
+  std::vector<double> out(D * P, std::nan(""));
+  if (T < 1) return out;
+  for (size_t s = 0; s < D; ++s) {
+    const double mu = mom[2 * s] / static_cast<double>(T), var = mom[2 * s + 1] / static_cast<double>(T) - mu * mu;
+    for (size_t p = 0; p < P; ++p) {
+      int used = 0;
+      double sum = 0;
+      for (size_t b = 0; b < NB; ++b) {
+        const int32_t h = hits[p * NB + b];
+        if (h <= 0) continue;
+        const double dev = prof[(s * P + p) * NB + b] / h - mu;
+        sum += h * dev * dev / var;
+        ++used;
+      }
+      if (used >= 2 && var > 0) out[s * P + p] = sum / (used - 1);
+    }
+  }
+  return out;
+}
+
 // A filled/empty hand-off buffer: what `Buffer&` is in acquisition.cxx:283,302-304
 // (data()/size()/resize()), backed by engine-owned pinned memory.
 class Buffer {
@@ -415,6 +462,22 @@ public:
     check(rpf_dedisperse(engine_, delays.data(), weights.empty() ? nullptr : weights.data(), D, out.data(),
                          static_cast<int64_t>(D) * T, &times));
     out.resize(static_cast<size_t>(D) * static_cast<size_t>(times));
+    return times;
+  }
+  // rpf_dedisperse_fold: the same plane, folded on the device at `steps` (period_steps above) into NB phase bins; prof
+  // (D x P x NB), hits (P x NB) and mom (D x 2) are resized.  Returns T.
+  int64_t dedisperse_fold(const std::vector<int32_t>& delays, const std::vector<double>& weights, const std::vector<uint64_t>& steps,
+                          int NB, std::vector<double>& prof, std::vector<int32_t>& hits, std::vector<double>& mom) {
+    const int D = static_cast<int>(delays.size() / static_cast<size_t>(params.N)), P = static_cast<int>(steps.size());
+    const size_t cells = static_cast<size_t>(P) * static_cast<size_t>(std::max(NB, 0));
+    prof.assign(std::max<size_t>(cells * D, 1), 0.0);
+    hits.assign(std::max<size_t>(cells, 1), 0);
+    mom.assign(2 * static_cast<size_t>(std::max(D, 1)), 0.0);
+    int64_t times = 0;
+    check(rpf_dedisperse_fold(engine_, delays.data(), weights.empty() ? nullptr : weights.data(), D, steps.data(), P, NB,
+                              prof.data(), static_cast<int64_t>(cells * D), hits.data(), mom.data(), &times));
+    prof.resize(cells * D);
+    hits.resize(cells);
     return times;
   }
   // the same into d_out = `capacity` device doubles (rpf_dedisperse_device), asynchronous on hip_stream

@@ -510,6 +510,54 @@ long rpf_host_format_text_dedisperse(const double* trial, long long T, long long
     return copy_out(os.str(), out, cap);
 }
 
+// The --fold options of a parsed command line: the trial periods into periods[cap_periods] and *phase_bins; returns the
+// number of periods (0 without --fold), or -(exit code) with the message in `msg`.
+int rpf_host_parse_fold(int argc, const char* const* argv, double* periods, int cap_periods, long long* phase_bins, char* msg,
+                        size_t cap)
+{
+    return static_cast<int>(or_exit_code(msg, cap, [&]() -> long long {
+        Options o = parse_command_line(argc, argv);
+        *phase_bins = o.phase_bins;
+        int n = 0;
+        for (double v : o.fold_periods)
+            if (n < cap_periods) periods[n++] = v;
+        return n;
+    }));
+}
+
+// datastore.h's period_steps (in_rows = 0: periods in seconds) or row_period_steps (in_rows != 0) into out[n]; 0, or
+// -(exit code) with the message in `msg`.
+int rpf_host_period_steps(const double* periods, int n, int in_rows, double rate, int N, long long L, long long step,
+                          unsigned long long* out, char* msg, size_t cap)
+{
+    return static_cast<int>(or_exit_code(msg, cap, [&]() -> long long {
+        const std::vector<double> v(periods, periods + n);
+        const std::vector<uint64_t> s = in_rows ? row_period_steps(v) : period_steps(v, rate, N, L, step);
+        std::copy(s.begin(), s.end(), out);
+        return 0;
+    }));
+}
+
+// datastore.h's fold_chi2 into out[D x P].
+void rpf_host_fold_chi2(const double* prof, const int* hits, const double* mom, int D, int P, int NB, long long T, double* out)
+{
+    const size_t cells = static_cast<size_t>(P) * NB;
+    const std::vector<double> c = fold_chi2(std::vector<double>(prof, prof + cells * D), std::vector<int32_t>(hits, hits + cells),
+                                            std::vector<double>(mom, mom + 2 * static_cast<size_t>(D)), D, P, NB, T);
+    std::copy(c.begin(), c.end(), out);
+}
+
+// The two --fold blocks (write_text_fold_plane, then write_text_fold_profile of cell (d, p)).
+long rpf_host_format_text_fold(const double* dms, int D, const double* periods, int P, int NB, long long T, const double* chi2,
+                               int d, int p, const double* prof, const int* hits, long long nb, int linear, char* out, size_t cap)
+{
+    std::ostringstream os;
+    const std::vector<double> c(chi2, chi2 + static_cast<size_t>(D) * P);
+    write_text_fold_plane(os, "a", "b", std::vector<double>(dms, dms + D), std::vector<double>(periods, periods + P), NB, T, c);
+    write_text_fold_profile(os, "a", "b", dms[d], periods[p], c[static_cast<size_t>(d) * P + p], prof, hits, NB, nb, linear != 0);
+    return copy_out(os.str(), out, cap);
+}
+
 void rpf_host_synthetic(unsigned long long seed, unsigned long long first, unsigned long long n, unsigned char* out)
 {
     SyntheticSource::generate(seed, first, n, out);

@@ -109,6 +109,11 @@ const Spec kSpecs[] = {
     // --series-stats, --excise, --quantile, --cross, --stft, --correlate, --pfb or several --gpus).
     {0, "dedisperse", Kind::Int64, "frames", nullptr},
     {0, "dm", Kind::Text, "lo:hi:step | value", nullptr},
+    // With --dedisperse: fold every trial of the DM-time plane at the periods of --fold (seconds; one value, or lo:hi:step;
+    // at most 4096) into --phase-bins phase bins (1 ... 128, default 16): one block of reduced chi-square per (DM, period)
+    // and the profile of the strongest cell, in place of the blocks of time and power.
+    {0, "fold", Kind::Text, "lo:hi:step | period", nullptr},
+    {0, "phase-bins", Kind::Int64, "n", nullptr},
     {0, "reduce", Kind::Text, "rccl|host", "With --gpus: where a scan's per-device spectra are added (default: rccl if it loads, else host)."},
     {'h', "help", Kind::Flag, "", "Displays usage information and exits."},
     {0, "version", Kind::Flag, "", "Displays version information and exits."},
@@ -257,9 +262,9 @@ static_assert(rows_end(0), "a row of kReplayModes refuses more than kMaxRefused 
     throw RPFexception("Option --" + mode + " " + what + " Exiting.", ReturnValue::InvalidArgument);
 }
 
-// --dm <value> or <lo:hi:step>: the trials lo + i step for i = 0 ... floor((hi - lo) / step + 1e-9), at most 4096 of them,
-// none negative.
-std::vector<double> parse_dm_list(const std::string& text)
+// <value> or <lo:hi:step> of --dm and --fold: the trials lo + i step for i = 0 ... floor((hi - lo) / step + 1e-9), at most
+// 4096 of them, none negative.  `option` and `expecting` go into the refusal.
+std::vector<double> parse_trial_list(const std::string& text, const char* option, const char* expecting)
 {
     std::vector<double> part;
     size_t pos = 0;
@@ -277,14 +282,16 @@ std::vector<double> parse_dm_list(const std::string& text)
     }
     good = good && (part.size() == 1 || (part.size() == 3 && part[1] >= part[0] && part[2] > 0.0));
     if (!good)
-        refuse("dedisperse", "could not use the value given to --dm: " + text +
-                                 ". Expecting one dispersion measure or lo:hi:step, none negative, hi >= lo and step > 0.");
+        refuse("dedisperse", std::string("could not use the value given to --") + option + ": " + text + ". Expecting " + expecting +
+                                 " or lo:hi:step, none negative, hi >= lo and step > 0.");
     if (part.size() == 1) return part;
     const double count = std::floor((part[1] - part[0]) / part[2] + 1e-9) + 1.0;
-    if (count > 4096.0) refuse("dedisperse", "takes at most 4096 trials in --dm, got " + std::to_string(static_cast<long long>(std::min(count, 1e18))) + ".");
-    std::vector<double> dms;
-    for (int i = 0; i < static_cast<int>(count); ++i) dms.push_back(part[0] + i * part[2]);
-    return dms;
+    if (count > 4096.0)
+        refuse("dedisperse", std::string("takes at most 4096 trials in --") + option + ", got " +
+                                 std::to_string(static_cast<long long>(std::min(count, 1e18))) + ".");
+    std::vector<double> trials;
+    for (int i = 0; i < static_cast<int>(count); ++i) trials.push_back(part[0] + i * part[2]);
+    return trials;
 }
 
 // False when the command line does not name the mode; else takes its frame count, throws the first of the row's
@@ -586,10 +593,26 @@ Options parse_command_line(int argc, const char* const* argv)
     if (p.has("dm") && !p.has("dedisperse"))
         throw RPFexception("Option --dm needs --dedisperse: it lists the dispersion measures that one tries. Exiting.",
                            ReturnValue::InvalidArgument);
+    for (const char* name : {"fold", "phase-bins"})
+        if (p.has(name) && !p.has("dedisperse"))
+            throw RPFexception(std::string("Option --") + name + " needs --dedisperse: it folds the DM-time plane that one builds. Exiting.",
+                               ReturnValue::InvalidArgument);
     if (replay_mode("dedisperse", p, o)) {
         if (o.baseline) refuse("dedisperse", "does not combine with --baseline (-B): the power is in units of every bin's median.");
         if (!p.has("dm")) refuse("dedisperse", "needs --dm: the dispersion measures to try, one value or lo:hi:step.");
-        o.dms = parse_dm_list(p.get("dm"));
+        o.dms = parse_trial_list(p.get("dm"), "dm", "one dispersion measure");
+        if (p.has("fold")) {
+            o.fold_periods = parse_trial_list(p.get("fold"), "fold", "one period in seconds");
+            o.phase_bins = p.has("phase-bins") ? to_number<int64_t>(*find_spec("--phase-bins"), p.get("phase-bins")) : 16;
+            if (o.phase_bins < 1 || o.phase_bins > 128)
+                refuse("dedisperse", "takes 1 to 128 phase bins in --phase-bins, got " + std::to_string(o.phase_bins) + ".");
+            const long long cells = static_cast<long long>(o.dms.size()) * static_cast<long long>(o.fold_periods.size()) * o.phase_bins;
+            if (cells > (1LL << 24))
+                refuse("dedisperse", "folds at most 16777216 cells (DMs x periods x phase bins) in one run, got " + std::to_string(cells) + ".");
+        } else if (p.has("phase-bins")) {
+            throw RPFexception("Option --phase-bins needs --fold: it is the number of phase bins of the folded profiles. Exiting.",
+                               ReturnValue::InvalidArgument);
+        }
     }
     if (p.has("input")) o.input_file = p.get("input");
     o.synthetic = p.has("synthetic");

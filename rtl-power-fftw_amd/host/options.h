@@ -63,6 +63,8 @@ struct Options : Params {
     std::vector<std::string> correlate_files;   // --correlate b,c,...: streams 1 .. M-1 of the correlator with --input (empty = off)
     int64_t dedisperse_frames = 0;   // --dedisperse <frames>: the DM-time plane of the replay's integrations of <frames> frames (0 = off)
     std::vector<double> dms;         // --dm lo:hi:step | value: its trial dispersion measures [pc cm^-3], at most 4096
+    std::vector<double> fold_periods;   // --fold lo:hi:step | period: fold that plane at these periods [s], at most 4096 (empty = off)
+    int64_t phase_bins = 16;         // --phase-bins <n>: the phase bins of the folded profiles, 1 ... 128
     std::string stft_file;           // --stft <file>: where the frames' complex spectra of --input go, raw float32 pairs ("" = off)
     // (--pfb <taps> sets Params::pfb_taps; the coefficients are the default prototype)
     bool show_help = false, show_version = false;

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <ctime>
 #include <fstream>
+#include <iomanip>
 #include <iostream>
 #include <memory>
 #include <mutex>
@@ -537,10 +538,26 @@ static double median_of(std::vector<double>& v)
 // every bin's median, the weights are w[b] = 1 / median[b] (0 for the DC bin and for a bin whose median is 0), and ONE
 // rpf_dedisperse adds the bins along every trial's delay curve (dm_delays).  One block per trial: time and the mean of the
 // summed bins in units of their medians.
+// With --fold <period | lo:hi:step> [--phase-bins <n>], ONE rpf_dedisperse_fold takes the place of that rpf_dedisperse: the
+// plane stays on the device and is folded there at every trial period (period_steps); fold_chi2 then gives the search
+// plane, block 1, and the strongest cell's profile is block 2.
 int run_dedisperse(const Options& options, AuxData& aux, int actual_samplerate, int64_t tuned_freq)
 {
-    Datastore data(options, aux.window_values);
     const int64_t L = options.dedisperse_frames;
+    const bool folding = !options.fold_periods.empty();
+    std::vector<uint64_t> steps;
+    if (folding) {
+        const double t_row = (static_cast<double>(L) * static_cast<double>(options.step())) / static_cast<double>(actual_samplerate);
+        for (double period : options.fold_periods)
+            if (!(period / t_row >= 2.0)) {
+                std::ostringstream why;
+                why << std::setprecision(9) << "Option --dedisperse: the period " << period << " s of --fold is under two integrations of "
+                    << L << " frames (" << t_row << " s each): the shortest period that works is " << 2.0 * t_row << " s. Exiting.";
+                throw RPFexception(why.str(), ReturnValue::InvalidArgument);
+            }
+        steps = period_steps(options.fold_periods, static_cast<double>(actual_samplerate), options.N, L, options.step());
+    }
+    Datastore data(options, aux.window_values);
     const size_t N = static_cast<size_t>(options.N), D = options.dms.size();
     const std::vector<int32_t> delays = dm_delays(options.dms, static_cast<double>(tuned_freq), static_cast<double>(actual_samplerate),
                                                   options.N, L, options.step());
@@ -566,6 +583,31 @@ int run_dedisperse(const Options& options, AuxData& aux, int actual_samplerate, 
     if (nb == 0)
         throw RPFexception("Option --dedisperse: every bin but DC has a median of 0, so no bin is left to add. Exiting.",
                            ReturnValue::InvalidInput);
+    if (folding) {
+        const size_t P = steps.size(), NB = static_cast<size_t>(options.phase_bins);
+        std::vector<double> prof, mom;
+        std::vector<int32_t> hits;
+        const int64_t T = data.dedisperse_fold(delays, weights, steps, options.phase_bins, prof, hits, mom);
+        const std::string end_stamp = Acquisition::utc_now();
+        const std::vector<double> chi2 = fold_chi2(prof, hits, mom, D, P, NB, T);
+        size_t best = chi2.size();          // the strongest cell: the first of the largest values that are not NaN
+        for (size_t i = 0; i < chi2.size(); ++i)
+            if (!std::isnan(chi2[i]) && (best == chi2.size() || chi2[i] > chi2[best])) best = i;
+        write_text_fold_plane(std::cout, start_stamp, end_stamp, options.dms, options.fold_periods, options.phase_bins, T, chi2);
+        std::cerr << "Folded: " << K << " integrations of " << L << " frames, " << T << " times of " << D << " trials at " << P
+                  << " periods";
+        if (best < chi2.size()) {
+            const size_t d = best / P, p = best % P;
+            write_text_fold_profile(std::cout, start_stamp, end_stamp, options.dms[d], options.fold_periods[p], chi2[best],
+                                    prof.data() + best * NB, hits.data() + p * NB, options.phase_bins, nb, options.linear);
+            std::cerr << "; strongest cell: DM " << options.dms[d] << " (trial " << d << "), period " << std::setprecision(9)
+                      << options.fold_periods[p] << std::setprecision(6) << " s (trial " << p << "), reduced chi2 " << chi2[best];
+        }
+        std::cout << std::endl;          // (the blank line that closes a pass)
+        std::cerr << std::endl;
+        if (chatty(options)) print_acquisition_summary(options.N, K * L, 0, 0, actual_samplerate);
+        return 0;
+    }
     const int64_t T = data.dedisperse(delays, weights, plane);
     const std::string end_stamp = Acquisition::utc_now();
     // the strongest sample in robust sigmas of its own trial: (x - median) / (1.4826 MAD), dedisperse.py's snr
