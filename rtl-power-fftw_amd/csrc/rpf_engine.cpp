@@ -71,6 +71,21 @@ struct StagingSlot {
     unsigned* verdict = nullptr;    // pinned host word the launch's verdict kernel sets to 1 if it gave up
 };
 
+// A pinned host block and its twin on the device, for a table the host writes anew for every call and uploads on the
+// call's stream.  The pair serves one call at a time: reserve() waits until the call before has passed `done`, which
+// record() puts behind the launches that read the table.
+struct UploadTable {
+    uint8_t* host = nullptr;
+    uint8_t* device = nullptr;
+    size_t bytes = 0;             // ... each holds
+    hipEvent_t done = nullptr;
+
+    int reserve(rpf_engine* e, size_t need);
+    int record(rpf_engine* e, hipStream_t s);
+    void release_blocks();        // the two blocks
+    void release();               // ... and the event
+};
+
 }  // namespace
 
 struct rpf_engine {
@@ -161,6 +176,7 @@ struct rpf_engine {
     int series_launches = 0;              // transform-kernel launches of the last series call
     uint8_t* d_series_in = nullptr;       // rpf_accumulate_series: one piece of the host stream ...
     size_t series_in_bytes = 0;
+    size_t series_in_stride = 0;          // ... bytes from one stream's piece to the next (the entries of several streams)
     double* d_series_out = nullptr;       // ... and its rows (N doubles each; a stats engine's 3 N)
     size_t series_out_rows = 0;
     // excised average (rpf_accumulate[_device]_excised): a piece's rows go to d_series_out, and
@@ -206,17 +222,11 @@ struct rpf_engine {
     double* d_corr_planes = nullptr;      // the M^2 running planes, then the host entry's result: 3 M^2 N doubles
     size_t corr_planes = 0;               // ... doubles it holds
     // incoherent dedispersion of the stored integrations (rpf_dedisperse_device, rpf_dedisperse); made at the first call
-    uint8_t* h_dd_tables = nullptr;       // pinned: the weights, the spans and the delay table of one call, as uploaded
-    uint8_t* d_dd_tables = nullptr;       // ... and on the device
-    size_t dd_tables_bytes = 0;           // ... bytes each holds
-    hipEvent_t dd_done = nullptr;         // after the last call's launch: the tables may be overwritten once it has passed
+    UploadTable dd_tables;                // the weights, the spans and the delay table of one call, as uploaded
     double* d_dd_out = nullptr;           // rpf_dedisperse: the D x T result on the device
     size_t dd_out = 0;                    // ... doubles it holds
     // fold of a plane at trial periods (rpf_fold_device, rpf_dedisperse_fold); made at the first call
-    uint64_t* h_fold_steps = nullptr;     // pinned: the steps of one call, as uploaded
-    uint64_t* d_fold_steps = nullptr;     // ... and on the device
-    size_t fold_steps = 0;                // ... values each holds
-    hipEvent_t fold_done = nullptr;       // after the last call's launches: steps and scratch may be overwritten once it has passed
+    UploadTable fold_steps;               // the steps of one call, as uploaded; its `done` also guards the scratch
     uint8_t* d_fold_scratch = nullptr;    // the partials of one group of series (fold_core.h), at most 256 MB
     size_t fold_scratch_bytes = 0;        // ... bytes it holds
     uint8_t* d_fold_out = nullptr;        // rpf_dedisperse_fold: prof, mom and hits on the device
@@ -251,6 +261,60 @@ int fail(rpf_engine* e, int rc, const std::string& msg)
     if (e) e->last_error = msg;
     g_last_error = msg;
     return rc;
+}
+
+// ---- the refusals the entries share, each worded once.  All but refuse() test their condition first and return RPF_OK
+// where it does not hold: the text is built only for a call that is refused. ----
+
+int refuse(rpf_engine* e, const char* who, const std::string& text)
+{
+    return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": " + text);
+}
+
+int refuse_if_running(rpf_engine* e, const char* who)
+{
+    return e->worker_running ? refuse(e, who, "acquisition running") : RPF_OK;
+}
+
+int refuse_negative_repeats(rpf_engine* e, int64_t repeats)
+{
+    return repeats < 0 ? fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.") : RPF_OK;
+}
+
+// subject: "d_stream", "d_a and d_b", "every stream", "streams" -- as the entry's own message has always had it
+int refuse_unaligned_stream(rpf_engine* e, const char* who, const char* subject, const void* ptr)
+{
+    if (!(reinterpret_cast<uintptr_t>(ptr) & (e->sample_bytes - 1))) return RPF_OK;
+    return refuse(e, who, std::string(subject) + " must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
+}
+
+int refuse_unaligned_out(rpf_engine* e, const char* who, const char* name, const void* ptr)
+{
+    return (reinterpret_cast<uintptr_t>(ptr) & 15) ? refuse(e, who, std::string(name) + " must be 16-byte aligned") : RPF_OK;
+}
+
+int refuse_ragged_bytes(rpf_engine* e, const char* who, size_t nbytes)
+{
+    if (nbytes % e->sample_bytes == 0) return RPF_OK;
+    return refuse(e, who, "nbytes must be a multiple of the sample size (" + std::to_string(e->sample_bytes) + " bytes)");
+}
+
+int refuse_not_power_of_two(rpf_engine* e, const char* who)
+{
+    if (!(e->N & (e->N - 1))) return RPF_OK;
+    return refuse(e, who, "the number of bins must be a power of two (Bluestein's spectrum lacks its final chirp); got " +
+                              std::to_string(e->N));
+}
+
+// the cross, STFT and correlator entries: built on the plain power path and the cf32 / catch-all engines
+int refuse_stats_engine(rpf_engine* e, const char* who)
+{
+    return e->stats ? refuse(e, who, "not on an engine created with RPF_FLAG_BIN_STATS") : RPF_OK;
+}
+
+int refuse_variant(rpf_engine* e, const char* who)
+{
+    return e->variant != 0 ? refuse(e, who, "not with a kernel variant other than 0") : RPF_OK;
 }
 
 // Frame f of a stream is bytes [bfS, bfS + b span), b bytes per sample; span: N samples, or T N on a PFB engine (whose
@@ -316,23 +380,72 @@ int grow_scratch(rpf_engine* e, T** d_ptr, size_t* have, size_t need, size_t uni
     return RPF_OK;
 }
 
-// The series family's host loop: the K integrations of `stream` in the pieces of series_pieces.h through d_series_in.
+int UploadTable::reserve(rpf_engine* e, size_t need)
+{
+    if (done)
+        HIP_TRY(e, hipEventSynchronize(done));
+    else
+        HIP_TRY(e, hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    if (need <= bytes) return RPF_OK;
+    release_blocks();
+    HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&host), need, hipHostMallocDefault));
+    HIP_TRY(e, hipMalloc(&device, need));
+    bytes = need;
+    return RPF_OK;
+}
+
+int UploadTable::record(rpf_engine* e, hipStream_t s)
+{
+    HIP_TRY(e, hipEventRecord(done, s));
+    return RPF_OK;
+}
+
+void UploadTable::release_blocks()
+{
+    if (host) (void)hipHostFree(host);
+    (void)hipFree(device);
+    host = device = nullptr;
+    bytes = 0;
+}
+
+void UploadTable::release()
+{
+    release_blocks();
+    if (done) (void)hipEventDestroy(done);
+    done = nullptr;
+}
+
+// The last lines of a host entry: the result to the caller's memory, then the one synchronise the caller waits for.
+int copy_back(rpf_engine* e, void* dst, const void* d_src, size_t bytes, hipStream_t s)
+{
+    HIP_TRY(e, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return RPF_OK;
+}
+
+// The host loop of the entries that take their streams from host memory: the K integrations (of L frames) of each of
+// the M `streams` in the pieces of series_pieces.h through d_series_in, stream m's piece at d_series_in + m stride.
+// The stride (e->series_in_stride, for the body) is the piece's bytes, rounded up to 256 where M > 1.
 // prepare(per_piece) makes room for what a piece leaves; body(k0, kc, s) enqueues integrations [k0, k0 + kc) and at most
-// one copy back.  A piece is ONE copy in from the caller's pointer (a registered stream from where it lies), the body
-// and ONE synchronise; a failed body's rc is looked at first, then the stream is synchronised and the rc returns.
+// one copy back.  A piece is ONE copy in per stream from the caller's pointer (a registered stream from where it lies),
+// stream by stream, then the body and ONE synchronise; a failed body's rc is looked at first, then the stream is
+// synchronised and the rc returns.
 // *landed: the integrations whose synchronise succeeded, which comes after the body, so a body cannot count them.
 template <class Prepare, class Body>
-int series_host_pieces(rpf_engine* e, const uint8_t* stream, int64_t L, int64_t K, int64_t row_cap, Prepare prepare,
-                              Body body, int64_t* landed = nullptr)
+int series_host_pieces(rpf_engine* e, const uint8_t* const* streams, int M, int64_t L, int64_t K, int64_t row_cap,
+                       Prepare prepare, Body body, int64_t* landed = nullptr)
 {
     hipStream_t s = e->compute_stream;
     const rpf::SeriesPieces p = rpf::series_pieces(frame_bytes(e), L, K, rpf::kSeriesPieceBytes, row_cap);
-    int rc = grow_scratch(e, &e->d_series_in, &e->series_in_bytes, p.bytes, 1, s);
+    const size_t stride = M > 1 ? (p.bytes + 255) / 256 * 256 : p.bytes;
+    e->series_in_stride = stride;
+    int rc = grow_scratch(e, &e->d_series_in, &e->series_in_bytes, static_cast<size_t>(M) * stride, 1, s);
     if (rc != RPF_OK || (rc = prepare(p.per_piece)) != RPF_OK) return rc;
     for (int64_t k0 = 0; k0 < K; k0 += p.per_piece) {
         const int64_t kc = std::min(p.per_piece, K - k0);
-        HIP_TRY(e, hipMemcpyAsync(e->d_series_in, stream + static_cast<size_t>(k0) * p.hop, frame_span(e, kc * L),
-                                  hipMemcpyHostToDevice, s));
+        for (int m = 0; m < M; ++m)
+            HIP_TRY(e, hipMemcpyAsync(e->d_series_in + static_cast<size_t>(m) * stride, streams[m] + static_cast<size_t>(k0) * p.hop,
+                                      frame_span(e, kc * L), hipMemcpyHostToDevice, s));
         if ((rc = body(k0, kc, s)) != RPF_OK) {
             (void)hipStreamSynchronize(s);
             return rc;
@@ -928,44 +1041,35 @@ void worker_main(rpf_engine* e)
 #undef WORKER_TRY
 }
 
+void release_device(rpf_engine* e);
+
+// An engine this one made for itself (create_inner); `self`: the cross entries of a cf32 engine use the engine itself.
+void destroy_inner(rpf_engine** slot, const rpf_engine* self)
+{
+    if (*slot && *slot != self) {
+        release_device(*slot);
+        delete *slot;
+    }
+    *slot = nullptr;
+}
+
 void release_device(rpf_engine* e)
 {
-    // every device block the engine owns (hipFree of a null pointer does nothing)
+    // every device block the engine owns (hipFree of a null pointer does nothing; d_fused_words is h_fused_words as the
+    // device addresses it)
     void* const blocks[] = {e->d_twiddles, e->d_tw_sub, e->d_tw_sub2, e->d_scratch, e->d_fused_ctl, e->d_fused_scratch,
                             e->d_step2, e->d_gather, e->d_chirp, e->d_bhat, e->d_window, e->d_partial,
                             e->d_series_partial, e->d_series_in, e->d_series_out, e->d_excise_state, e->d_excise_mask,
                             e->d_quantile_rows, e->d_quantile_work, e->d_quantile_out, e->d_pfb_coeffs, e->d_pfb_z,
-                            e->d_cross_uv, e->d_cross_planes, e->d_pwr};
+                            e->d_cross_uv, e->d_cross_planes, e->d_stft_rows, e->d_corr_rows, e->d_corr_partial,
+                            e->d_corr_planes, e->d_dd_out, e->d_fold_scratch, e->d_fold_out, e->d_pwr};
     for (void* p : blocks) (void)hipFree(p);
     if (e->h_fused_words) (void)hipHostFree(e->h_fused_words);
-    if (e->inner) {
-        release_device(e->inner);
-        delete e->inner;
-        e->inner = nullptr;
-    }
-    if (e->cross_inner && e->cross_inner != e) {
-        release_device(e->cross_inner);
-        delete e->cross_inner;
-    }
-    e->cross_inner = nullptr;
-    (void)hipFree(e->d_stft_rows);
-    (void)hipFree(e->d_corr_rows);
-    (void)hipFree(e->d_corr_partial);
-    (void)hipFree(e->d_corr_planes);
-    (void)hipFree(e->d_dd_tables);
-    (void)hipFree(e->d_dd_out);
-    if (e->h_dd_tables) (void)hipHostFree(e->h_dd_tables);
-    if (e->dd_done) (void)hipEventDestroy(e->dd_done);
-    (void)hipFree(e->d_fold_steps);
-    (void)hipFree(e->d_fold_scratch);
-    (void)hipFree(e->d_fold_out);
-    if (e->h_fold_steps) (void)hipHostFree(e->h_fold_steps);
-    if (e->fold_done) (void)hipEventDestroy(e->fold_done);
-    if (e->stft_inner) {
-        release_device(e->stft_inner);
-        delete e->stft_inner;
-        e->stft_inner = nullptr;
-    }
+    e->dd_tables.release();
+    e->fold_steps.release();
+    destroy_inner(&e->inner, e);
+    destroy_inner(&e->cross_inner, e);
+    destroy_inner(&e->stft_inner, e);
     for (auto& s : e->staging) {
         if (s.base) (void)hipFree(s.base);
         if (s.kernel_done) (void)hipEventDestroy(s.kernel_done);
@@ -1350,21 +1454,33 @@ int create_queues(rpf_engine* e, bool inner_of_pfb)
 
 int create_engine(const rpf_config* cfg, const PfbSpec* pfb, bool inner_of_pfb, rpf_engine** out);
 
-// A PFB engine's coefficients and its transform: a rectangular cf32 engine of the same N, device and staging flag,
-// with one minimal buffer.
-int create_pfb(rpf_engine* e, const rpf_config* cfg, const PfbSpec* pfb)
+// An engine of this one's N and device that serves it from the inside (a PFB engine's transform, the cross entries'
+// cf32 engine, the STFT's catch-all engine): never fed through its queues, so it has one minimal buffer.  A creation
+// that fails has said why in g_last_error; that becomes this engine's message too.
+int create_inner(rpf_engine* e, uint32_t flags, const float* window, int frame_step, rpf_engine** slot)
 {
-    if (int rc = upload(e, &e->d_pfb_coeffs, pfb->coeffs, static_cast<size_t>(e->taps) * static_cast<size_t>(e->N))) return rc;
     rpf_config icfg;
     icfg.struct_size = sizeof(icfg);
     icfg.N = e->N;
-    icfg.window = nullptr;
+    icfg.window = window;
     icfg.n_buffers = 1;
     icfg.buffer_capacity = 8;
     icfg.device = e->device;
-    icfg.flags = (cfg->flags & (RPF_FLAG_NO_LDS_DMA | RPF_FLAG_CATCH_ALL)) | RPF_FLAG_SAMPLE_FORMAT(RPF_FORMAT_CF32);
-    icfg.frame_step = 0;
-    return create_engine(&icfg, nullptr, /*inner_of_pfb=*/true, &e->inner);
+    icfg.flags = flags;
+    icfg.frame_step = frame_step;
+    const int rc = create_engine(&icfg, nullptr, /*inner_of_pfb=*/true, slot);
+    return rc == RPF_OK ? rc : fail(e, rc, g_last_error);
+}
+
+// The window an inner engine is created from: this engine's, as it was given.
+const float* window_as_given(const rpf_engine* e) { return e->window.empty() ? nullptr : e->window.data(); }
+
+// A PFB engine's coefficients and its transform: a rectangular cf32 engine of the same N, device and staging flag.
+int create_pfb(rpf_engine* e, const rpf_config* cfg, const PfbSpec* pfb)
+{
+    if (int rc = upload(e, &e->d_pfb_coeffs, pfb->coeffs, static_cast<size_t>(e->taps) * static_cast<size_t>(e->N))) return rc;
+    return create_inner(e, (cfg->flags & (RPF_FLAG_NO_LDS_DMA | RPF_FLAG_CATCH_ALL)) | RPF_FLAG_SAMPLE_FORMAT(RPF_FORMAT_CF32),
+                        nullptr, 0, &e->inner);
 }
 
 // Everything a new engine owns on its device, step by step; the first step that fails has said why and ends it.
@@ -1683,16 +1799,13 @@ int rpf_accumulate(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t 
 static int accumulate_device(rpf_engine* e, const char* who, bool want_stats, const void* d_stream, size_t nbytes,
                              int64_t repeats, double* d_out, void* hip_stream, int64_t* repeats_done)
 {
-    const std::string me = who, out_name = want_stats ? "d_out" : "d_pwr_out";
-    if (!e || !d_out || (!d_stream && nbytes)) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
-    if (want_stats && !e->stats)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": the engine was created without RPF_FLAG_BIN_STATS");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": acquisition running");
-    if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
-    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": " + out_name + " must be 16-byte aligned");
+    if (!e || !d_out || (!d_stream && nbytes)) return refuse(e, who, "NULL argument");
+    if (want_stats && !e->stats) return refuse(e, who, "the engine was created without RPF_FLAG_BIN_STATS");
+    int rc = refuse_if_running(e, who);
+    if (rc == RPF_OK) rc = refuse_negative_repeats(e, repeats);
+    if (rc == RPF_OK) rc = refuse_unaligned_stream(e, who, "d_stream", d_stream);
+    if (rc == RPF_OK) rc = refuse_unaligned_out(e, who, want_stats ? "d_out" : "d_pwr_out", d_out);
+    if (rc != RPF_OK) return rc;
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the HIP null stream
@@ -1724,18 +1837,14 @@ int rpf_accumulate_device_stats(rpf_engine* e, const void* d_stream, size_t nbyt
 static int cross_check(rpf_engine* e, const char* who, const void* a, const void* b, size_t nbytes, int64_t repeats,
                        const void* out)
 {
-    const std::string me = who;
-    if (!e || !out || ((!a || !b) && nbytes)) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
-    if (e->stats)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not on an engine created with RPF_FLAG_BIN_STATS");
-    if (e->taps) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not on a PFB engine");
-    if (e->variant != 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not with a kernel variant other than 0");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": acquisition running");
-    if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
-    if (nbytes % e->sample_bytes)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": nbytes must be a multiple of the sample size (" + std::to_string(e->sample_bytes) + " bytes)");
-    return RPF_OK;
+    if (!e || !out || ((!a || !b) && nbytes)) return refuse(e, who, "NULL argument");
+    int rc = refuse_stats_engine(e, who);
+    if (rc == RPF_OK && e->taps) rc = refuse(e, who, "not on a PFB engine");
+    if (rc == RPF_OK) rc = refuse_variant(e, who);
+    if (rc == RPF_OK) rc = refuse_if_running(e, who);
+    if (rc == RPF_OK) rc = refuse_negative_repeats(e, repeats);
+    if (rc == RPF_OK) rc = refuse_ragged_bytes(e, who, nbytes);
+    return rc;
 }
 
 // The cf32 engine (a cf32 engine: itself) and the scratch of the cross entries, made at the first call.
@@ -1745,17 +1854,8 @@ static int ensure_cross(rpf_engine* e)
         if (e->format == RPF_FORMAT_CF32) {
             e->cross_inner = e;
         } else {
-            rpf_config icfg;
-            icfg.struct_size = sizeof(icfg);
-            icfg.N = e->N;
-            icfg.window = e->window.empty() ? nullptr : e->window.data();
-            icfg.n_buffers = 1;
-            icfg.buffer_capacity = 8;
-            icfg.device = e->device;
-            icfg.flags = (e->flags & ~RPF_FLAG_SAMPLE_FORMAT(0xf)) | RPF_FLAG_SAMPLE_FORMAT(RPF_FORMAT_CF32);
-            icfg.frame_step = e->step;
-            const int rc = create_engine(&icfg, nullptr, /*inner_of_pfb=*/true, &e->cross_inner);
-            if (rc != RPF_OK) return fail(e, rc, g_last_error);
+            const uint32_t flags = (e->flags & ~RPF_FLAG_SAMPLE_FORMAT(0xf)) | RPF_FLAG_SAMPLE_FORMAT(RPF_FORMAT_CF32);
+            if (int rc = create_inner(e, flags, window_as_given(e), e->step, &e->cross_inner)) return rc;
         }
     }
     const size_t N = static_cast<size_t>(e->N), S = static_cast<size_t>(e->step);
@@ -1802,12 +1902,12 @@ static int cross_enqueue(rpf_engine* e, const uint8_t* d_a, const uint8_t* d_b, 
 int rpf_accumulate_device_cross(rpf_engine* e, const void* d_a, const void* d_b, size_t nbytes, int64_t repeats, double* d_out,
                                 void* hip_stream, int64_t* repeats_done)
 {
-    const std::string me = "rpf_accumulate_device_cross";
-    int rc = cross_check(e, me.c_str(), d_a, d_b, nbytes, repeats, d_out);
+    const char* who = "rpf_accumulate_device_cross";
+    int rc = cross_check(e, who, d_a, d_b, nbytes, repeats, d_out);
+    if (rc == RPF_OK) rc = refuse_unaligned_stream(e, who, "d_a and d_b",
+                                                     reinterpret_cast<const void*>(reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)));
+    if (rc == RPF_OK) rc = refuse_unaligned_out(e, who, "d_out", d_out);
     if (rc != RPF_OK) return rc;
-    if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_a and d_b must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_out must be 16-byte aligned");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -1840,27 +1940,17 @@ int rpf_accumulate_cross(rpf_engine* e, const uint8_t* a, const uint8_t* b, size
     HIP_TRY(e, on_device.status());
     hipStream_t s = e->compute_stream;
     if ((rc = ensure_cross(e)) != RPF_OK) return rc;
-    // pieces of whole frames, series_pieces.h's rule with L = 1: one piece of each stream at a time, side by side
-    const rpf::FrameBytes fb = frame_bytes(e);
-    const rpf::SeriesPieces p = rpf::series_pieces(fb, 1, nframes);
-    const size_t half = (p.bytes + 255) / 256 * 256;
-    if ((rc = grow_scratch(e, &e->d_series_in, &e->series_in_bytes, 2 * half, 1, s)) != RPF_OK) return rc;
-    for (int64_t k0 = 0; k0 < nframes; k0 += p.per_piece) {
-        const int64_t kc = std::min(p.per_piece, nframes - k0);
-        const size_t at = static_cast<size_t>(k0) * p.hop, span = fb.span(kc);
-        HIP_TRY(e, hipMemcpyAsync(e->d_series_in, a + at, span, hipMemcpyHostToDevice, s));
-        HIP_TRY(e, hipMemcpyAsync(e->d_series_in + half, b + at, span, hipMemcpyHostToDevice, s));
-        if ((rc = cross_enqueue(e, e->d_series_in, e->d_series_in + half, kc, /*accumulate=*/k0 > 0, s)) != RPF_OK) {
-            (void)hipStreamSynchronize(s);
-            return rc;
-        }
-        HIP_TRY(e, hipStreamSynchronize(s));
-    }
+    // pieces of whole frames (L = 1), one piece of each stream at a time, side by side
+    const uint8_t* const streams[2] = {a, b};
+    rc = series_host_pieces(
+        e, streams, 2, 1, nframes, INT64_MAX, [](int64_t) { return static_cast<int>(RPF_OK); },
+        [&](int64_t k0, int64_t kc, hipStream_t ps) {
+            return cross_enqueue(e, e->d_series_in, e->d_series_in + e->series_in_stride, kc, /*accumulate=*/k0 > 0, ps);
+        });
+    if (rc != RPF_OK) return rc;
     double* const d_result = e->d_cross_planes + out_doubles;
     HIP_TRY(e, rpf::launch_cross_finish(e->d_cross_planes, e->N, d_result, s));
-    HIP_TRY(e, hipMemcpyAsync(out, d_result, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    return RPF_OK;
+    return copy_back(e, out, d_result, sizeof(double) * out_doubles, s);
 }
 
 // ---- the frames' spectra themselves: rpf_stft_device, rpf_stft (include/rpf_engine.h has the definition) -------------
@@ -1868,20 +1958,14 @@ int rpf_accumulate_cross(rpf_engine* e, const uint8_t* a, const uint8_t* b, size
 // Everything both entries refuse, before any launch.
 static int stft_check(rpf_engine* e, const char* who, const void* stream, size_t nbytes, int64_t max_frames, const void* out)
 {
-    const std::string me = who;
-    if (!e || !out || !stream) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
-    if (e->N & (e->N - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": the number of bins must be a power of two (Bluestein's spectrum lacks its final chirp); got " +
-                        std::to_string(e->N));
-    if (e->stats) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not on an engine created with RPF_FLAG_BIN_STATS");
-    if (e->variant != 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not with a kernel variant other than 0");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": acquisition running");
-    if (max_frames < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": max_frames must not be negative");
-    if (nbytes % e->sample_bytes)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": nbytes must be a multiple of the sample size (" + std::to_string(e->sample_bytes) + " bytes)");
-    return RPF_OK;
+    if (!e || !out || !stream) return refuse(e, who, "NULL argument");
+    int rc = refuse_not_power_of_two(e, who);
+    if (rc == RPF_OK) rc = refuse_stats_engine(e, who);
+    if (rc == RPF_OK) rc = refuse_variant(e, who);
+    if (rc == RPF_OK) rc = refuse_if_running(e, who);
+    if (rc == RPF_OK && max_frames < 0) rc = refuse(e, who, "max_frames must not be negative");
+    if (rc == RPF_OK) rc = refuse_ragged_bytes(e, who, nbytes);
+    return rc;
 }
 
 // K1's store kernels serve every K1 engine the checks let through.
@@ -1908,17 +1992,8 @@ static int ensure_stft(rpf_engine* e)
         return RPF_OK;
     }
     if (e->family == rpf::Family::Generic || e->stft_inner) return RPF_OK;
-    rpf_config icfg;
-    icfg.struct_size = sizeof(icfg);
-    icfg.N = e->N;
-    icfg.window = e->window.empty() ? nullptr : e->window.data();
-    icfg.n_buffers = 1;
-    icfg.buffer_capacity = 8;
-    icfg.device = e->device;
-    icfg.flags = (e->flags & (RPF_FLAG_NO_LDS_DMA | RPF_FLAG_SAMPLE_FORMAT(0xf))) | RPF_FLAG_CATCH_ALL;
-    icfg.frame_step = e->step;
-    const int rc = create_engine(&icfg, nullptr, /*inner_of_pfb=*/true, &e->stft_inner);
-    return rc == RPF_OK ? rc : fail(e, rc, g_last_error);
+    return create_inner(e, (e->flags & (RPF_FLAG_NO_LDS_DMA | RPF_FLAG_SAMPLE_FORMAT(0xf))) | RPF_FLAG_CATCH_ALL, window_as_given(e),
+                        e->step, &e->stft_inner);
 }
 
 // One launch of the plain or (frame step != N) the strided store kernel: rows [0, nframes) of d_out.
@@ -1992,12 +2067,11 @@ static int stft_enqueue(rpf_engine* e, const uint8_t* d_frames, int64_t nframes,
 int rpf_stft_device(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t max_frames, void* d_out, int64_t* frames_done,
                     void* hip_stream)
 {
-    const std::string me = "rpf_stft_device";
-    int rc = stft_check(e, me.c_str(), d_stream, nbytes, max_frames, d_out);
+    const char* who = "rpf_stft_device";
+    int rc = stft_check(e, who, d_stream, nbytes, max_frames, d_out);
+    if (rc == RPF_OK) rc = refuse_unaligned_stream(e, who, "d_stream", d_stream);
+    if (rc == RPF_OK) rc = refuse_unaligned_out(e, who, "d_out", d_out);
     if (rc != RPF_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_out must be 16-byte aligned");
     const int64_t nframes = std::min(frames_in(e, nbytes), max_frames);
     if (frames_done) *frames_done = 0;
     if (nframes == 0) return RPF_OK;
@@ -2027,7 +2101,7 @@ int rpf_stft(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t max_fr
     const int64_t row_cap = rpf::stft_pieces(frame_bytes(e), sizeof(float) * row_floats).per_piece;
     float* const host_rows = static_cast<float*>(out);
     return series_host_pieces(
-        e, stream, 1, nframes, row_cap,
+        e, &stream, 1, 1, nframes, row_cap,
         [&](int64_t per_piece) {
             return grow_scratch(e, &e->d_stft_rows, &e->stft_rows, static_cast<size_t>(per_piece), sizeof(float) * row_floats, s);
         },
@@ -2046,24 +2120,18 @@ int rpf_stft(rpf_engine* e, const uint8_t* stream, size_t nbytes, int64_t max_fr
 static int correlate_check(rpf_engine* e, const char* who, const void* const* streams, int n_streams, size_t nbytes,
                            int64_t repeats, const void* out)
 {
-    const std::string me = who;
     bool null = !e || !streams || !out;
     for (int m = 0; !null && m < n_streams && m < rpf::kCorrelateMaxStreams; ++m) null = !streams[m];
-    if (null) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+    if (null) return refuse(e, who, "NULL argument");
     if (n_streams < rpf::kCorrelateMinStreams || n_streams > rpf::kCorrelateMaxStreams)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": n_streams must be 2 to 8; got " + std::to_string(n_streams));
-    if (e->N & (e->N - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": the number of bins must be a power of two (Bluestein's spectrum lacks its final chirp); got " +
-                        std::to_string(e->N));
-    if (e->stats) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not on an engine created with RPF_FLAG_BIN_STATS");
-    if (e->variant != 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": not with a kernel variant other than 0");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": acquisition running");
-    if (repeats < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
-    if (nbytes % e->sample_bytes)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": nbytes must be a multiple of the sample size (" + std::to_string(e->sample_bytes) + " bytes)");
-    return RPF_OK;
+        return refuse(e, who, "n_streams must be 2 to 8; got " + std::to_string(n_streams));
+    int rc = refuse_not_power_of_two(e, who);
+    if (rc == RPF_OK) rc = refuse_stats_engine(e, who);
+    if (rc == RPF_OK) rc = refuse_variant(e, who);
+    if (rc == RPF_OK) rc = refuse_if_running(e, who);
+    if (rc == RPF_OK) rc = refuse_negative_repeats(e, repeats);
+    if (rc == RPF_OK) rc = refuse_ragged_bytes(e, who, nbytes);
+    return rc;
 }
 
 // What the STFT route needs, the rows scratch of M streams, the X-engine's partial planes and the running planes (the
@@ -2106,14 +2174,12 @@ static int correlate_enqueue(rpf_engine* e, const uint8_t* const* d_streams, int
 int rpf_correlate_device(rpf_engine* e, const void* const* d_streams, int n_streams, size_t nbytes, int64_t repeats, double* d_out,
                          void* hip_stream, int64_t* frames_done)
 {
-    const std::string me = "rpf_correlate_device";
+    const char* who = "rpf_correlate_device";
     if (frames_done) *frames_done = 0;
-    int rc = correlate_check(e, me.c_str(), d_streams, n_streams, nbytes, repeats, d_out);
+    int rc = correlate_check(e, who, d_streams, n_streams, nbytes, repeats, d_out);
+    for (int m = 0; rc == RPF_OK && m < n_streams; ++m) rc = refuse_unaligned_stream(e, who, "every stream", d_streams[m]);
+    if (rc == RPF_OK) rc = refuse_unaligned_out(e, who, "d_out", d_out);
     if (rc != RPF_OK) return rc;
-    for (int m = 0; m < n_streams; ++m)
-        if (reinterpret_cast<uintptr_t>(d_streams[m]) & (e->sample_bytes - 1))
-            return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": every stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": d_out must be 16-byte aligned");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -2148,28 +2214,18 @@ int rpf_correlate(rpf_engine* e, const uint8_t* const* streams, int n_streams, s
     HIP_TRY(e, on_device.status());
     hipStream_t s = e->compute_stream;
     if ((rc = ensure_correlate(e, n_streams, /*host=*/true, s)) != RPF_OK) return rc;
-    // pieces of whole frames, series_pieces.h's rule with L = 1 per stream: one piece of each stream at a time, side by side
-    const rpf::FrameBytes fb = frame_bytes(e);
-    const rpf::SeriesPieces p = rpf::series_pieces(fb, 1, nframes);
-    const size_t part = (p.bytes + 255) / 256 * 256;
-    if ((rc = grow_scratch(e, &e->d_series_in, &e->series_in_bytes, static_cast<size_t>(n_streams) * part, 1, s)) != RPF_OK) return rc;
-    const uint8_t* ptrs[rpf::kCorrelateMaxStreams];
-    for (int m = 0; m < n_streams; ++m) ptrs[m] = e->d_series_in + static_cast<size_t>(m) * part;
-    for (int64_t k0 = 0; k0 < nframes; k0 += p.per_piece) {
-        const int64_t kc = std::min(p.per_piece, nframes - k0);
-        const size_t at = static_cast<size_t>(k0) * p.hop, span = fb.span(kc);
-        for (int m = 0; m < n_streams; ++m)
-            HIP_TRY(e, hipMemcpyAsync(e->d_series_in + static_cast<size_t>(m) * part, streams[m] + at, span, hipMemcpyHostToDevice, s));
-        if ((rc = correlate_enqueue(e, ptrs, n_streams, kc, /*accumulate=*/k0 > 0, s)) != RPF_OK) {
-            (void)hipStreamSynchronize(s);
-            return rc;
-        }
-        HIP_TRY(e, hipStreamSynchronize(s));
-    }
+    // pieces of whole frames (L = 1), one piece of each stream at a time, side by side
+    rc = series_host_pieces(
+        e, streams, n_streams, 1, nframes, INT64_MAX, [](int64_t) { return static_cast<int>(RPF_OK); },
+        [&](int64_t k0, int64_t kc, hipStream_t ps) {
+            const uint8_t* ptrs[rpf::kCorrelateMaxStreams];
+            for (int m = 0; m < n_streams; ++m) ptrs[m] = e->d_series_in + static_cast<size_t>(m) * e->series_in_stride;
+            return correlate_enqueue(e, ptrs, n_streams, kc, /*accumulate=*/k0 > 0, ps);
+        });
+    if (rc != RPF_OK) return rc;
     double* const d_result = e->d_corr_planes + MM * N;
     HIP_TRY(e, rpf::launch_correlate_finish(e->d_corr_planes, n_streams, e->N, d_result, s));
-    HIP_TRY(e, hipMemcpyAsync(out, d_result, sizeof(double) * 2 * MM * N, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
+    if ((rc = copy_back(e, out, d_result, sizeof(double) * 2 * MM * N, s)) != RPF_OK) return rc;
     if (frames_done) *frames_done = nframes;                          // (only with the visibilities of all of them in `out`)
     return RPF_OK;
 }
@@ -2177,22 +2233,18 @@ int rpf_correlate(rpf_engine* e, const uint8_t* const* streams, int n_streams, s
 int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t repeats,
                      void* hip_stream, int64_t* repeats_done)
 {
-    if (!e || !d_stream) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: NULL argument");
-    if (e->taps)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: not on a PFB engine (the fold and the transform are several launches: use rpf_accumulate_device)");
-    if (e->stats)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: not on an engine with RPF_FLAG_BIN_STATS (use rpf_accumulate_device_stats)");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: acquisition running");
-    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    if (overlapped(e) && !is_k1(e))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    "rpf_device_fused: overlapped frames (frame step < N) on this size need rpf_accumulate_device");
+    const char* who = "rpf_device_fused";
+    if (!e || !d_stream) return refuse(e, who, "NULL argument");
+    if (e->taps) return refuse(e, who, "not on a PFB engine (the fold and the transform are several launches: use rpf_accumulate_device)");
+    if (e->stats) return refuse(e, who, "not on an engine with RPF_FLAG_BIN_STATS (use rpf_accumulate_device_stats)");
+    if (int rc = refuse_if_running(e, who)) return rc;
+    if (int rc = refuse_unaligned_stream(e, who, "d_stream", d_stream)) return rc;
+    if (overlapped(e) && !is_k1(e)) return refuse(e, who, "overlapped frames (frame step < N) on this size need rpf_accumulate_device");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     int64_t nframes = frames_in(e, nbytes);
     nframes = std::min(nframes, repeats);
-    if (nframes < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused: no whole frame");
+    if (nframes < 1) return refuse(e, who, "no whole frame");
     if (repeats_done) *repeats_done = nframes;
     if (e->fused) note_device_path_aborts(e);
     int nslots = 0;
@@ -2207,14 +2259,12 @@ int rpf_device_fused(rpf_engine* e, const void* d_stream, size_t nbytes, int64_t
 
 int rpf_device_reduce(rpf_engine* e, double* d_pwr_out, void* hip_stream)
 {
-    if (!e || !d_pwr_out) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: NULL argument");
-    if (reinterpret_cast<uintptr_t>(d_pwr_out) & 15)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: d_pwr_out must be 16-byte aligned");
-    if (e->stats)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: not on an engine with RPF_FLAG_BIN_STATS (use rpf_accumulate_device_stats)");
-    if (e->taps)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: not on a PFB engine (use rpf_accumulate_device)");
-    if (e->last_slots < 1 && e->last_hops < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_reduce: nothing to reduce");
+    const char* who = "rpf_device_reduce";
+    if (!e || !d_pwr_out) return refuse(e, who, "NULL argument");
+    if (int rc = refuse_unaligned_out(e, who, "d_pwr_out", d_pwr_out)) return rc;
+    if (e->stats) return refuse(e, who, "not on an engine with RPF_FLAG_BIN_STATS (use rpf_accumulate_device_stats)");
+    if (e->taps) return refuse(e, who, "not on a PFB engine (use rpf_accumulate_device)");
+    if (e->last_slots < 1 && e->last_hops < 1) return refuse(e, who, "nothing to reduce");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     if (e->last_hops > 0) {
@@ -2229,15 +2279,13 @@ int rpf_device_reduce(rpf_engine* e, double* d_pwr_out, void* hip_stream)
 static int check_hops(rpf_engine* e, const char* who, const void* const* d_streams, const size_t* nbytes,
                       const int64_t* repeats, int H, std::vector<int64_t>* frames)
 {
-    if (!e || !d_streams || !nbytes || !repeats || H < 1)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument or no hop");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": acquisition running");
+    if (!e || !d_streams || !nbytes || !repeats || H < 1) return refuse(e, who, "NULL argument or no hop");
+    if (int rc = refuse_if_running(e, who)) return rc;
     frames->resize(H);
     for (int h = 0; h < H; ++h) {
-        if (repeats[h] < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "Argument to 'repeats' must be a positive number.");
-        if (!d_streams[h] && nbytes[h]) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL stream");
-        if (reinterpret_cast<uintptr_t>(d_streams[h]) & (e->sample_bytes - 1))
-            return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": streams must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
+        if (int rc = refuse_negative_repeats(e, repeats[h])) return rc;
+        if (!d_streams[h] && nbytes[h]) return refuse(e, who, "NULL stream");
+        if (int rc = refuse_unaligned_stream(e, who, "streams", d_streams[h])) return rc;
         (*frames)[h] = std::min<int64_t>(frames_in(e, nbytes[h]), repeats[h]);
     }
     return RPF_OK;
@@ -2257,12 +2305,12 @@ int rpf_accumulate_device_hops(rpf_engine* e, const void* const* d_streams, cons
                                const int64_t* repeats, int n_hops, double* d_pwr_out, void* hip_stream,
                                int64_t* repeats_done)
 {
+    const char* who = "rpf_accumulate_device_hops";
     std::vector<int64_t> frames;
-    int rc = check_hops(e, "rpf_accumulate_device_hops", d_streams, nbytes, repeats, n_hops, &frames);
+    int rc = check_hops(e, who, d_streams, nbytes, repeats, n_hops, &frames);
     if (rc != RPF_OK) return rc;
-    if (!d_pwr_out) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_hops: NULL argument");
-    if (reinterpret_cast<uintptr_t>(d_pwr_out) & 15)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_accumulate_device_hops: d_pwr_out must be 16-byte aligned");
+    if (!d_pwr_out) return refuse(e, who, "NULL argument");
+    if ((rc = refuse_unaligned_out(e, who, "d_pwr_out", d_pwr_out)) != RPF_OK) return rc;
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -2305,17 +2353,15 @@ int rpf_accumulate_device_hops(rpf_engine* e, const void* const* d_streams, cons
 int rpf_device_fused_hops(rpf_engine* e, const void* const* d_streams, const size_t* nbytes,
                           const int64_t* repeats, int n_hops, void* hip_stream, int64_t* repeats_done)
 {
+    const char* who = "rpf_device_fused_hops";
     std::vector<int64_t> frames;
-    int rc = check_hops(e, "rpf_device_fused_hops", d_streams, nbytes, repeats, n_hops, &frames);
+    int rc = check_hops(e, who, d_streams, nbytes, repeats, n_hops, &frames);
     if (rc != RPF_OK) return rc;
-    if (e->stats)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused_hops: not on an engine with RPF_FLAG_BIN_STATS");
-    if (e->taps)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_device_fused_hops: not on a PFB engine (use rpf_accumulate_device_hops)");
+    if (e->stats) return refuse(e, who, "not on an engine with RPF_FLAG_BIN_STATS");
+    if (e->taps) return refuse(e, who, "not on a PFB engine (use rpf_accumulate_device_hops)");
     if (!is_k1(e) || n_hops > rpf::kMaxHops || overlapped(e))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    "rpf_device_fused_hops: needs a size the LDS-resident kernel serves, frames side by side (frame step N) "
-                    "and at most rpf_max_hops_per_launch() hops");
+        return refuse(e, who, "needs a size the LDS-resident kernel serves, frames side by side (frame step N) and at most "
+                              "rpf_max_hops_per_launch() hops");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     if (repeats_done)
@@ -2345,17 +2391,13 @@ static bool series_native(const rpf_engine* e, int64_t L)
 static int series_check(rpf_engine* e, const char* who, const void* stream, size_t nbytes, int64_t L, int64_t max_spectra,
                         const void* out, bool want_stats, int64_t* K)
 {
-    if (!e || !out || (!stream && nbytes)) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
-    if (e->taps)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": not on a PFB engine (PFB with series, statistics or excision is not built)");
-    if (want_stats && !e->stats)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": the engine was created without RPF_FLAG_BIN_STATS");
-    if (!want_stats && e->stats)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    std::string(who) + ": not on an engine with RPF_FLAG_BIN_STATS (time-resolved statistics are not built)");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": acquisition running");
-    if (L < 1) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": frames_per_spectrum must be at least 1");
-    if (max_spectra < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": max_spectra must not be negative");
+    if (!e || !out || (!stream && nbytes)) return refuse(e, who, "NULL argument");
+    if (e->taps) return refuse(e, who, "not on a PFB engine (PFB with series, statistics or excision is not built)");
+    if (want_stats && !e->stats) return refuse(e, who, "the engine was created without RPF_FLAG_BIN_STATS");
+    if (!want_stats && e->stats) return refuse(e, who, "not on an engine with RPF_FLAG_BIN_STATS (time-resolved statistics are not built)");
+    if (int rc = refuse_if_running(e, who)) return rc;
+    if (L < 1) return refuse(e, who, "frames_per_spectrum must be at least 1");
+    if (max_spectra < 0) return refuse(e, who, "max_spectra must not be negative");
     *K = std::min(max_spectra, frames_in(e, nbytes) / L);
     return RPF_OK;
 }
@@ -2364,10 +2406,8 @@ static int series_check(rpf_engine* e, const char* who, const void* stream, size
 // (null in a host entry) are refused if misaligned, the launch count starts over and the caller learns K.
 static int series_begin(rpf_engine* e, const char* who, const void* d_stream, const void* d_out, int64_t K, int64_t* done)
 {
-    if (reinterpret_cast<uintptr_t>(d_stream) & (e->sample_bytes - 1))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_stream must be at least 2-byte aligned (4-byte for 16-bit samples, 8-byte for cf32)");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
+    if (int rc = refuse_unaligned_stream(e, who, "d_stream", d_stream)) return rc;
+    if (int rc = refuse_unaligned_out(e, who, "d_out", d_out)) return rc;
     e->series_launches = 0;
     if (done) *done = K;
     return RPF_OK;
@@ -2462,7 +2502,7 @@ static int series_host(rpf_engine* e, const char* who, bool want_stats, const ui
     HIP_TRY(e, on_device.status());
     const size_t row = static_cast<size_t>(e->N) * (e->stats ? rpf::kStatsPlanes : 1);       // doubles per row
     return series_host_pieces(
-        e, stream, L, K, INT64_MAX, [&](int64_t per_piece) { return ensure_series_rows(e, per_piece, e->compute_stream); },
+        e, &stream, 1, L, K, INT64_MAX, [&](int64_t per_piece) { return ensure_series_rows(e, per_piece, e->compute_stream); },
         [&](int64_t k0, int64_t kc, hipStream_t s) -> int {
             const int rc = series_enqueue(e, e->d_series_in, L, kc, e->d_series_out, s);
             if (rc != RPF_OK) return rc;
@@ -2495,13 +2535,9 @@ static int excise_check(rpf_engine* e, const char* who, const void* stream, size
 {
     const int rc = series_check(e, who, stream, nbytes, L, max_spectra, out, /*want_stats=*/true, K);
     if (rc != RPF_OK) return rc;
-    if (L < 2)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    std::string(who) + ": frames_per_spectrum must be at least 2 (the spectral kurtosis of one frame is undefined)");
-    if (sk_lo != sk_lo || sk_hi != sk_hi)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": a threshold is NaN");
-    if (sk_lo > sk_hi)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": sk_lo is above sk_hi");
+    if (L < 2) return refuse(e, who, "frames_per_spectrum must be at least 2 (the spectral kurtosis of one frame is undefined)");
+    if (sk_lo != sk_lo || sk_hi != sk_hi) return refuse(e, who, "a threshold is NaN");
+    if (sk_lo > sk_hi) return refuse(e, who, "sk_lo is above sk_hi");
     return RPF_OK;
 }
 
@@ -2577,7 +2613,7 @@ int rpf_accumulate_excised(rpf_engine* e, const uint8_t* stream, size_t nbytes, 
     hipStream_t s = e->compute_stream;
     // (a piece's rows are capped as the device entry's are, on top of its input's 64 MB)
     rc = series_host_pieces(
-        e, stream, L, K, excise_row_cap(e),
+        e, &stream, 1, L, K, excise_row_cap(e),
         [&](int64_t per_piece) -> int {
             int rc = grow_scratch(e, &e->d_excise_mask, &e->excise_mask_bytes, mask ? static_cast<size_t>(per_piece) * e->N : 0, 1, s);
             if (rc == RPF_OK) rc = ensure_series_rows(e, per_piece, s);
@@ -2594,9 +2630,7 @@ int rpf_accumulate_excised(rpf_engine* e, const uint8_t* stream, size_t nbytes, 
     if (rc != RPF_OK) return rc;
     double* d_result = e->d_excise_state + rpf::excise_state_doubles(e->N);
     HIP_TRY(e, rpf::launch_excise_combine(e->d_excise_state, e->N, d_result, s));
-    HIP_TRY(e, hipMemcpyAsync(out, d_result, sizeof(double) * out_doubles, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    return RPF_OK;
+    return copy_back(e, out, d_result, sizeof(double) * out_doubles, s);
 }
 
 // ---- per-bin quantiles: rows of the series kept in HBM, order statistics by radix select -----------------------------
@@ -2608,14 +2642,11 @@ static int64_t quantile_max_rows(const rpf_engine* e) { return std::max<int64_t>
 // What every quantile entry refuses, before anything else: the store holds the rows of the plain series.
 static int quantile_check(rpf_engine* e, const char* who)
 {
-    if (!e) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
-    if (e->taps)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": not on a PFB engine (quantiles of PFB spectra are not built)");
+    if (!e) return refuse(e, who, "NULL argument");
+    if (e->taps) return refuse(e, who, "not on a PFB engine (quantiles of PFB spectra are not built)");
     if (e->stats)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    std::string(who) + ": not on an engine with RPF_FLAG_BIN_STATS (the row store holds the rows of rpf_accumulate_device_series)");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": acquisition running");
-    return RPF_OK;
+        return refuse(e, who, "not on an engine with RPF_FLAG_BIN_STATS (the row store holds the rows of rpf_accumulate_device_series)");
+    return refuse_if_running(e, who);
 }
 
 // The append entries' checks; *K = the rows the call appends.  Nothing on the device is touched.
@@ -2626,10 +2657,9 @@ static int quantile_append_check(rpf_engine* e, const char* who, const void* str
     if (rc != RPF_OK) return rc;
     if ((rc = series_check(e, who, stream, nbytes, L, max_spectra, /*out=*/e, /*want_stats=*/false, K)) != RPF_OK) return rc;
     if (e->quantile_rows + *K > quantile_max_rows(e))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    std::string(who) + ": " + std::to_string(e->quantile_rows) + " rows stored and " + std::to_string(*K) +
-                        " to append, the store holds at most " + std::to_string(quantile_max_rows(e)) + " rows of " +
-                        std::to_string(e->N) + " bins (1 GiB): raise the frames per integration or cap max_spectra");
+        return refuse(e, who, std::to_string(e->quantile_rows) + " rows stored and " + std::to_string(*K) +
+                                  " to append, the store holds at most " + std::to_string(quantile_max_rows(e)) + " rows of " +
+                                  std::to_string(e->N) + " bins (1 GiB): raise the frames per integration or cap max_spectra");
     return RPF_OK;
 }
 
@@ -2661,7 +2691,7 @@ static int ensure_quantile_rows(rpf_engine* e, int64_t rows, hipStream_t s)
 
 int rpf_quantile_reset(rpf_engine* e)
 {
-    if (!e) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_quantile_reset: NULL argument");
+    if (!e) return refuse(e, "rpf_quantile_reset", "NULL argument");
     e->quantile_rows = 0;
     return RPF_OK;
 }
@@ -2705,7 +2735,7 @@ int rpf_quantile_append(rpf_engine* e, const uint8_t* stream, size_t nbytes, int
     const int64_t stored = e->quantile_rows;
     int64_t landed = 0;
     rc = series_host_pieces(
-        e, stream, L, K, INT64_MAX, [&](int64_t) { return ensure_quantile_rows(e, stored + K, e->compute_stream); },
+        e, &stream, 1, L, K, INT64_MAX, [&](int64_t) { return ensure_quantile_rows(e, stored + K, e->compute_stream); },
         [&](int64_t k0, int64_t kc, hipStream_t s) {
             return series_enqueue(e, e->d_series_in, L, kc, e->d_quantile_rows + static_cast<size_t>(stored + k0) * e->N, s);
         },
@@ -2721,9 +2751,8 @@ static int quantile_select_check(rpf_engine* e, const char* who, const double* q
     const int rc = quantile_check(e, who);
     if (rc != RPF_OK) return rc;
     if (nq < 1 || nq > rpf::kQuantileMaxQ)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    std::string(who) + ": nq must be in 1 .. " + std::to_string(rpf::kQuantileMaxQ) + ", got " + std::to_string(nq));
-    if (!q || !out) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+        return refuse(e, who, "nq must be in 1 .. " + std::to_string(rpf::kQuantileMaxQ) + ", got " + std::to_string(nq));
+    if (!q || !out) return refuse(e, who, "NULL argument");
     ranks->nq = nq;
     for (int i = 0; i < rpf::kQuantileMaxQ; ++i) {
         ranks->j[i] = 0;
@@ -2731,8 +2760,7 @@ static int quantile_select_check(rpf_engine* e, const char* who, const double* q
     }
     for (int i = 0; i < nq; ++i) {
         if (!(q[i] >= 0.0 && q[i] <= 1.0))
-            return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                        std::string(who) + ": q[" + std::to_string(i) + "] = " + std::to_string(q[i]) + " is not in [0, 1]");
+            return refuse(e, who, "q[" + std::to_string(i) + "] = " + std::to_string(q[i]) + " is not in [0, 1]");
         if (e->quantile_rows > 0) {
             int64_t j = 0;
             rpf::quantile_rank(q[i], e->quantile_rows, j, ranks->g[i]);
@@ -2753,10 +2781,9 @@ int rpf_quantile_select_device(rpf_engine* e, const double* q, int nq, double* d
 {
     const char* who = "rpf_quantile_select_device";
     rpf::QuantileRanks ranks;
-    const int rc = quantile_select_check(e, who, q, nq, d_out, &ranks);
+    int rc = quantile_select_check(e, who, q, nq, d_out, &ranks);
+    if (rc == RPF_OK) rc = refuse_unaligned_out(e, who, "d_out", d_out);
     if (rc != RPF_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(d_out) & 15)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     return quantile_select_enqueue(e, ranks, d_out, static_cast<hipStream_t>(hip_stream));
@@ -2773,9 +2800,7 @@ int rpf_quantile_select(rpf_engine* e, const double* q, int nq, double* out)
     rc = grow_scratch(e, &e->d_quantile_out, &e->quantile_out_planes, static_cast<size_t>(nq), sizeof(double) * e->N, s);
     if (rc != RPF_OK) return rc;
     if ((rc = quantile_select_enqueue(e, ranks, e->d_quantile_out, s)) != RPF_OK) return rc;
-    HIP_TRY(e, hipMemcpyAsync(out, e->d_quantile_out, sizeof(double) * static_cast<size_t>(nq) * e->N, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    return RPF_OK;
+    return copy_back(e, out, e->d_quantile_out, sizeof(double) * static_cast<size_t>(nq) * e->N, s);
 }
 
 // ---- incoherent dedispersion of the stored integrations: rpf_dedisperse_device, rpf_dedisperse (include/rpf_engine.h) --
@@ -2801,31 +2826,27 @@ static int dedisperse_check(rpf_engine* e, const char* who, const int32_t* delay
     if (times) *times = 0;
     const int rc = quantile_check(e, who);
     if (rc != RPF_OK) return rc;
-    const std::string me = who;
-    if (!delays || !out || !times) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
+    if (!delays || !out || !times) return refuse(e, who, "NULL argument");
     if (n_trials < 1 || n_trials > rpf::kDedispMaxTrials)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": n_trials must be in 1 .. " + std::to_string(rpf::kDedispMaxTrials) + ", got " + std::to_string(n_trials));
+        return refuse(e, who, "n_trials must be in 1 .. " + std::to_string(rpf::kDedispMaxTrials) + ", got " + std::to_string(n_trials));
     const size_t N = static_cast<size_t>(e->N);
     size_t at = 0;
     const int64_t dmax = dedisperse_dmax(delays, static_cast<size_t>(n_trials) * N, &at);
     if (dmax < 0)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": negative delay " + std::to_string(delays[at]) + " at trial " + std::to_string(at / N) + ", bin " +
-                        std::to_string(at % N));
+        return refuse(e, who, "negative delay " + std::to_string(delays[at]) + " at trial " + std::to_string(at / N) + ", bin " +
+                                  std::to_string(at % N));
     for (size_t b = 0; weights && b < N; ++b)
-        if (!std::isfinite(weights[b]))
-            return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": weights[" + std::to_string(b) + "] is not finite");
+        if (!std::isfinite(weights[b])) return refuse(e, who, "weights[" + std::to_string(b) + "] is not finite");
     *T = rpf::dedisperse_times(e->quantile_rows, dmax);
     if (static_cast<int64_t>(n_trials) * *T > capacity)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": " + std::to_string(n_trials) + " trials of " + std::to_string(*T) + " times need " +
-                        std::to_string(static_cast<int64_t>(n_trials) * *T) + " doubles, the capacity is " + std::to_string(capacity));
+        return refuse(e, who, std::to_string(n_trials) + " trials of " + std::to_string(*T) + " times need " +
+                                  std::to_string(static_cast<int64_t>(n_trials) * *T) + " doubles, the capacity is " +
+                                  std::to_string(capacity));
     return RPF_OK;
 }
 
 // Uploads the weights (NULL: ones), the spans of dedisperse_core.h and the table into the engine's tables, then the
-// launch, all on `s`.  The tables serve one call at a time: the call before this one has passed dd_done by then.
+// launch, all on `s`.  The tables serve one call at a time (UploadTable).
 static int dedisperse_enqueue(rpf_engine* e, const int32_t* delays, const double* weights, int D, int64_t T, double* d_out,
                               hipStream_t s)
 {
@@ -2833,35 +2854,24 @@ static int dedisperse_enqueue(rpf_engine* e, const int32_t* delays, const double
     const int tiles = rpf::dedisperse_trial_tiles(D), nblocks = rpf::dedisperse_bin_blocks(e->N);
     const size_t spans_at = sizeof(double) * N, delays_at = spans_at + sizeof(rpf::DedispSpan) * tiles * nblocks;
     const size_t bytes = delays_at + sizeof(int32_t) * static_cast<size_t>(D) * N;
-    if (e->dd_done)
-        HIP_TRY(e, hipEventSynchronize(e->dd_done));
-    else
-        HIP_TRY(e, hipEventCreateWithFlags(&e->dd_done, hipEventDisableTiming));
-    if (bytes > e->dd_tables_bytes) {
-        if (e->h_dd_tables) (void)hipHostFree(e->h_dd_tables);
-        (void)hipFree(e->d_dd_tables);
-        e->h_dd_tables = e->d_dd_tables = nullptr;
-        e->dd_tables_bytes = 0;
-        HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_dd_tables), bytes, hipHostMallocDefault));
-        HIP_TRY(e, hipMalloc(&e->d_dd_tables, bytes));
-        e->dd_tables_bytes = bytes;
-    }
-    double* const w = reinterpret_cast<double*>(e->h_dd_tables);
+    UploadTable& t = e->dd_tables;
+    if (int rc = t.reserve(e, bytes)) return rc;
+    double* const w = reinterpret_cast<double*>(t.host);
     if (weights)
         std::copy(weights, weights + N, w);
     else
         std::fill(w, w + N, 1.0);
-    rpf::DedispSpan* const spans = reinterpret_cast<rpf::DedispSpan*>(e->h_dd_tables + spans_at);
+    rpf::DedispSpan* const spans = reinterpret_cast<rpf::DedispSpan*>(t.host + spans_at);
     for (int tile = 0; tile < tiles; ++tile)
         for (int blk = 0; blk < nblocks; ++blk) spans[tile * nblocks + blk] = rpf::dedisperse_span(delays, w, e->N, D, tile, blk);
-    std::memcpy(e->h_dd_tables + delays_at, delays, bytes - delays_at);
-    HIP_TRY(e, hipMemcpyAsync(e->d_dd_tables, e->h_dd_tables, bytes, hipMemcpyHostToDevice, s));
+    std::memcpy(t.host + delays_at, delays, bytes - delays_at);
+    HIP_TRY(e, hipMemcpyAsync(t.device, t.host, bytes, hipMemcpyHostToDevice, s));
     const hipError_t launched = rpf::launch_dedisperse(e->d_quantile_rows, e->quantile_rows, e->N,
-                                                       reinterpret_cast<const int32_t*>(e->d_dd_tables + delays_at),
-                                                       reinterpret_cast<const double*>(e->d_dd_tables),
-                                                       e->d_dd_tables + spans_at, D, T, d_out, s);
+                                                       reinterpret_cast<const int32_t*>(t.device + delays_at),
+                                                       reinterpret_cast<const double*>(t.device), t.device + spans_at, D, T,
+                                                       d_out, s);
     // (recorded whether or not the launch went out: the copy above reads the pinned block until then)
-    HIP_TRY(e, hipEventRecord(e->dd_done, s));
+    if (int rc = t.record(e, s)) return rc;
     HIP_TRY(e, launched);
     return RPF_OK;
 }
@@ -2878,10 +2888,9 @@ int rpf_dedisperse_device(rpf_engine* e, const int32_t* delays, const double* we
 {
     const char* who = "rpf_dedisperse_device";
     int64_t T = 0;
-    const int rc = dedisperse_check(e, who, delays, weights, n_trials, d_out, capacity, times, &T);
+    int rc = dedisperse_check(e, who, delays, weights, n_trials, d_out, capacity, times, &T);
+    if (rc == RPF_OK) rc = refuse_unaligned_out(e, who, "d_out", d_out);
     if (rc != RPF_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(d_out) & 15)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_out must be 16-byte aligned");
     if (T == 0) return RPF_OK;
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
@@ -2902,8 +2911,7 @@ int rpf_dedisperse(rpf_engine* e, const int32_t* delays, const double* weights, 
     const size_t cells = static_cast<size_t>(n_trials) * static_cast<size_t>(T);
     if ((rc = grow_scratch(e, &e->d_dd_out, &e->dd_out, cells, sizeof(double), s)) != RPF_OK) return rc;
     if ((rc = dedisperse_enqueue(e, delays, weights, n_trials, T, e->d_dd_out, s)) != RPF_OK) return rc;
-    HIP_TRY(e, hipMemcpyAsync(out, e->d_dd_out, sizeof(double) * cells, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
+    if ((rc = copy_back(e, out, e->d_dd_out, sizeof(double) * cells, s)) != RPF_OK) return rc;
     *times = T;
     return RPF_OK;
 }
@@ -2914,65 +2922,49 @@ int rpf_dedisperse(rpf_engine* e, const int32_t* delays, const double* weights, 
 static int fold_check(rpf_engine* e, const char* who, int D, int64_t T, const uint64_t* steps, int P, int NB, const void* prof,
                       int64_t capacity)
 {
-    const std::string me = who;
-    if (!steps || !prof) return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": NULL argument");
-    if (D < 1 || D > rpf::kFoldMaxSeries)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": n_series must be in 1 .. " + std::to_string(rpf::kFoldMaxSeries) + ", got " + std::to_string(D));
-    if (P < 1 || P > rpf::kFoldMaxPeriods)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": n_periods must be in 1 .. " + std::to_string(rpf::kFoldMaxPeriods) + ", got " + std::to_string(P));
-    if (NB < 1 || NB > rpf::kFoldMaxBins)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": phase_bins must be in 1 .. " + std::to_string(rpf::kFoldMaxBins) + ", got " + std::to_string(NB));
-    if (T < 0 || T >= (static_cast<int64_t>(1) << 31))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, me + ": T must be in 0 .. 2^31 - 1, got " + std::to_string(T));
+    auto range = [&](const char* name, int hi, int got) {
+        return refuse(e, who, std::string(name) + " must be in 1 .. " + std::to_string(hi) + ", got " + std::to_string(got));
+    };
+    if (!steps || !prof) return refuse(e, who, "NULL argument");
+    if (D < 1 || D > rpf::kFoldMaxSeries) return range("n_series", rpf::kFoldMaxSeries, D);
+    if (P < 1 || P > rpf::kFoldMaxPeriods) return range("n_periods", rpf::kFoldMaxPeriods, P);
+    if (NB < 1 || NB > rpf::kFoldMaxBins) return range("phase_bins", rpf::kFoldMaxBins, NB);
+    if (T < 0 || T >= (static_cast<int64_t>(1) << 31)) return refuse(e, who, "T must be in 0 .. 2^31 - 1, got " + std::to_string(T));
     const int64_t cells = static_cast<int64_t>(D) * P * NB;
     if (cells > capacity || cells > rpf::kFoldMaxCells)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT,
-                    me + ": " + std::to_string(D) + " series x " + std::to_string(P) + " periods x " + std::to_string(NB) +
-                        " phase bins are " + std::to_string(cells) + " cells, the capacity is " + std::to_string(capacity) +
-                        " and a call folds at most " + std::to_string(rpf::kFoldMaxCells));
+        return refuse(e, who, std::to_string(D) + " series x " + std::to_string(P) + " periods x " + std::to_string(NB) +
+                                  " phase bins are " + std::to_string(cells) + " cells, the capacity is " + std::to_string(capacity) +
+                                  " and a call folds at most " + std::to_string(rpf::kFoldMaxCells));
     return RPF_OK;
 }
 
 // Uploads the steps into the engine's table and enqueues the launches of every group of series, all on `s`.  The table
-// and the scratch serve one call at a time: the call before this one has passed fold_done by then.
+// and the scratch serve one call at a time (UploadTable).
 static int fold_enqueue(rpf_engine* e, const double* d_x, int D, int64_t T, const uint64_t* steps, int P, int NB, double* d_prof,
                         int32_t* d_hits, double* d_mom, hipStream_t s)
 {
-    if (e->fold_done)
-        HIP_TRY(e, hipEventSynchronize(e->fold_done));
-    else
-        HIP_TRY(e, hipEventCreateWithFlags(&e->fold_done, hipEventDisableTiming));
-    if (static_cast<size_t>(P) > e->fold_steps) {
-        if (e->h_fold_steps) (void)hipHostFree(e->h_fold_steps);
-        (void)hipFree(e->d_fold_steps);
-        e->h_fold_steps = e->d_fold_steps = nullptr;
-        e->fold_steps = 0;
-        HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_fold_steps), sizeof(uint64_t) * P, hipHostMallocDefault));
-        HIP_TRY(e, hipMalloc(&e->d_fold_steps, sizeof(uint64_t) * P));
-        e->fold_steps = static_cast<size_t>(P);
-    }
+    UploadTable& t = e->fold_steps;
+    if (int rc = t.reserve(e, sizeof(uint64_t) * P)) return rc;
+    uint64_t* const d_steps = reinterpret_cast<uint64_t*>(t.device);
     const int per_group = rpf::fold_group_series(D, P, NB);
     const size_t need = rpf::fold_scratch(per_group, P, NB).bytes;
-    if (need > e->fold_scratch_bytes) {          // (nothing of this engine reads the scratch now: fold_done has passed)
+    if (need > e->fold_scratch_bytes) {          // (nothing of this engine reads the scratch now: the table's `done` has passed)
         (void)hipFree(e->d_fold_scratch);
         e->d_fold_scratch = nullptr;
         e->fold_scratch_bytes = 0;
         HIP_TRY(e, hipMalloc(&e->d_fold_scratch, need));
         e->fold_scratch_bytes = need;
     }
-    std::copy(steps, steps + P, e->h_fold_steps);
-    HIP_TRY(e, hipMemcpyAsync(e->d_fold_steps, e->h_fold_steps, sizeof(uint64_t) * P, hipMemcpyHostToDevice, s));
+    std::copy(steps, steps + P, reinterpret_cast<uint64_t*>(t.host));
+    HIP_TRY(e, hipMemcpyAsync(d_steps, t.host, sizeof(uint64_t) * P, hipMemcpyHostToDevice, s));
     hipError_t launched = hipSuccess;
     const size_t cells = static_cast<size_t>(P) * NB;
     for (int s0 = 0; s0 < D && launched == hipSuccess; s0 += per_group)
-        launched = rpf::launch_fold(d_x + static_cast<size_t>(s0) * T, std::min(per_group, D - s0), T, e->d_fold_steps, P, NB,
+        launched = rpf::launch_fold(d_x + static_cast<size_t>(s0) * T, std::min(per_group, D - s0), T, d_steps, P, NB,
                                     e->d_fold_scratch, d_prof + s0 * cells, s0 == 0 ? d_hits : nullptr,
                                     d_mom ? d_mom + 2 * static_cast<size_t>(s0) : nullptr, s);
     // (recorded whether or not the launches went out: the copy above reads the pinned block until then)
-    HIP_TRY(e, hipEventRecord(e->fold_done, s));
+    if (int rc = t.record(e, s)) return rc;
     HIP_TRY(e, launched);
     return RPF_OK;
 }
@@ -2981,16 +2973,14 @@ int rpf_fold_device(rpf_engine* e, const double* d_series, int n_series, int64_t
                     int phase_bins, double* d_prof, int64_t capacity, int32_t* d_hits, double* d_mom, void* hip_stream)
 {
     const char* who = "rpf_fold_device";
-    if (!e || !d_series) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": acquisition running");
-    const int rc = fold_check(e, who, n_series, T, steps, n_periods, phase_bins, d_prof, capacity);
+    if (!e || !d_series) return refuse(e, who, "NULL argument");
+    int rc = refuse_if_running(e, who);
+    if (rc == RPF_OK) rc = fold_check(e, who, n_series, T, steps, n_periods, phase_bins, d_prof, capacity);
     if (rc != RPF_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(d_series) & 7)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_series must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_series) & 7) return refuse(e, who, "d_series must be 8-byte aligned");
     if ((reinterpret_cast<uintptr_t>(d_prof) & 15) || (reinterpret_cast<uintptr_t>(d_mom) & 15))
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_prof and d_mom must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_hits) & 3)
-        return fail(e, RPF_ERR_INVALID_ARGUMENT, std::string(who) + ": d_hits must be 4-byte aligned");
+        return refuse(e, who, "d_prof and d_mom must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_hits) & 3) return refuse(e, who, "d_hits must be 4-byte aligned");
     if (T == 0) return RPF_OK;
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
@@ -3034,8 +3024,8 @@ int rpf_series_launches(const rpf_engine* e) { return e ? e->series_launches : 0
 
 int rpf_stream_register(rpf_engine* e, const void* stream, size_t nbytes)
 {
-    if (!e || !stream || nbytes == 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_stream_register: NULL or empty stream");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_stream_register: acquisition running");
+    if (!e || !stream || nbytes == 0) return refuse(e, "rpf_stream_register", "NULL or empty stream");
+    if (int rc = refuse_if_running(e, "rpf_stream_register")) return rc;
     DeviceScope on_device(e->device);
     HIP_TRY(e, on_device.status());
     const hipError_t err = hipHostRegister(const_cast<void*>(stream), nbytes, hipHostRegisterDefault);
@@ -3049,8 +3039,8 @@ int rpf_stream_register(rpf_engine* e, const void* stream, size_t nbytes)
 
 int rpf_stream_unregister(rpf_engine* e, const void* stream)
 {
-    if (!e || !stream) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_stream_unregister: NULL argument");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_stream_unregister: acquisition running");
+    if (!e || !stream) return refuse(e, "rpf_stream_unregister", "NULL argument");
+    if (int rc = refuse_if_running(e, "rpf_stream_unregister")) return rc;
     for (size_t k = 0; k < e->registered.size(); ++k) {
         if (e->registered[k].first != stream) continue;
         DeviceScope on_device(e->device);
@@ -3059,7 +3049,7 @@ int rpf_stream_unregister(rpf_engine* e, const void* stream)
         e->registered.erase(e->registered.begin() + static_cast<long>(k));
         return RPF_OK;
     }
-    return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_stream_unregister: not a registered stream");
+    return refuse(e, "rpf_stream_unregister", "not a registered stream");
 }
 
 int rpf_fused_status(rpf_engine* e, int* active, int64_t* launches_gave_up, int64_t* launches_recovered)
@@ -3074,8 +3064,8 @@ int rpf_fused_status(rpf_engine* e, int* active, int64_t* launches_gave_up, int6
 
 int rpf_debug_fused_fault(rpf_engine* e, int mode, int skip, int count)
 {
-    if (!e || mode < 0 || mode > 2 || skip < 0) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_debug_fused_fault: bad argument");
-    if (e->worker_running) return fail(e, RPF_ERR_INVALID_ARGUMENT, "rpf_debug_fused_fault: acquisition running");
+    if (!e || mode < 0 || mode > 2 || skip < 0) return refuse(e, "rpf_debug_fused_fault", "bad argument");
+    if (int rc = refuse_if_running(e, "rpf_debug_fused_fault")) return rc;
     e->fused_fault_mode = mode;
     e->fused_fault_skip = skip;
     e->fused_fault_count = mode ? count : 0;
