@@ -475,7 +475,7 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_rows_kernel(const cf* __restr
 // through -- and a line stored by one CU is served to another CU OF THE SAME XCD from the L2 (sc1 loads): the read
 // half of the round trip can stay on chip, and with one 2 MB buffer of Y per team part of the write half too (the
 // shipped two-buffer form cycles 4 MB through a 4 MB L2: all of Y is written back once and about two thirds of
-// its reads miss, see NBUF below).  Here ONE persistent launch does both
+// its reads miss).  Here ONE persistent launch does both
 // steps: the 32 workgroups that share an XCD (one per CU, found by HW_REG_XCC_ID: correctness never rests on a
 // block -> XCD guess) form a team that owns one round of FR = 262144 / N frames at a time, 2 MB of Y, double
 // buffered in the team's 4 MB L2.  Inside a workgroup the sixteen wavefronts split into two ROLES that run their
@@ -500,27 +500,14 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_rows_kernel(const cf* __restr
 struct FusedCtl {
     unsigned arrivals[8][32];     // [xcd][0]: members registered (own 128-byte line each)
     // One pair of counters per buffer, cumulative over the rounds that use the buffer: a producer arrives for round j only
-    // after all 32 consumers of round j - NBUF, a consumer for round j only after all 32 producers of round j -- no
+    // after all 32 consumers of round j - 2, a consumer for round j only after all 32 producers of round j -- no
     // arrival of a later round of the SAME buffer can stand in for a missing one of an earlier round.  (One counter for
     // two buffers could: 31 arrivals of round j + 1 of round j + 1 = 32.)
-    unsigned produced[8][4][32];  // [xcd][buffer][0]: producer arrivals, 32 per round (three buffers in the half-frame form)
-    unsigned consumed[8][4][32];  // [xcd][buffer][0]: consumer arrivals, 32 per round (16 per half round, half-frame form)
+    unsigned produced[8][4][32];  // [xcd][buffer][0]: producer arrivals, 32 per round (buffers 0 and 1 are used)
+    unsigned consumed[8][4][32];  // [xcd][buffer][0]: consumer arrivals, 32 per round (buffers 0 and 1 are used)
     unsigned registered[32];      // [0]: workgroups registered, grid-wide
     unsigned abort[32];           // [0]: != 0 -> results invalid
 };
-#ifdef RPF_FUSED_PROFILE
-// measurement knobs (rpf_debug_fused_knobs): [0] poll pause 0: s_sleep 2, 1: none, 2: s_sleep 8, 4: vector-path polls;
-// [1] 1: tiles rotated by half a frame against the team ranks, 2: the tiles' places in Y rotated, 3: no raw rows (garbage
-// in), 5 / 6: the raw rows' LDS-DMA issued after the column transforms; [2] consumers skip their transforms; [3] producers
-// skip theirs (results are garbage with 2, 3)
-__device__ int g_fused_knob[4];
-#define FKNOB(i) g_fused_knob[i]
-#else
-#ifndef RPF_FUSED_KNOB1
-#define RPF_FUSED_KNOB1 0
-#endif
-#define FKNOB(i) ((i) == 1 ? RPF_FUSED_KNOB1 : 0)      // (-DRPF_FUSED_KNOB1=n: knob 1 at compile time; round 4's A/B, profiles/r04_c4_fused.txt)
-#endif
 constexpr unsigned kSpinLimit = 4u << 20;      // global polls of ~0.1-3 us: >= 0.5 s
 constexpr unsigned kLdsSpinLimit = 1u << 26;   // LDS polls of ~50 ns
 
@@ -529,31 +516,24 @@ __device__ __forceinline__ unsigned ctl_load(const unsigned* p)
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Current value of a team counter: an sc1 load, written in assembly, is served by the XCD's L2 -- where the team's
-// atomics execute -- and never by this CU's L1 (a plain or sc0 load is, stale for ever once the line is resident).
-// Round 2 polled with a returning atomic add of zero: 64 pollers per XCD saturate the one L2 channel that owns the
-// counter's line (~88 atomics per microsecond), and every stream that stripes over the channels -- the Y stores'
-// drain, the tile loads -- then runs at that channel's pace (measured: 94 us per round instead of < 10).
-__device__ __forceinline__ unsigned l2_read(const unsigned* p)
-{
-    unsigned r;
-    asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(r) : "v"(p) : "memory");
-    return r;
-}
-
 // What the two roles of a workgroup share in LDS (static: the dynamic area is full).
 struct FusedSync {
     unsigned bar[3];          // [0], [1]: role barriers, monotonically increasing arrival counts (8 per barrier);
                               // [2]: consumer waves that have taken their columns out of the tile (8 per round)
     unsigned seen[2][4];      // [0][buffer]: `consumed` as last polled by the producers' wave 0; [1][buffer]: `produced`, consumers'
+                              // (buffers 0 and 1 are used)
     unsigned abort;           // a bounded spin ran out somewhere in this workgroup (or the grid's flag was seen)
     int team[3];              // xcd, rank, ok
 };
 
-// The same word through the SCALAR memory path (s_load_dword glc: past the scalar cache, to the L2): a queue of its own,
-// not behind the CU's vector-memory traffic -- where a poll otherwise waits out the CU's own tile loads, Y stores and
-// LDS-DMA (measured in the profile build: + 3 % with two buffers of Y per team, + 16 % with one).  What the shipped
-// kernel polls with; the vector form stays for measurement (knob 0 = 4).
+// Current value of a team counter, read where the team's atomics execute: in the XCD's L2, never in this CU's caches
+// (a plain load is served by the L1, stale for ever once the line is resident).  A poll is a LOAD, not a returning
+// atomic: round 2 polled with a returning atomic add of zero, 64 pollers per XCD saturate the one L2 channel that owns
+// the counter's line (~88 atomics per microsecond), and every stream that stripes over the channels -- the Y stores'
+// drain, the tile loads -- then runs at that channel's pace (measured: 94 us per round instead of < 10).
+// It goes through the SCALAR memory path (s_load_dword glc: past the scalar cache, to the L2): a queue of its own,
+// not behind the CU's vector-memory traffic -- where an sc1 vector load waits out the CU's own tile loads, Y stores and
+// LDS-DMA (+ 3 % with two buffers of Y per team, + 16 % with one: DESIGN.md, Four-step, "Retired experiments").
 __device__ __forceinline__ unsigned l2_read_scalar(const unsigned* p)
 {
     const unsigned long long a = reinterpret_cast<unsigned long long>(p);
@@ -620,41 +600,19 @@ __device__ __forceinline__ bool role_barrier(FusedSync* sy, int role, unsigned t
 
 // Wait until the team's counter reaches `target`: wave 0 of the role polls the L2 (one lane), everybody else
 // watches the value it publishes in LDS.
-// dma_pending (knob 1 = 6, measurement only): the wave has LDS-DMA in flight and keeps off the LDS until it has landed.
 __device__ __forceinline__ bool team_wait(FusedCtl* ctl, FusedSync* sy, const unsigned* counter, unsigned* seen, unsigned target,
-                                          bool poller, int lane, bool dma_pending = false)
+                                          bool poller, int lane)
 {
-    if (!dma_pending && lds_peek(seen) >= target) return true;
+    if (lds_peek(seen) >= target) return true;
     unsigned spins = 0;
-    if (poller && dma_pending) {
+    if (poller) {
         for (;;) {
             const unsigned v = l2_read_scalar(counter);
             if (v >= target) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (lane == 0) __hip_atomic_store(seen, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 return true;
             }
             __builtin_amdgcn_s_sleep(2);
-            if (++spins > kSpinLimit || ((spins & 255u) == 0 && l2_read_scalar(&ctl->abort[0]) != 0)) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane == 0) {
-                    __hip_atomic_store(&ctl->abort[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&sy->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                return false;
-            }
-        }
-    }
-    if (dma_pending) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (poller) {
-        for (;;) {
-            const unsigned v = FKNOB(0) == 4 ? __builtin_amdgcn_readfirstlane(l2_read(counter)) : l2_read_scalar(counter);
-            if (v >= target) {
-                if (lane == 0) __hip_atomic_store(seen, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                return true;
-            }
-            if (FKNOB(0) == 0 || FKNOB(0) == 4) __builtin_amdgcn_s_sleep(2);
-            else if (FKNOB(0) == 2) __builtin_amdgcn_s_sleep(8);
             if (++spins > kSpinLimit || lds_peek(&sy->abort) ||
                 ((spins & 255u) == 0 && l2_read_scalar(&ctl->abort[0]) != 0)) {
                 if (lane == 0) {
@@ -672,40 +630,6 @@ __device__ __forceinline__ bool team_wait(FusedCtl* ctl, FusedSync* sy, const un
     return true;
 }
 
-// -DRPF_FUSED_PROFILE: lane 0 of wave 0 of each role adds the wall-clock ticks (100 MHz) it spends in each segment
-// of a round to g_fused_prof (printed by tools/gpu_fused_profile.py, which left the tree in round 6: `git show 71dca54:tools/gpu_fused_profile.py`); never in the shipped library.
-#ifdef RPF_FUSED_PROFILE
-__device__ unsigned long long g_fused_prof[16];
-__device__ unsigned long long g_fused_prof_wg[256][16];     // the same per workgroup (32 xcd + rank), last launch
-// absolute 100 MHz time stamps of the hand-offs, [workgroup = 32 xcd + rank][round < 64][event]: 0 producers arrived,
-// 1 consumers saw `produced`, 2 consumers arrived, 3 producers saw `consumed` (that tool prints
-// where the signals spend their time)
-__device__ unsigned long long g_fused_trace[256][64][4];
-#define FTRACE(ev) do { if (rw == 0 && lane == 0 && j < 64) g_fused_trace[32 * xcd + rank][j][ev] = wall_clock64(); } while (0)
-
-struct FusedClock {
-    unsigned long long last, sum[8];
-    __device__ __forceinline__ void start() { for (int i = 0; i < 8; ++i) sum[i] = 0; last = wall_clock64(); }
-    __device__ __forceinline__ void stamp(int i) { const unsigned long long now = wall_clock64(); sum[i] += now - last; last = now; }
-    __device__ __forceinline__ void publish(int base, bool who, int wg = -1)
-    {
-        if (who) {
-            for (int i = 0; i < 7; ++i) atomicAdd(&g_fused_prof[base + i], sum[i]);
-            atomicAdd(&g_fused_prof[base + 7], 1ull);
-            if (wg >= 0) for (int i = 0; i < 7; ++i) g_fused_prof_wg[wg][base + i] = sum[i];
-        }
-    }
-};
-#define FSTAMP(i) fclk.stamp(i)
-#else
-struct FusedClock {
-    __device__ __forceinline__ void start() {}
-    __device__ __forceinline__ void publish(int, bool, int = -1) {}
-};
-#define FSTAMP(i) ((void)0)
-#define FTRACE(ev) ((void)0)
-#endif
-
 constexpr int kRoleWaves = kWaves / 2, kRoleThreads = kRoleWaves * 64;
 
 template <class S>
@@ -719,19 +643,10 @@ constexpr int fused_lds_bytes()
     return slabs + tile + raw + twtables + steptab + kWideTabBytes;
 }
 
-// NBUF: buffers of Y per team.  1: the round's 2 MB stay in the L2 for good (every read hits, 39 % of the writes never
-// leave: 3.4 x the algorithmic traffic, measured) but every round waits out both hand-offs, 2 x 1.2 - 3.8 us on a busy
-// CU: 0.22 Tsample/s; 2 (shipped): a round's hand-offs hide behind the other buffer's work, 4 MB of Y cycle through a
-// 4 MB L2, all of it is written back once and about two thirds of the reads miss: 0.245.  NT (measurement only): the
-// consumers' tile loads and the raw rows carry the non-temporal hint -- no effect either way (profiles/r04_c4_fused.txt).
-// 3 (round 5's experiment, -DRPF_FUSED_NBUF=3; profiles/r05_c4_halfframe.txt): the HALF-FRAME form -- Y in three buffers of HALF a round (the k1 tiles
-// [0, TPF/2) and [TPF/2, TPF) of every frame slot: 1 MB each), half round q = 2 j + h in buffer q mod 3; the producers
-// signal each half as its stores have drained, the sixteen consumer workgroups of a half start while the other half is
-// being stored; 3 MB of Y per 4 MB L2 (profiles/r04_l2_residency.txt: at that footprint the reads still hit).
-#ifndef RPF_FUSED_NBUF
-#define RPF_FUSED_NBUF 2
-#endif
-template <class S, bool WINDOW, bool DMA, int NBUF = RPF_FUSED_NBUF, int NT = 0>
+// Two buffers of Y per team: a round's hand-offs hide behind the other buffer's work; 4 MB of Y cycle through a 4 MB L2,
+// all of it is written back once and about two thirds of the reads miss.  The rejected forms (one buffer, three half
+// buffers, non-temporal loads, the LDS-DMA issued late) and their numbers: DESIGN.md, Four-step, "Retired experiments".
+template <class S, bool WINDOW, bool DMA>
 __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* __restrict__ stream, int nframes,
                                                                const cf* __restrict__ tw_n1,
                                                                const cf* __restrict__ tw_n2,
@@ -797,24 +712,15 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
     __syncthreads();                                 // the only workgroup-wide barrier before the output stage
     const int xcd = sy->team[0], rank = sy->team[1];
     if (!sy->team[2] || rank >= 32) return;
-    // (measurement knob 1, profile build: the tiles rotated by half a frame against the ranks -- does a slow workgroup
-    //  follow its tile or its CU?)
-    const int fsl = rank / TPF, tl = (rank % TPF + (FKNOB(1) == 1 ? TPF / 2 : 0)) % TPF;            // frame slot of the round, tile of the frame
-    const int YROT = FKNOB(1) == 2 ? 7 % TPF : 0;     // (knob 1 = 2: the tiles' places in Y rotated by 7 -- does the slow tile follow its address?)
+    const int fsl = rank / TPF, tl = rank % TPF;            // frame slot of the round, tile of the frame
     const int nrounds = (nframes + FR - 1) / FR;
     const int nj = xcd < nrounds ? (nrounds - xcd + 7) / 8 : 0;    // this team's rounds: xcd, xcd + 8, ...
-    constexpr bool HALFF = NBUF == 3;                // half-frame form
-    constexpr int HT = TPF / 2;                      // k1 tiles per half
-    constexpr size_t HB = static_cast<size_t>(FR) * N / 2;      // complex values per half buffer
-    static_assert(!HALFF || TPF % 2 == 0, "two halves of whole tiles");
-    cf* const Yteam = HALFF ? Yall + static_cast<size_t>(xcd) * 3 * HB + static_cast<size_t>(fsl) * (N / 2)       // + (q % 3) * HB
-                            : Yall + static_cast<size_t>(xcd) * NBUF * FR * N + static_cast<size_t>(fsl) * N;     // + (j % NBUF) * FR * N
+    cf* const Yteam = Yall + static_cast<size_t>(xcd) * 2 * FR * N + static_cast<size_t>(fsl) * N;     // + (j % 2) * FR * N
 
     const bool producer = wave < kRoleWaves;
     const int rw = wave & (kRoleWaves - 1);          // wave inside its role
     const int rtid = rw * 64 + lane;                 // thread inside its role
     bool alive = true;
-    FusedClock fclk;
 
     // Raw rows of (frame f, tile tl) -> LDS in 16-byte pieces, asynchronously (LDS-DMA) when DMA: two instructions
     // per wave and round.  (Dword pieces into padded rows -- conflict-free column reads -- took 72 LDS-DMA
@@ -841,8 +747,7 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
                 // drain_vector_memory() at the end of the round.  No other instruction of this kernel uses m0.
                 const unsigned dst = __builtin_amdgcn_readfirstlane(
                     static_cast<unsigned>(reinterpret_cast<unsigned long long>(raw + 16 * (i * kRoleThreads + rw * 64))));
-                if constexpr (NT) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt" :: "v"(src), "s"(dst) : "memory", "m0");
-                else asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(dst) : "memory", "m0");
+                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(dst) : "memory", "m0");
             } else {
                 uint16_t h[8];                              // (any even stream address)
 #pragma unroll
@@ -857,9 +762,6 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
         }
     };
 #pragma clang diagnostic pop
-    // (knob 1 = 7 / 8, measurement: the consumer / producer waves at raised issue priority)
-    if (FKNOB(1) == 7 && !producer) __builtin_amdgcn_s_setprio(2);
-    if (FKNOB(1) == 8 && producer) __builtin_amdgcn_s_setprio(2);
     if (producer) {
         // ================================ producers: columns ====================================
         const int sub0 = lane / TA, t0 = lane % TA;
@@ -887,7 +789,6 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
         unsigned nbar = 0;
         drain_vector_memory();
         alive = role_barrier(sy, 0, (nbar += kRoleWaves), lane);          // the first round's raw rows are in
-        fclk.start();
 #pragma unroll 1
         for (int j = 0; j < nj && alive; ++j) {
             const int f = (xcd + 8 * j) * FR + fsl;
@@ -916,8 +817,7 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
                 }
             }
             if (!(alive = role_barrier(sy, 0, (nbar += kRoleWaves), lane))) break;
-            if (j + 1 < nj && f + 8 * FR < nframes && FKNOB(1) < 3) stage_rows(f + 8 * FR);     // (knob 1 = 3: no raw rows -- garbage in, timing only)
-            FSTAMP(0);                       // samples in registers, next rows on their way
+            if (j + 1 < nj && f + 8 * FR < nframes) stage_rows(f + 8 * FR);       // samples in registers, next rows on their way
             // Both column groups are transformed BEFORE the team's one buffer is free (the consumers are still loading
             // the previous round out of it): the second group waits in this wave's slab in natural k1 order, the
             // first in registers.
@@ -936,7 +836,7 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
                         if constexpr (WINDOW) x[a] = (v - (kTwo23 + 127.0f)) * wsgn[g][a];
                         else x[a] = v * sgn + off;
                     }
-                    if (!FKNOB(3)) group_fft_twlds<GA>(t, x, tw, slab, twtabA);
+                    group_fft_twlds<GA>(t, x, tw, slab, twtabA);
                     exchange_sync<false>();
                     if (g == 0) {
 #pragma unroll
@@ -949,62 +849,9 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
                     }
                 }
             }
-            FSTAMP(1);                       // both column groups transformed
-            // (knob 1 = 5: the next rows' LDS-DMA is issued here instead, under the wait for the buffer; 6: and the wave keeps
-            //  off the LDS until they have landed.  Both measured slower than the issue at the top of the round, 0.255 / 0.257
-            //  against 0.285 Tsample/s: profiles/r04_c4_fused.txt.)
-            if (FKNOB(1) >= 5 && j + 1 < nj && f + 8 * FR < nframes) stage_rows(f + 8 * FR);
-            if (FKNOB(1) == 6 && j < NBUF) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if constexpr (HALFF) {
-                // ---- half-frame form: group 1 (in the slab) goes out first, half by half, as the two half buffers come free;
-                // then group 0 -- and each half is signalled as soon as ITS stores have drained
-                auto store_half = [&](int g, int h, int b) {
-                    const int c = COLS * tl + (rw * S::SUBA + sub) * GROUPS + g;
-                    cf* const ycol = Yteam + static_cast<size_t>(b) * HB + static_cast<size_t>(c) * RT;
-#pragma unroll
-                    for (int a = h * (P / 4); a < (h + 1) * (P / 4); ++a) {
-                        const int e = 2 * t + 2 * TA * a;
-                        cf4 v;
-                        v.lo = slab[GA::slot(e)];
-                        v.hi = slab[GA::slot(e + 1)];
-                        *reinterpret_cast<cf4*>(ycol + static_cast<size_t>((e / RT) % HT) * (N2 * RT) + e % RT) = v;
-                    }
-                };
-                static_assert(P % 4 == 0 && (2 * TA * (P / 4)) % RT == 0 && (2 * TA * (P / 4)) / RT == HT, "the store loop splits at k1 = N1 / 2");
-                const int q0 = 2 * j, b0 = q0 % 3, b1 = (q0 + 1) % 3;
-                const unsigned u0 = static_cast<unsigned>(q0 / 3), u1 = static_cast<unsigned>((q0 + 1) / 3);
-                if (u0 > 0 && !(alive = team_wait(ctl, sy, &ctl->consumed[xcd][b0][0], &sy->seen[0][b0], 16u * u0, rw == 0, lane))) break;
-                FTRACE(3);
-                FSTAMP(2);                   // wait: first half buffer free
-                if (valid) store_half(1, 0, b0);
-                if (u1 > 0 && !(alive = team_wait(ctl, sy, &ctl->consumed[xcd][b1][0], &sy->seen[0][b1], 16u * u1, rw == 0, lane))) break;
-                if (valid) {
-                    store_half(1, 1, b1);
-                    exchange_sync<false>();
-#pragma unroll
-                    for (int a = 0; a < P; ++a) slab[GA::slot(bin_of<GA>(t, a))] = y0[a];
-                    exchange_sync<false>();
-                    store_half(0, 0, b0);
-                }
-                drain_vector_memory();
-                if (!(alive = role_barrier(sy, 0, (nbar += kRoleWaves), lane))) break;
-                if (rw == 0 && lane == 0)
-                    __hip_atomic_fetch_add(&ctl->produced[xcd][b0][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                FSTAMP(3);                   // first half stored, drained, signalled
-                if (valid) {
-                    store_half(0, 1, b1);
-                    exchange_sync<false>();
-                }
-                drain_vector_memory();
-                if (!(alive = role_barrier(sy, 0, (nbar += kRoleWaves), lane))) break;
-                if (rw == 0 && lane == 0)
-                    __hip_atomic_fetch_add(&ctl->produced[xcd][b1][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else {
-            // the team has finished reading round j - NBUF out of the buffer
-            if (j >= NBUF && !(alive = team_wait(ctl, sy, &ctl->consumed[xcd][j % NBUF][0], &sy->seen[0][j % NBUF], 32u * (j / NBUF),
-                                                 rw == 0, lane, FKNOB(1) == 6))) break;
-            FTRACE(3);
-            FSTAMP(2);                       // wait: buffer free
+            // the team has finished reading round j - 2 out of the buffer
+            if (j >= 2 && !(alive = team_wait(ctl, sy, &ctl->consumed[xcd][j % 2][0], &sy->seen[0][j % 2], 32u * (j / 2),
+                                              rw == 0, lane))) break;
             if (valid) {
 #pragma unroll
                 for (int g = GROUPS - 1; g >= 0; --g) {
@@ -1014,14 +861,15 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
                         for (int a = 0; a < P; ++a) slab[GA::slot(bin_of<GA>(t, a))] = y0[a];
                         exchange_sync<false>();
                     }
-                    cf* const ycol = Yteam + static_cast<size_t>(j % NBUF) * FR * N + static_cast<size_t>(c) * RT;      // tile-major, like K2a
+                    cf* const ycol = Yteam + static_cast<size_t>(j % 2) * FR * N + static_cast<size_t>(c) * RT;      // tile-major, like K2a
 #pragma unroll
                     for (int a = 0; a < P / 2; ++a) {
                         const int e = 2 * t + 2 * TA * a;
                         cf4 v;
                         v.lo = slab[GA::slot(e)];
                         v.hi = slab[GA::slot(e + 1)];
-                        *reinterpret_cast<cf4*>(ycol + static_cast<size_t>((e / RT + YROT) % TPF) * (N2 * RT) + e % RT) = v;
+                        // (the modulo is a no-op, kept so that the compiled kernel is commit aba7fc0's)
+                        *reinterpret_cast<cf4*>(ycol + static_cast<size_t>((e / RT) % TPF) * (N2 * RT) + e % RT) = v;
                     }
                     exchange_sync<false>();
                 }
@@ -1029,15 +877,10 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
             // The round's rows of Y sit in the team's L2 once every producer wave's stores have drained (plain stores:
             // the lines stay there, dirty -- profiles/r04_l2_residency.txt); the next round's raw rows landed long ago.
             drain_vector_memory();
-            FSTAMP(3);                       // stores issued and drained
             if (!(alive = role_barrier(sy, 0, (nbar += kRoleWaves), lane))) break;
             if (rw == 0 && lane == 0)
-                __hip_atomic_fetch_add(&ctl->produced[xcd][j % NBUF][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            FTRACE(0);
-            FSTAMP(4);                       // arrived
+                __hip_atomic_fetch_add(&ctl->produced[xcd][j % 2][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-        fclk.publish(0, rw == 0 && lane == 0, 32 * xcd + rank);
     } else {
         // ================================ consumers: rows =======================================
         const int sub = lane / TB, t = lane % TB;
@@ -1053,21 +896,16 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
         constexpr int PERB = N2 * RT / kRoleThreads / 2;     // 16-byte loads per thread and tile
         typedef float f4 __attribute__((ext_vector_type(4)));
         unsigned nbar = 0;
-        fclk.start();
 #pragma unroll 1
         for (int j = 0; j < nj && alive; ++j) {
             const int f = (xcd + 8 * j) * FR + fsl;
             const bool valid = f < nframes;
-            // (half-frame form: this workgroup's tile lies in half h of the round, half round q = 2 j + h, buffer q mod 3)
-            const int hq = HALFF ? 2 * j + tl / (HT > 0 ? HT : 1) : j;
-            const int cb = HALFF ? hq % 3 : j % NBUF;
-            const unsigned cu = static_cast<unsigned>(HALFF ? hq / 3 : j / NBUF);
+            const int cb = j % 2;                                      // the round's buffer
+            const unsigned cu = static_cast<unsigned>(j / 2);          // rounds that have used it before
             if (!(alive = team_wait(ctl, sy, &ctl->produced[xcd][cb][0], &sy->seen[1][cb], 32u * (cu + 1), rw == 0, lane))) break;
-            FTRACE(1);
-            FSTAMP(0);                       // wait: round produced
             if (valid) {
-                const cf* const yt = HALFF ? Yteam + static_cast<size_t>(cb) * HB + static_cast<size_t>(tl % (HT > 0 ? HT : 1)) * (N2 * RT)
-                                           : Yteam + static_cast<size_t>(j % NBUF) * FR * N + static_cast<size_t>((tl + YROT) % TPF) * (N2 * RT);
+                // (the modulo is a no-op, kept so that the compiled kernel is commit aba7fc0's)
+                const cf* const yt = Yteam + static_cast<size_t>(j % 2) * FR * N + static_cast<size_t>(tl % TPF) * (N2 * RT);
                 // sc1 loads: served by the L2, never by this CU's L1 (other CUs wrote these lines); 16 bytes per lane,
                 // all eight of a thread's loads in flight -- and the wait for them in the SAME asm statement: the
                 // compiler does not know that an asm load's destination is written when the data returns, and is free
@@ -1077,35 +915,19 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
                 const cf* src[PERB];
 #pragma unroll
                 for (int i = 0; i < PERB; ++i) src[i] = yt + 2 * (i * kRoleThreads + rtid);
-                if constexpr (NT == 1) {
-                    asm volatile(
-                        "global_load_dwordx4 %0, %8, off sc1 nt\n\t"
-                        "global_load_dwordx4 %1, %9, off sc1 nt\n\t"
-                        "global_load_dwordx4 %2, %10, off sc1 nt\n\t"
-                        "global_load_dwordx4 %3, %11, off sc1 nt\n\t"
-                        "global_load_dwordx4 %4, %12, off sc1 nt\n\t"
-                        "global_load_dwordx4 %5, %13, off sc1 nt\n\t"
-                        "global_load_dwordx4 %6, %14, off sc1 nt\n\t"
-                        "global_load_dwordx4 %7, %15, off sc1 nt\n\t"
-                        "s_waitcnt vmcnt(0)"
-                        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-                        : "v"(src[0]), "v"(src[1]), "v"(src[2]), "v"(src[3]), "v"(src[4]), "v"(src[5]), "v"(src[6]), "v"(src[7])
-                        : "memory");
-                } else {
-                    asm volatile(
-                        "global_load_dwordx4 %0, %8, off sc1\n\t"
-                        "global_load_dwordx4 %1, %9, off sc1\n\t"
-                        "global_load_dwordx4 %2, %10, off sc1\n\t"
-                        "global_load_dwordx4 %3, %11, off sc1\n\t"
-                        "global_load_dwordx4 %4, %12, off sc1\n\t"
-                        "global_load_dwordx4 %5, %13, off sc1\n\t"
-                        "global_load_dwordx4 %6, %14, off sc1\n\t"
-                        "global_load_dwordx4 %7, %15, off sc1\n\t"
-                        "s_waitcnt vmcnt(0)"
-                        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
-                        : "v"(src[0]), "v"(src[1]), "v"(src[2]), "v"(src[3]), "v"(src[4]), "v"(src[5]), "v"(src[6]), "v"(src[7])
-                        : "memory");
-                }
+                asm volatile(
+                    "global_load_dwordx4 %0, %8, off sc1\n\t"
+                    "global_load_dwordx4 %1, %9, off sc1\n\t"
+                    "global_load_dwordx4 %2, %10, off sc1\n\t"
+                    "global_load_dwordx4 %3, %11, off sc1\n\t"
+                    "global_load_dwordx4 %4, %12, off sc1\n\t"
+                    "global_load_dwordx4 %5, %13, off sc1\n\t"
+                    "global_load_dwordx4 %6, %14, off sc1\n\t"
+                    "global_load_dwordx4 %7, %15, off sc1\n\t"
+                    "s_waitcnt vmcnt(0)"
+                    : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
+                    : "v"(src[0]), "v"(src[1]), "v"(src[2]), "v"(src[3]), "v"(src[4]), "v"(src[5]), "v"(src[6]), "v"(src[7])
+                    : "memory");
                 // the previous round's columns have left the tile (arrivals posted long ago: see below)
                 if (!(alive = role_wait(sy, 2, static_cast<unsigned>(kRoleWaves) * j))) break;
 #pragma unroll
@@ -1116,13 +938,10 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
                     dst[1] = cf{v[i].z, v[i].w};
                 }
             }
-            FSTAMP(1);                       // tile loaded
             if (!(alive = role_barrier(sy, 1, (nbar += kRoleWaves), lane))) break;
             // every consumer wave's loads have returned: the team may overwrite the buffer
             if (rw == 0 && lane == 0)
                 __hip_atomic_fetch_add(&ctl->consumed[xcd][cb][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            FTRACE(2);
-            FSTAMP(2);
             if (valid) {
 #pragma unroll
                 for (int g = 0; g < GROUPS; ++g) {
@@ -1134,16 +953,14 @@ __global__ __launch_bounds__(kWG, 4) void fourstep_fused_kernel(const uint8_t* _
                     // next round's tile write waits for all eight arrivals, by then long posted -- a barrier behind the
                     // transforms, where the waves are skewed, cost 1.5 us per round
                     if (g == GROUPS - 1) role_arrive(sy, 2, lane);
-                    if (!FKNOB(2)) group_fft_but_last<GB, true, fourstep_wide2<GB>(S::N)>(t, x, tw, slab, twtabB, widetab);
+                    group_fft_but_last<GB, true, fourstep_wide2<GB>(S::N)>(t, x, tw, slab, twtabB, widetab);
                     last_pass_accumulate<GB, fourstep_is_wide(S::N)>(x, acc[g]);
                     exchange_sync<false>();
                 }
             } else {
                 role_arrive(sy, 2, lane);
             }
-            FSTAMP(3);                       // rows transformed
         }
-        fclk.publish(8, rw == 0 && lane == 0, 32 * xcd + rank);
         // partial spectrum of (team, frame slot): the accumulators go through the tile area (the consumers' own: every
         // consumer wave has left its last round's column reads behind at that round's barrier) as [N2 k2][ROW_PITCH] doubles
         if (alive) {
@@ -1198,33 +1015,6 @@ __global__ __launch_bounds__(64) void fused_squatter_kernel(const FusedCtl* __re
     }
 }
 
-#ifdef RPF_FUSED_PROFILE
-}  // namespace
-}  // namespace rpf
-extern "C" int rpf_debug_fused_trace(unsigned long long* out)      // 256 x 64 x 4 values
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(rpf::g_fused_trace), sizeof(unsigned long long) * 256 * 64 * 4) == hipSuccess ? 0 : 1;
-}
-extern "C" int rpf_debug_fused_profile_wg(unsigned long long* out)      // 256 x 16 values
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(rpf::g_fused_prof_wg), sizeof(unsigned long long) * 256 * 16) == hipSuccess ? 0 : 1;
-}
-extern "C" int rpf_debug_fused_knobs(const int* four)
-{
-    return hipMemcpyToSymbol(HIP_SYMBOL(rpf::g_fused_knob), four, sizeof(int) * 4) == hipSuccess ? 0 : 1;
-}
-extern "C" int rpf_debug_fused_profile(unsigned long long* out16, int reset)
-{
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(rpf::g_fused_prof), sizeof(unsigned long long) * 16) != hipSuccess) return 1;
-    if (reset) {
-        unsigned long long z[16] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(rpf::g_fused_prof), z, sizeof z);
-    }
-    return 0;
-}
-namespace rpf {
-namespace {
-#endif
 
 
 // Large Bluestein path: even N in (4096, 131072] that is not a power of two,
@@ -1351,9 +1141,6 @@ struct SplitInfo {
     RowsTableFn step_twiddles;   // W_N^{n2 k1} in K2a's lane order
     FusedFn fused[2][2];         // [window][dma]
     int fused_lds, fused_fr;     // LDS bytes; frames per team round
-#ifdef RPF_FUSED_PROFILE
-    FusedFn fused_ab[4];         // measurement only (RPF_FUSED_MODE=0..3, rectangular + LDS-DMA): NBUF 2/2/1/2, NT both/none/none/raw rows only
-#endif
 };
 
 template <int N1, int N2>
@@ -1367,10 +1154,6 @@ SplitInfo make_split()
                      {{fourstep_fused_kernel<S, false, false>, fourstep_fused_kernel<S, false, true>},
                       {fourstep_fused_kernel<S, true, false>, fourstep_fused_kernel<S, true, true>}},
                      fused_lds_bytes<S>(), 262144 / S::N,
-#ifdef RPF_FUSED_PROFILE
-                     {fourstep_fused_kernel<S, false, true, 2, 1>, fourstep_fused_kernel<S, false, true, 2, 0>,
-                      fourstep_fused_kernel<S, false, true, 1, 0>, fourstep_fused_kernel<S, false, true, 2, 2>}
-#endif
     };
 }
 
@@ -1605,12 +1388,6 @@ hipError_t launch_fourstep_fused(int N, bool window, bool use_dma, const uint8_t
         if (__atomic_load_n(running, __ATOMIC_ACQUIRE) == 0) return hipErrorNotReady;      // (the squatter never started)
     }
     FusedFn fn = s->fused[window ? 1 : 0][use_dma ? 1 : 0];
-#ifdef RPF_FUSED_PROFILE
-    if (const char* mode = getenv("RPF_FUSED_MODE"); mode && !window && use_dma) {
-        fn = s->fused_ab[atoi(mode) & 3];
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, s->fused_lds);
-    }
-#endif
     // One fused launch at a time per device: the kernel needs every CU for itself (one 1024-thread workgroup with all of
     // the LDS per CU), and two of them dispatched side by side from two streams -- two engines on one device -- could each
     // hold CUs the other is waiting for until both give up.  Each launch waits for the previous one's event.

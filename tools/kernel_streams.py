@@ -13,7 +13,18 @@ so is the `, 0` of the defaulted `int LDW` behind it (a kernel with loader waves
 kernel, and the one it replaced is reported as different or missing); and so is the `, false, 0, false` that follows
 the sixth template argument (DMA, counting N and P of the Geom apart) of every K1 accumulate kernel (`fft_accum_*kernel<`)
 in a build that still has the three retired experiments' parameters ("Retired experiments"), so that such
-a build can be compared with one without them."""
+a build can be compared with one without them; and so is the `, 2, 0` of the defaulted `int NBUF, int NT` at the end of
+the fused four-step kernel's (`fourstep_fused_kernel<`) argument list in a build that still has those two retired
+experiments' parameters (Four-step, "Retired experiments": a kernel with another value, `, 1, 0` say, keeps
+it and is reported as different or missing).
+
+A kernel reaches its constant tables through a pc-relative address: `s_getpc_b64 s[LO:HI]`, then `s_add_u32 sLO, sLO,
+<literal>` / `s_addc_u32 sHI, sHI, <literal>`.  The literal is the distance from the instruction to the table and moves
+whenever the code object's layout does (a shorter mangled name is enough), with no instruction of the kernel changed.
+A second digest of every stream is therefore taken with the literals of exactly that pair masked -- the same
+instructions anywhere else, or on other registers, are left as they are -- and the two-library report counts and NAMES
+the kernels that are identical only under it (`identical_but_for_pc_relative_literal`), so that the mask cannot
+silently swallow a real difference."""
 import hashlib
 import json
 import os
@@ -27,7 +38,36 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
+def drop_fused_defaults(name):
+    """The demangled name without the `, 2, 0` of `fourstep_fused_kernel`'s retired `int NBUF = 2, int NT = 0`."""
+    if "fourstep_fused_kernel<" not in name:
+        return name
+    return re.sub(r", 2, 0>\(", ">(", name)
+
+
+PCREL = "<pc-relative>"
+
+
+def mask_pc_relative(lines):
+    """The instruction lines with the literals of `s_add_u32 sLO, sLO, <literal>` / `s_addc_u32 sHI, sHI, <literal>`
+    masked where the pair directly follows `s_getpc_b64 s[LO:HI]`; every other line as it is."""
+    out = list(lines)
+    for i, line in enumerate(lines):
+        m = re.match(r"^s_getpc_b64 s\[(\d+):(\d+)\]$", line)
+        if not m:
+            continue
+        pair = ["%s s%s, s%s, " % (op, reg, reg) for op, reg in (("s_add_u32", m.group(1)), ("s_addc_u32", m.group(2)))]
+        if all(re.match(re.escape(head) + r"\S+$", nxt) for head, nxt in zip(pair, lines[i + 1:i + 3] + ["", ""])):
+            out[i + 1:i + 3] = [head + PCREL for head in pair]
+    return out
+
+
+def digest(lines):
+    return hashlib.sha256("\n".join(lines).encode()).hexdigest()
+
+
 def streams(lib):
+    """{demangled name: (digest of the stream, its length, digest with the pc-relative literals masked)}"""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         fat = os.path.join(tmp, "fatbin")
@@ -64,24 +104,28 @@ def streams(lib):
             name = re.sub(r", (false|true), 0>\(", r", \1>(", name)      # the defaulted `int LDW` behind STATS
         if "fft_accum_kernel<" in name or "fft_accum_strided_kernel<" in name:
             name = re.sub(r", false>\(", ">(", name)
-        res[name] = (hashlib.sha256("\n".join(out[mangled]).encode()).hexdigest(), len(out[mangled]))
+        name = drop_fused_defaults(name)
+        res[name] = (digest(out[mangled]), len(out[mangled]), digest(mask_pc_relative(out[mangled])))
     return res
 
 
 def main():
     if len(sys.argv) == 2:
-        for name, (h, n) in sorted(streams(sys.argv[1]).items()):
+        for name, (h, n, _) in sorted(streams(sys.argv[1]).items()):
             print(h[:16], n, name)
         return 0
     a, b = streams(sys.argv[1]), streams(sys.argv[2])
     k1 = [n for n in a if "fft_accum" in n]
     other = [n for n in a if n not in k1]
+    pcrel = sorted(n for n in a if n in b and b[n] != a[n] and b[n][2] == a[n][2])
     rep = {"parent_kernels": len(a), "kernels": len(b),
            "k1_parent": len(k1), "k1_identical": sum(1 for n in k1 if b.get(n) == a[n]),
            "k1_instructions": sum(a[n][1] for n in k1),
            "other_parent": len(other), "other_identical": sum(1 for n in other if b.get(n) == a[n]),
+           "identical_but_for_pc_relative_literal": len(pcrel),
+           "identical_but_for_pc_relative_literal_names": pcrel,
            "new_kernels": sum(1 for n in b if n not in a),
-           "different_or_missing": sorted(n for n in a if b.get(n) != a[n])}
+           "different_or_missing": sorted(n for n in a if b.get(n) != a[n] and n not in pcrel)}
     print(json.dumps(rep, indent=1))
     return 0 if not rep["different_or_missing"] else 1
 
